@@ -2,6 +2,10 @@
 """bench.py -- iLQR-ADMM outer iterations per second on MI355X (BASELINE.json metric).
 
     python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run)
+    python bench.py ... --full                             (+ general-layout and shared-LTI legs, per-kernel events, roofline, CPU baseline)
+    python bench.py ... --dump-outputs DIR                 (+ the last timed step's results as DIR/<name>.npy, float64)
+
+A plain run sets up, warms up, times the K steps and prints the result line; everything else it can measure is behind --full.
 
 Workload (config 2 of BASELINE.json): 3-D double integrator iLQR-ADMM, fp64, per GPU
 B=4096 trajectories x N=100 steps, n=6, m=3, J=5 ADMM iterations per outer iteration, L=20 line-search
@@ -122,6 +126,28 @@ def iteration_bytes(n, m, N, w, hess_shared, has_x=True, has_u=True, ab_shared=F
     return w * N * (n * n + n * m + ab + m * m + m + 3 * (n + m) + zl - (n * n + m * m if hess_shared else 0))
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, per_trajectory, whole):
+    """`--dump-outputs DIR`: every array as DIR/<name>.npy in float64.  `per_trajectory` holds [B, ...] arrays (None entries are
+    skipped); when they and `whole` would exceed DUMP_LIMIT_BYTES, a fixed, seeded sample of trajectories is written (the same
+    rows of every array).  trajectory_index.npy names the rows written."""
+    host = {k: v.detach().cpu().numpy().astype(np.float64) for k, v in per_trajectory.items() if v is not None}
+    whole = {k: np.asarray(v, dtype=np.float64) for k, v in whole.items()}
+    B = next(iter(host.values())).shape[0]
+    row_bytes = 8 + sum(a[0].nbytes for a in host.values())          # + the row's entry in trajectory_index
+    headers = 1024 * (len(host) + len(whole) + 1)                     # .npy headers, generously
+    rows = max(1, (DUMP_LIMIT_BYTES - headers - sum(a.nbytes for a in whole.values())) // row_bytes)
+    idx = np.arange(B) if rows >= B else np.sort(np.random.default_rng(0).choice(B, int(rows), replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.ascontiguousarray(a[idx]))
+    for k, a in whole.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+    np.save(os.path.join(out_dir, "trajectory_index.npy"), idx.astype(np.float64))
+
+
 def spawn_ranks(n_gpus):
     """`python bench.py --gpus N` without a launcher: start `torch.distributed.run` with N ranks (one per GPU, RCCL) as a
     CHILD process and return its exit code.  Called before anything initialises the GPU; device_count() does not."""
@@ -157,7 +183,7 @@ def main():
     ap.add_argument("--lti", action="store_true", help="share A,B over batch and time (stride-0 views)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--only-timed-region", action="store_true",
-                    help="profiling: skip the general-layout and shared-LTI legs behind the timed region (counter passes then see its kernels only)")
+                    help="profiling with --full: skip the general-layout and shared-LTI legs behind the timed region (counter passes then see its kernels only)")
     ap.add_argument("--separate-launches", action="store_true",
                     help="A/B: accept, ADMM restart, linearisation and expansion as four launches instead of isls_outer_advance")
     ap.add_argument("--cpu-sample", type=int, default=0, help="trajectories in the CPU-baseline sample (0: auto)")
@@ -166,7 +192,15 @@ def main():
     ap.add_argument("--config5", action="store_true", help="secondary workload: SLS-ADMM with chance constraints (B=8192, N=50)")
     ap.add_argument("--config5-dim", type=int, default=1, help="double integrator dimension of the config-5 workload (1 or 3)")
     ap.add_argument("--isls-admm", action="store_true", help="secondary workload: iSLS.isls_admm on the 3R arm with robust control bounds")
+    ap.add_argument("--full", action="store_true",
+                    help="headline workload: also time the general-layout and shared-LTI legs, sample per-kernel HIP events in the "
+                         "timed region (kernels_ms_per_step, roofline) and time the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="headline workload: write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB; "
+                         "rank 0's trajectories when --gpus > 1)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.config5 or args.isls_admm or args.config in (3, 4)):
+        ap.error("--dump-outputs serves the headline workload only")
     if args.config5:
         return config5_main(args)
     if args.isls_admm:
@@ -176,6 +210,8 @@ def main():
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return spawn_ranks(args.gpus)                         # child launcher; nothing has touched the GPU yet
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -258,14 +294,17 @@ def main():
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
-    timing = lib.isls_timing_create()                        # caller-owned event context, handed to the C driver
-    eng._outer_args.timing = timing
-    lib.isls_timing_reset(timing)
+    timing = None
+    if args.full:
+        timing = lib.isls_timing_create()                    # caller-owned event context, handed to the C driver
+        eng._outer_args.timing = timing
+        lib.isls_timing_reset(timing)
     t0 = time.perf_counter()
     for i in range(args.steps):
-        # per-launch HIP events on every EVENT_PERIOD-th step of the timed region: an event pair per launch costs a
+        # --full: per-launch HIP events on every EVENT_PERIOD-th step of the timed region: an event pair per launch costs a
         # few microseconds of queue bubbles (measured: 2.03 ms per step with events on every step, 1.89 without)
-        lib.isls_timing_pause(timing, 0 if i % EVENT_PERIOD == 0 else 1)
+        if timing is not None:
+            lib.isls_timing_pause(timing, 0 if i % EVENT_PERIOD == 0 else 1)
         step()
     xch.finish()                                             # every exchange of the timed region is inside it
     if dist is not None:
@@ -280,13 +319,18 @@ def main():
 
     red_host = xch.finish().cpu().numpy()
     hess_shared = bool(eng._shared_hessian())
+    if args.dump_outputs and rank == 0:                      # before the --full legs below run more steps on the same engine
+        dump_outputs(args.dump_outputs, {
+            "x": eng.xhat, "u": eng.uhat, "cost": eng.cost,  # nominal trajectory after the last step's accept, and its cost
+            "z_u": eng.zu, "admm_residuals": eng.res,         # ADMM state the last step left (its lambda is restarted)
+            "status": eng.status}, {"convergence_table": red_host})
 
     # ---- the same workload in the GENERAL layout: time-varying A_t, B_t per trajectory read from HBM by the gain pass, whole
     # records by the feed-forward passes, A_t, B_t rewritten by every step -- what any model that is not a double integrator
     # (or a caller's get_AB) runs; the timed region above is the product's default path, which recognises the model
     structured = bool(eng._outer_args.ff.lin_on)               # what the timed region ran with
     general_it_per_s = None
-    if structured and not args.only_timed_region:
+    if structured and args.full and not args.only_timed_region:
         eng.use_model_structure = False
         step()
         if dist is not None:
@@ -309,7 +353,7 @@ def main():
 
     # ---- the same workload with A,B shared over batch and time (stride-0 views; SURVEY 8(d): "report both") ----
     lti_it_per_s = None
-    if not args.lti and not args.only_timed_region:
+    if not args.lti and args.full and not args.only_timed_region:
         eng.A = torch.as_tensor(cfg["A"], device=dev).reshape(1, 1, n, n)
         eng.Bm = torch.as_tensor(cfg["B"], device=dev).reshape(1, 1, n, m)
         eng.build_outer(L, J, tol_abs=0.0, tol_rel=0.0, begin_done=not args.separate_launches)
@@ -341,40 +385,20 @@ def main():
             dl = float(tl.item())
         lti_it_per_s = world * args.steps / dl
 
-    # ---- per-kernel-family durations from the HIP events recorded on the launch stream ------------
-    fam = []
-    for kind in range(5):
-        cnt = ctypes.c_int(0)
-        ms = lib.isls_timing_read_ms(timing, kind, ctypes.byref(cnt))
-        fam.append((ms, cnt.value))
-    lib.isls_timing_destroy(timing)
+    # ---- --full: per-kernel-family durations from the HIP events recorded on the launch stream ------------
+    fam = None
+    if timing is not None:
+        fam = []
+        for kind in range(5):
+            cnt = ctypes.c_int(0)
+            ms = lib.isls_timing_read_ms(timing, kind, ctypes.byref(cnt))
+            fam.append((ms, cnt.value))
+        lib.isls_timing_destroy(timing)
 
     if rank == 0:
         it_per_s = world * args.steps / dt
-        w = 8
-        records = eng.ff_record() is not None
-        gain_ff = fam[1][1] < fam[2][1]                         # fewer ff launches than rollouts: the first pass rode on the gain pass
-        has_x, has_u = eng.zx is not None, eng.zu is not None
-        abytes = algorithmic_bytes(n, m, N, w, has_x=has_x, has_u=has_u, lti=args.lti, hess_shared=hess_shared, records=records,
-                                   gain_ff=gain_ff, structured=structured)
-        nseg_ff = max(1, int(eng._outer_args.ff.seg.nseg))
-        abytes[4] = abytes[4] * (nseg_ff - 1) / nseg_ff          # the operators cover every segment but the last
-        sampled = len(range(0, args.steps, EVENT_PERIOD))
-        dom = int(np.argmax([ms for ms, _ in fam]))
-        default_workload = (B, N, J, L) == (4096, 100, 5, 20) and not args.lti
-        avg_ms = fam[dom][0] / max(1, fam[dom][1])
-        achieved = abytes[dom] * B / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-        it_bytes = iteration_bytes(n, m, N, w, hess_shared, has_x=has_x, has_u=has_u, ab_shared=structured or args.lti) * B
-        # every kernel family against the same HBM figure (algorithmic bytes / event-timed launch) with the PMC-measured
-        # traffic of the committed profile next to it: the rollout is issue bound, the feed-forward pass is the one that streams
-        families = {}
-        for k in range(5):
-            avg = fam[k][0] / max(1, fam[k][1])
-            ach = abytes[k] * B / (avg * 1e-3) / 1e9 if avg > 0 else 0.0
-            pmc = pmc_traffic(k, structured) if default_workload else None
-            families[KIND_NAMES[k]] = {"avg_launch_ms": avg, "algorithmic_bytes_per_launch": abytes[k] * B, "achieved": ach,
-                                       "frac": ach / HBM_PEAK_GBS, "pmc_bytes": pmc,
-                                       "pmc_over_algorithmic": (pmc / (abytes[k] * B) if pmc and abytes[k] else None)}
+        # fewer ff launches than rollouts: the first pass rode on the gain pass (counted by the events of --full)
+        gain_ff = fam[1][1] < fam[2][1] if fam is not None else None
         out = {
             "metric": "iLQR-ADMM iterations/sec, batch=4096 N=100 x_dim=6",
             "value": it_per_s, "unit": "iterations/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -392,26 +416,48 @@ def main():
                                          "SURVEY 8d: Cxx,Cuu terms dropped)" if hess_shared else "per trajectory [B,N,n,n]"),
                        "early_exit": False, "lti_stride0_layout_iterations_per_s": lti_it_per_s,
                        "ff_time_parallel_segments": max(1, int(eng._outer_args.ff.seg.nseg)),
-                       "first_ff_pass_inside_gain_pass": bool(gain_ff), "trajectory_iterations_per_s": it_per_s * B,
+                       "first_ff_pass_inside_gain_pass": gain_ff, "trajectory_iterations_per_s": it_per_s * B,
                        "admm_iterations_per_s": it_per_s * J},
-            "roofline": {"bound": "hbm", "kernel": KIND_NAMES[dom], "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": pmc_traffic(dom, structured) if default_workload else None,
-                         "avg_launch_ms": avg_ms, "algorithmic_bytes_per_launch": abytes[dom] * B,
-                         "iteration_algorithmic_bytes": it_bytes,
-                         "iteration_frac": it_bytes * (it_per_s / world) / 1e9 / HBM_PEAK_GBS,
-                         # every kernel family against the same HBM figure (algorithmic bytes / event-timed launch): the
-                         # rollout is issue bound, the feed-forward pass is the one that streams
-                         "pmc_profile": os.path.basename(PMC_FILE) if (PMC_FILE and default_workload) else None,
-                         "pmc_tree": pmc_tree() if default_workload else None,
-                         "families": families},
-            "kernels_ms_per_step": {KIND_NAMES[k]: fam[k][0] / sampled for k in range(5)},
-            "launches_per_step": {KIND_NAMES[k]: fam[k][1] / sampled for k in range(5)},
-            "event_sampled_steps": sampled,
             "convergence": {"sum_cost": float(red_host[:, 0].sum()), "max_prim": float(red_host[:, 1].max()),
                             "max_dual": float(red_host[:, 2].max()), "active": float(red_host[:, 3].sum()),
                             "failed": float(red_host[:, 4].sum())},
         }
+        if fam is not None:
+            w = 8
+            records = eng.ff_record() is not None
+            has_x, has_u = eng.zx is not None, eng.zu is not None
+            abytes = algorithmic_bytes(n, m, N, w, has_x=has_x, has_u=has_u, lti=args.lti, hess_shared=hess_shared, records=records,
+                                       gain_ff=gain_ff, structured=structured)
+            nseg_ff = max(1, int(eng._outer_args.ff.seg.nseg))
+            abytes[4] = abytes[4] * (nseg_ff - 1) / nseg_ff          # the operators cover every segment but the last
+            sampled = len(range(0, args.steps, EVENT_PERIOD))
+            dom = int(np.argmax([ms for ms, _ in fam]))
+            default_workload = (B, N, J, L) == (4096, 100, 5, 20) and not args.lti
+            avg_ms = fam[dom][0] / max(1, fam[dom][1])
+            achieved = abytes[dom] * B / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+            it_bytes = iteration_bytes(n, m, N, w, hess_shared, has_x=has_x, has_u=has_u, ab_shared=structured or args.lti) * B
+            # every kernel family against the same HBM figure (algorithmic bytes / event-timed launch) with the PMC-measured
+            # traffic of the committed profile next to it: the rollout is issue bound, the feed-forward pass is the one that streams
+            families = {}
+            for k in range(5):
+                avg = fam[k][0] / max(1, fam[k][1])
+                ach = abytes[k] * B / (avg * 1e-3) / 1e9 if avg > 0 else 0.0
+                pmc = pmc_traffic(k, structured) if default_workload else None
+                families[KIND_NAMES[k]] = {"avg_launch_ms": avg, "algorithmic_bytes_per_launch": abytes[k] * B, "achieved": ach,
+                                           "frac": ach / HBM_PEAK_GBS, "pmc_bytes": pmc,
+                                           "pmc_over_algorithmic": (pmc / (abytes[k] * B) if pmc and abytes[k] else None)}
+            out["roofline"] = {"bound": "hbm", "kernel": KIND_NAMES[dom], "achieved": achieved, "peak": HBM_PEAK_GBS,
+                               "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                               "traffic": pmc_traffic(dom, structured) if default_workload else None,
+                               "avg_launch_ms": avg_ms, "algorithmic_bytes_per_launch": abytes[dom] * B,
+                               "iteration_algorithmic_bytes": it_bytes,
+                               "iteration_frac": it_bytes * (it_per_s / world) / 1e9 / HBM_PEAK_GBS,
+                               "pmc_profile": os.path.basename(PMC_FILE) if (PMC_FILE and default_workload) else None,
+                               "pmc_tree": pmc_tree() if default_workload else None,
+                               "families": families}
+            out["kernels_ms_per_step"] = {KIND_NAMES[k]: fam[k][0] / sampled for k in range(5)}
+            out["launches_per_step"] = {KIND_NAMES[k]: fam[k][1] / sampled for k in range(5)}
+            out["event_sampled_steps"] = sampled
         # what the collective layer saw: ranks that joined the process group (1 without one) and the RCCL build
         out["n_ranks_joined"] = int(dist.get_world_size()) if dist is not None else 1
         out["collective_backend"] = (dist.get_backend() if dist is not None else None)
@@ -421,8 +467,9 @@ def main():
             out["rccl_version"] = None
         if REHEARSAL:
             out["rehearsal"] = True                             # N ranks on one device over gloo: exercises the code path, measures nothing
-        # the CPU baseline is timed on rank 0 at N = 1 only (the key is present, null, on the N > 1 lines)
-        out["cpu_baseline"] = cpu_baseline(cfg, args, B, N, n, m, J, L) if (not args.no_cpu_baseline and world == 1) else None
+        # --full: the CPU baseline is timed on rank 0 at N = 1 only (the key is present, null, on the other lines)
+        out["cpu_baseline"] = (cpu_baseline(cfg, args, B, N, n, m, J, L)
+                               if (args.full and not args.no_cpu_baseline and world == 1) else None)
         print(json.dumps(out))
     if dist is not None:
         dist.destroy_process_group()

@@ -107,7 +107,7 @@ def test_bench_two_rank_rehearsal():
     env = dict(os.environ, ISLS_BENCH_REHEARSAL="1")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "300",
-                        "--horizon", "40"], env=env, capture_output=True, text=True, timeout=600)
+                        "--horizon", "40", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

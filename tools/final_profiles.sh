@@ -4,7 +4,7 @@ set -e
 out=gpurun_out/$1; tag=$2
 mkdir -p "$out"
 tools/pmc_headline.sh "$1/pmc" "$tag"
-python bench.py > "$out/bench.json" 2> "$out/bench.err"
+python bench.py --full > "$out/bench.json" 2> "$out/bench.err"
 for c in 3 4; do
   python bench.py --config $c > "$out/config${c}_bench.json" 2> "$out/config${c}.err"
   rocprofv3 --kernel-trace --stats --output-format csv -d "$out/config${c}_stats" -o s -- python3 bench.py --config $c --no-cpu-baseline > /dev/null 2> "$out/config${c}_stats.log"
