@@ -80,6 +80,7 @@ class OracleDriver:
         self.res, self.res_prev = z(B, 2), z(B, 2)
         self.outer_active = np.ones(B, dtype=np.int32)
         self.admm_active = np.ones(B, dtype=np.int32)
+        self.iters = np.zeros(B, dtype=np.int32)          # ADMM iterations the driver ran (run_c)
         self.cost_log = [[] for _ in range(B)]
         # initial cost (nominal_values setter, isls/isls_base.py:80-85)
         self.kern.expand_quadratic(pa["Qtab"], pa["ztab"], pa["seq"], pa["u_std"], self.c0x, self.c0u,
@@ -146,9 +147,10 @@ class OracleDriver:
                               relax=self.relax, tol_abs=tol, tol_rel=tol, res_prev=self.res_prev,
                               active=self.admm_active)
 
-    def run_c(self, L, J, tol=0.0, log=None):
+    def run_c(self, L, J, tol=0.0, log=None, accept_kw=None):
         """One outer iteration through the library's own driver entry point (`*_ilqr_admm_outer`):
-        linearise + expand, then gain -> J x [ff -> rollout -> update] in one C call, then accept."""
+        linearise + expand, then gain -> J x [ff -> rollout -> update] in one C call, then accept (accept_kw: the cost-log tail
+        and the stop rules of `accept_step`, as iSLS.ilqr_admm runs it)."""
         pa, K = self.pa, capi.Kernels
         alphas = ALPHAS[:L].astype(self.dtype)
         self.linearize_expand()
@@ -167,12 +169,13 @@ class OracleDriver:
                            x_hi=pa.get("x_hi") if self.zx is not None else None,
                            u_lo=pa["u_lo"] if self.zu is not None else None,
                            u_hi=pa["u_hi"] if self.zu is not None else None,
-                           relax=self.relax, tol_abs=tol, tol_rel=tol, res_prev=self.res_prev, active=self.admm_active)
+                           relax=self.relax, tol_abs=tol, tol_rel=tol, res_prev=self.res_prev, active=self.admm_active,
+                           iters=self.iters)
         self._keep = (alphas,)
         sfx = "f64" if self.dtype == np.float64 else "f32"
         self.kern.outer(gain, ff, ro, admm, J, sfx, log=log, outer_active=self.outer_active)
         self.kern.accept_step(self.xx, self.xu, self.cost_new, self.xhat, self.uhat, self.cost,
-                              outer_active=self.outer_active)
+                              outer_active=self.outer_active, **(accept_kw or {}))
 
     def run(self, max_iter, L, J, tol):
         """Returns trace[outer] = dict(K, k[J], xx[J], xu[J], regx[J], regu[J], logs[J,B,2], cost[B], z.., n_inner[B])."""
@@ -231,6 +234,69 @@ def rel_err(a, b):
     return float(np.max(np.abs(a - b)) / max(1.0, float(np.max(np.abs(b)))))
 
 
+def _per_trajectory(got, ref, floor):
+    got, ref = np.asarray(got), np.asarray(ref)
+    if got.shape != ref.shape:
+        raise AssertionError(f"shape {got.shape} != oracle {ref.shape}")
+    rows = ref.shape[0] if ref.ndim else 1
+    cols = ref.size // rows if rows else 0
+    g, r = got.astype(np.float64).reshape(rows, cols), ref.astype(np.float64).reshape(rows, cols)
+    same = (g == r) | (np.isnan(g) & np.isnan(r))
+    bad = ~same & ~(np.isfinite(g) & np.isfinite(r))
+    mag = np.where(np.isfinite(r), np.abs(r), 0.0)
+    scale = np.maximum(mag.max(axis=1, initial=0.0), floor * max(1.0, float(mag.max(initial=0.0))))
+    with np.errstate(invalid="ignore"):
+        diff = np.where(same | bad, 0.0, np.abs(g - r))
+    return g, r, bad, diff, scale
+
+
+def batched_errors(got, ref, floor=1e-3):
+    """[B] per-trajectory relative errors (the measure of compare_batched); inf where a non-finite value differs."""
+    _, _, bad, diff, scale = _per_trajectory(got, ref, floor)
+    err = diff.max(axis=1, initial=0.0) / scale
+    err[bad.any(axis=1)] = np.inf
+    return err
+
+
+def compare_batched(name, got, ref, tol, floor=1e-3):
+    """Worst per-trajectory relative error of `got` against `ref` (axis 0 = trajectory); AssertionError above `tol`.
+    The scale of trajectory b is max(max|ref_b|, floor * max(1, max|ref|)): never larger than rel_err's, so a wrong slot whose
+    values are small next to the batch maximum still shows.  A non-finite value in `got` fails unless `ref` holds the same
+    one in the same place (identical infinities and NaNs agree).  The message names the array, the trajectory, the index
+    within it and both values."""
+    try:
+        g, r, bad, diff, scale = _per_trajectory(got, ref, floor)
+    except AssertionError as exc:
+        raise AssertionError(f"{name}: {exc}") from None
+    if r.size == 0:
+        return 0.0
+    inner = np.shape(ref)[1:]
+
+    def where(b, i):
+        idx = tuple(int(j) for j in np.unravel_index(i, inner)) if inner else ()
+        return f"{name}: trajectory {int(b)}, index {idx}: oracle={r[b, i].item()!r} got={g[b, i].item()!r}"
+    if bad.any():
+        b, i = np.unravel_index(int(np.argmax(bad)), bad.shape)
+        raise AssertionError("non-finite mismatch: " + where(b, i))
+    err = diff.max(axis=1) / scale
+    b = int(np.argmax(err))
+    if not err[b] <= tol:
+        i = int(np.argmax(diff[b]))
+        raise AssertionError(f"per-trajectory rel err {err[b]:.3e} > {tol:.1e} (scale {scale[b]:.3e}): " + where(b, i))
+    return float(err[b])
+
+
+def compare_exact(name, got, ref):
+    """Integer state (winner index, status, activity flags, iteration counts): equal element by element."""
+    got, ref = np.asarray(got), np.asarray(ref)
+    if got.shape != ref.shape or not np.array_equal(got, ref):
+        if got.shape != ref.shape:
+            raise AssertionError(f"{name}: shape {got.shape} != oracle {ref.shape}")
+        idx = np.argwhere(got != ref)
+        first = tuple(int(j) for j in idx[0])
+        raise AssertionError(f"{name}: {len(idx)} mismatches, first at {first}: oracle={ref[first].item()!r} got={got[first].item()!r}")
+
+
 def tassa_arrays(g, bsel, dtype=np.float64):
     """problem_arrays for the Tassa car-parking golden case (tests/golden/g8_tassa.npz): model ISLS_MODEL_TASSA, cost
     ISLS_COST_PHUBER, nominal = open-loop rollout of the recorded u0 from x0 (the notebook's get_trajectory_batch)."""
@@ -250,7 +316,9 @@ def outer_iteration_on_device(cfg, bsel, hip, oracle_kern, L, J, rho_u, relax=1.
                               structured=False):
     """One outer DP-form iLQR-ADMM iteration through the library's own driver (`isls_ilqr_admm_outer_*`: gain pass with the
     first feed-forward pass inside, J x [ff -> rollout with the fused ADMM update]) on the device, and the same through the
-    oracle's driver on the host; returns the worst relative error over K, k, the x-step, z, lambda and the residuals.
+    oracle's driver on the host; returns the worst per-trajectory relative error (compare_batched) over K, k, the x-step, z,
+    lambda, the residuals, the accepted nominal and its cost, and asserts the integer state (winner index, status, activity
+    flags, ADMM iteration counts) equal.
     dtype "f64" / "f32" selects isls_ilqr_admm_outer_f64 / _f32 (and the oracle of the same precision); outer_iters > 1 repeats
     the iteration (linearise + expand, driver call, accept) so that the gain pass also sees a moved nominal.  scramble_best (a
     seed): the `best` array the rollout reads as its PREDICTION of the winner is filled with random candidate indices first, so
@@ -285,7 +353,7 @@ def outer_iteration_on_device(cfg, bsel, hip, oracle_kern, L, J, rho_u, relax=1.
                         pa["u_std"], h.xx, h.xu, best=h.best, cost_new=h.cost_new, wr=h.wr[:1], zu=h.zu, lu=h.lu, cost_cur=h.cost,
                         status=h.status, active=h.admm_active)
     admm = K.admm_args(h.xx, h.xu, h.res, zu=h.zu, lu=h.lu, u_lo=pa["u_lo"], u_hi=pa["u_hi"], relax=h.relax, tol_abs=0.0,
-                       tol_rel=0.0, res_prev=h.res_prev, active=h.admm_active)
+                       tol_rel=0.0, res_prev=h.res_prev, active=h.admm_active, iters=h.iters)
     for it_ in range(outer_iters):
         h.linearize_expand()
         if scramble_best is not None:
@@ -293,4 +361,8 @@ def outer_iteration_on_device(cfg, bsel, hip, oracle_kern, L, J, rho_u, relax=1.
         hip.outer(gain, ff, ro, admm, J, dtype, outer_active=h.outer_active)
         hip.accept_step(h.xx, h.xu, h.cost_new, h.xhat, h.uhat, h.cost, outer_active=h.outer_active)
     torch.cuda.synchronize()
-    return max(rel_err(getattr(h, name).cpu().numpy(), getattr(o, name)) for name in ("K", "k", "xx", "xu", "zu", "lu", "res", "xhat", "uhat", "cost"))
+    for name in ("best", "status", "outer_active", "admm_active", "iters"):
+        compare_exact(name, getattr(h, name).cpu().numpy(), getattr(o, name))
+    # every array through the per-trajectory criterion; np.max keeps a NaN that Python's max() would drop after a finite value
+    return float(np.max([compare_batched(name, getattr(h, name).cpu().numpy(), getattr(o, name), np.inf)
+                         for name in ("K", "k", "xx", "xu", "zu", "lu", "res", "xhat", "uhat", "cost")]))

@@ -49,11 +49,12 @@ def test_vectorised_nominal_equals_the_per_trajectory_one():
             assert np.array_equal(xs[i], x1) and np.array_equal(us[i], u1)
 
 
-def test_config3_full_size_properties(monkeypatch):
+@pytest.mark.parametrize("nseg", ["3", "1"])
+def test_config3_full_size_properties(monkeypatch, nseg):
     """Config 3: 3R arm, B = 4096, N = 100, n = 9, state + control boxes (the notebook's call: 5 candidates, 10 ADMM
-    iterations per outer iteration)."""
+    iterations per outer iteration).  nseg "1": the sequential passes on the arm's structure (lean records) in both batches."""
     from isls import Box
-    monkeypatch.setenv("ISLS_FF_NSEG", "3")                       # same feed-forward segmentation in both batch sizes
+    monkeypatch.setenv("ISLS_FF_NSEG", nseg)                      # same feed-forward segmentation in both batch sizes
     B = 4096
     cfg = P.config3(batch=B, N=100, seed=0)
     kw = dict(project_x=Box(cfg["x_lo"], cfg["x_hi"]), project_u=Box(cfg["u_lo"], cfg["u_hi"]), max_iter=2,
@@ -66,6 +67,8 @@ def test_config3_full_size_properties(monkeypatch):
     small = _make(cfg, sel)
     small.ilqr_admm(**kw)
     e, es = big.engine, small.engine
+    if nseg == "1":
+        assert e._outer_args.gain.lin_on == 1 and e._outer_args.ff.lin_on == 1 and es._outer_args.gain.lin_on == 1
     for name in ("xhat", "uhat", "K", "k", "zx", "lx", "zu", "lu", "cost"):
         assert np.array_equal(getattr(e, name)[sel].cpu().numpy(), getattr(es, name).cpu().numpy()), name
     zx, zu = e.zx.cpu().numpy(), e.zu.cpu().numpy()

@@ -23,6 +23,8 @@ def dual(oracle):
 def _report(dk):
     worst = sorted(dk.max_err.items(), key=lambda kv: -kv[1])[:6]
     print("calls", dk.calls, "worst:", ", ".join(f"{k}={v:.1e}" for k, v in worst))
+    worst = sorted(dk.max_err_traj.items(), key=lambda kv: -kv[1])[:6]
+    print("  per trajectory:", ", ".join(f"{k}={v:.1e}" for k, v in worst))
 
 
 @pytest.mark.parametrize("B,ff_nseg", [(1, 1), (7, 1), (23, 1), (7, 4), (23, 5)])

@@ -572,15 +572,18 @@ def test_admm_lqt_dp_with_convex_sets(golden):
     assert rel(outs[0][1], outs[1][1]) < 1e-6 and np.max(np.abs(outs[1][1])) < 5.0 + 1e-4
 
 
-def test_headline_size_properties(monkeypatch):
+@pytest.mark.parametrize("nseg", ["3", "1"])
+def test_headline_size_properties(monkeypatch, nseg):
     """BASELINE.json's full size (B = 4096, N = 100, n = 6, m = 3, fp64) through size-independent properties:
     batch invariance (a trajectory solved inside the 4096-batch equals the same trajectory solved in a batch of 5, bit for
     bit: slots never interact), the consensus variable is inside the box exactly, every cost is finite and below the
-    initial one, no status bit is raised, and the ADMM primal residual does not grow over the inner iterations."""
+    initial one, no status bit is raised, and the ADMM primal residual does not grow over the inner iterations.
+    nseg "3": the time-parallel feed-forward passes (dense records) in both batches; "1": the sequential passes on the model's
+    structure (lean records) in both -- the form bench.py times."""
     from isls import Box
-    # the engine picks the number of time-parallel feed-forward segments from the batch size (3 at B >= 4096, else 4), which
-    # changes the association of a few sums; with the same segmentation the results are bit-identical
-    monkeypatch.setenv("ISLS_FF_NSEG", "3")
+    # the engine picks the number of time-parallel feed-forward segments from the batch size, which changes the association
+    # of a few sums; with the same segmentation the results are bit-identical
+    monkeypatch.setenv("ISLS_FF_NSEG", nseg)
     B = 4096
     cfg = P.config2(batch=B, N=100, seed=0)
     box = Box(cfg["u_lo"], cfg["u_hi"])
@@ -592,6 +595,8 @@ def test_headline_size_properties(monkeypatch):
     small = make_isls(cfg, sel)
     small.ilqr_admm(project_u=box, **kw)
     e, es = big.engine, small.engine
+    if nseg == "1":
+        assert e._outer_args.gain.lin_on == 1 and e._outer_args.ff.lin_on == 1 and es._outer_args.gain.lin_on == 1
     for name in ("xhat", "uhat", "K", "k", "zu", "lu", "cost"):
         a, b_ = getattr(e, name)[sel].cpu().numpy(), getattr(es, name).cpu().numpy()
         assert np.array_equal(a, b_), name
