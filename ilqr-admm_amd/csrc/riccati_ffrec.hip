@@ -339,14 +339,16 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec2_kernel(FfRecP<T> p)
     const T *rrec = lds + ssh * SLOT;
     // vectors: own component of c0, xhat/uhat, z, lambda (lanes without a regularised block load c0 again and drop it)
     const T *pc0 = xl ? p.c0x.at(bb, 0) + i : p.c0u.at(bb, 0) + iu;
-    const int64_t c0st = xl ? p.c0x.st : p.c0u.st;
+    // per-step strides in elements as 32-bit lane values: (N - 1) x stride < 2^31 (launch_ff_record), so a step's offset is
+    // one 32-bit multiply per pointer instead of the 64-bit product (5 instructions per load, 4 loads per step)
+    const uint32_t c0st = (uint32_t)(xl ? p.c0x.st : p.c0u.st);
     const int dd = xl ? NX : NU;
     const int64_t ovec = ((int64_t)col * p.B + bb) * N * dd + (xl ? i : iu);
     const T *phat = xl ? p.xhat : p.uhat;
     const bool hash = hasreg && phat != nullptr;
     const T *ph = hash ? phat + ovec : pc0;
     const T *pz = hasreg ? (xl ? p.zx : p.zu) + ovec : pc0, *pl = hasreg ? (xl ? p.lx : p.lu) + ovec : pc0;
-    const int64_t vst = hasreg ? dd : c0st, hst = hash ? dd : c0st;
+    const uint32_t vst = hasreg ? (uint32_t)dd : c0st, hst = hash ? (uint32_t)dd : c0st;
     const T dmask = hasreg ? T(1) : T(0), hmask = hash ? T(1) : T(0);
     // 2 * rows of the ADMM weights: the lane's own row of Qr (x-lanes) and all of Rr (every lane evaluates cu)
     T qrow[NX], rr2[NU][NU];
@@ -381,10 +383,11 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec2_kernel(FfRecP<T> p)
             if constexpr (ISLS_NT_FFREC) g.rr[j] = ld_stream(reinterpret_cast<const V2 *>(r + oR[j]));
             else g.rr[j] = *reinterpret_cast<const V2 *>(r + oR[j]);
         }
-        g.c0 = pc0[(int64_t)t * c0st];
-        g.hv = ph[(int64_t)t * hst];
-        g.zv = pz[(int64_t)t * vst];
-        g.lv = pl[(int64_t)t * vst];
+        const uint32_t tu = (uint32_t)t;
+        g.c0 = pc0[tu * c0st];
+        g.hv = ph[tu * hst];
+        g.zv = pz[tu * vst];
+        g.lv = pl[tu * vst];
     };
     const int d_dst = D_OFF + i;                               // own d component (x-lanes: d_x[i]; u-lanes: d_u[r] at D_OFF + NX + r)
     const int c_dst = xl ? DUMP_OFF : C0U_OFF + iu;            // u-lanes publish c0u_r
@@ -471,9 +474,11 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec2_kernel(FfRecP<T> p)
                 for (int c = 0; c < NU; ++c) sacc += rr2[r][c] * du[c];
                 cu[r] = c0u[r] + sacc;
             }
-            T sx = T(0);
+            T sx = T(0);                                       // without a state block qrow = 0 and the sum is +0 exactly:
+            if (hasx) {                                        // skip it (uniform)
 #pragma unroll
-            for (int j = 0; j < NX; ++j) sx += qrow[j] * dx[j];
+                for (int j = 0; j < NX; ++j) sx += qrow[j] * dx[j];
+            }
             T ci = c0_own + sx;                                // x-lanes: cx_i
 #pragma unroll
             for (int r = 0; r < NU; ++r) ci = (!xl && iu == r) ? cu[r] : ci;
@@ -663,6 +668,9 @@ int launch_ff_record(const isls_ff_args &a, hipStream_t s)
         if (!(rowc && v2_on) || segmented) return ISLS_ERR_UNSUPPORTED;
     }
     p.lin_par = (const T *)a.lin_par; p.lin_par_sb = a.lin_par_sb;
+    // the one-hand-off kernel addresses a step of c0x / c0u with a 32-bit offset
+    const int64_t c0lim = ((int64_t)1 << 31) / (a.N > 1 ? a.N - 1 : 1);
+    if (rowc && v2_on && (a.c0x.st < 0 || a.c0u.st < 0 || a.c0x.st >= c0lim || a.c0u.st >= c0lim)) return ISLS_ERR_UNSUPPORTED;
 #define LAUNCH2(NX_, NU_, MODE_)                                                                                        \
     {                                                                                                                   \
         if (segmented) launch_ffrec2<T, NX_, NU_, ISLS_FF2_SEG_DEPTH, ISLS_FF2_SEG_DEPTH, (NX_ * NX_ > 64 ? 1 : 2), MODE_>(lin, dim3(grid, p.nseg, p.ncol), s, p); /* n = 9: 256 registers spill */ \
