@@ -58,7 +58,6 @@ static int outer_iteration(const isls_outer_args &a, hipStream_t s)
     if (!a.skip_gain) {
         {
             ScopedTimer tm(tmg, 0, s);
-            static const bool fuse_ff = [] { const char *e = getenv("ISLS_GAIN_FF"); return !e || atoi(e) != 0; }();
             // The gain pass with the recursion inside holds 370-400 registers: one wavefront per SIMD.  While its wavefronts fit
             // the chip's SIMDs that costs nothing; beyond (B > 7168 at n = 6, m = 3 on 256 CUs) the surplus runs as a second round
             // and the launch doubles (123 -> 251 us from B = 4096 to 8192), where the pass without the recursion (<= 256 registers,
@@ -70,7 +69,7 @@ static int outer_iteration(const isls_outer_args &a, hipStream_t s)
             }();
             const int lanes = a.gain.n + a.gain.m;
             const int64_t waves = lanes > 0 && lanes <= kWave ? (a.gain.B + kWave / lanes - 1) / (kWave / lanes) : 0;
-            const bool fuse_now = fuse_ff && a.J > 0 && waves <= simds;
+            const bool fuse_now = a.J > 0 && waves <= simds;
             if ((rc = launch_gain<T>(a.gain, s, fuse_now ? &a.ff : nullptr, &ff_done)) != ISLS_OK) return rc;
         }
         if (ff_seg_enabled(a.ff.seg)) {                        // operators of the time-parallel feed-forward pass

@@ -275,14 +275,11 @@ int launch_columns_rollout(const isls_columns_args &a, hipStream_t s)
     p.K = (const T *)a.K; p.k = (const T *)a.k; p.zu = (const T *)a.zu; p.lu = (const T *)a.lu;
     p.dx = (T *)a.dx; p.du = (T *)a.du; p.active = a.active;
     const int pb = 4, blocks = (a.B + pb - 1) / pb;
-    static const bool rows_on = [] { const char *e = getenv("ISLS_COL_ROWS"); return !e || atoi(e) != 0; }();
 #define LAUNCH_C(NX_, NU_, C_)                                                                                         \
     {                                                                                                                  \
         if constexpr (C_ * (NX_ + NU_) <= 64) {                                                                        \
-            if (rows_on) {                                                                                             \
-                constexpr int PBR = 64 / (C_ * (NX_ + NU_));                                                           \
-                hipLaunchKernelGGL((columns_rollout_rows_kernel<T, NX_, NU_, C_>), dim3((a.B + PBR - 1) / PBR), dim3(64), 0, s, p); \
-            } else hipLaunchKernelGGL((columns_rollout_kernel<T, NX_, NU_, C_>), dim3(blocks), dim3(64), 0, s, p);     \
+            constexpr int PBR = 64 / (C_ * (NX_ + NU_));                                                               \
+            hipLaunchKernelGGL((columns_rollout_rows_kernel<T, NX_, NU_, C_>), dim3((a.B + PBR - 1) / PBR), dim3(64), 0, s, p); \
         } else hipLaunchKernelGGL((columns_rollout_kernel<T, NX_, NU_, C_>), dim3(blocks), dim3(64), 0, s, p);         \
     }
 #define CALL(NX_, NU_)                                                                                               \

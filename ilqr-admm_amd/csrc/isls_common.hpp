@@ -47,32 +47,20 @@ __device__ __forceinline__ void static_for(F &&f)
     static_for_impl<N>(static_cast<F &&>(f), std::make_integer_sequence<int, N>{});
 }
 
+// Streaming accesses (the `nt` bit of a gfx950 global load / store): data a launch touches once -- the packed records of a
+// feed-forward pass, the arrays a pass writes for a later launch -- should not push the re-used lines (the vectors a
+// recursion walks 8 bytes at a time, the gains the winner replay reads again) out of the L2.  Measured per site
+// (tools/kbench.py), they pay for the record loads of the feed-forward passes and the stores of the gain pass only.
+template <typename V>
+__device__ __forceinline__ V ld_stream(const V *p) { return __builtin_nontemporal_load(p); }
+template <typename V>
+__device__ __forceinline__ void st_stream(V *p, V v) { __builtin_nontemporal_store(v, p); }
+
 // Hand-off through LDS between the lanes of ONE wavefront (every recursive kernel here runs
 // single-wave workgroups).  DS instructions of a wave execute in issue order, so a ds_write followed by a
 // ds_read needs no s_barrier and, crucially, no `s_waitcnt vmcnt(0)`: __syncthreads() would drain the
 // global loads that are deliberately kept in flight several steps ahead.  This only pins the compiler's
 // ordering of memory operations (wavefront-scope fences and a wave barrier emit no instructions).
-// Streaming accesses (the `nt` bit of a gfx950 global load / store): data a launch touches once -- the packed records of a
-// feed-forward pass, the arrays a pass writes for a later launch -- should not push the re-used lines (the vectors a
-// recursion walks 8 bytes at a time, the gains the winner replay reads again) out of the L2.  Measured per site
-// (tools/kbench.py): the switches default to what paid.
-template <typename V>
-__device__ __forceinline__ V ld_stream(const V *p) { return __builtin_nontemporal_load(p); }
-template <typename V>
-__device__ __forceinline__ void st_stream(V *p, V v) { __builtin_nontemporal_store(v, p); }
-#ifndef ISLS_NT_FFREC
-#define ISLS_NT_FFREC 1
-#endif
-#ifndef ISLS_NT_GAIN_LD
-#define ISLS_NT_GAIN_LD 0
-#endif
-#ifndef ISLS_NT_GAIN_ST
-#define ISLS_NT_GAIN_ST 1
-#endif
-#ifndef ISLS_NT_RO_LD
-#define ISLS_NT_RO_LD 0
-#endif
-
 __device__ __forceinline__ void slot_sync()
 {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -276,16 +264,6 @@ template <typename T> int launch_reduce(int32_t B, const void *cost, const void 
 template <typename T> int launch_outer_begin(int32_t B, int32_t N, int32_t n, int32_t m, int32_t *admm_active,
                                              const int32_t *outer_active, void *lx, void *lu, void *res_prev,
                                              int32_t *iters, hipStream_t s);
-
-// Trajectories per wavefront for the slot kernels (env override for tuning experiments).
-inline int pick_tpw(int B, int max_tpw, const char *env)
-{
-    int tpw = max_tpw;       // measured on MI355X (B=4096): fuller wavefronts win, the per-step latency does not shrink with fewer slots
-    (void)B;
-    if (const char *e = getenv(env)) tpw = atoi(e);
-    if (tpw < 1) tpw = 1;
-    return tpw > max_tpw ? max_tpw : tpw;
-}
 
 inline int check_launch()
 {

@@ -25,7 +25,7 @@ struct ProjP {
 template <typename T, int D, int BLOCK>
 __global__ __launch_bounds__(BLOCK, (BLOCK <= 256 ? 2 : 1)) void project_rows_kernel(ProjP<T> p)
 {
-    __shared__ T red[2][2][16];                                // [parity][a / b][wavefront]
+    __shared__ T red[2][16];                                   // [a / b][wavefront]
     const int pb = blockIdx.x, r = threadIdx.x;
     if (p.active != nullptr && p.active[pb] == 0) return;      // uniform per workgroup
     const bool inr = r < p.R;
@@ -43,14 +43,6 @@ __global__ __launch_bounds__(BLOCK, (BLOCK <= 256 ? 2 : 1)) void project_rows_ke
         sets[s].b = p.b[s] ? p.b[s] + (int64_t)pb * p.b_sp[s] : nullptr;
         sets[s].par = p.par[s] ? p.par[s] + (int64_t)pb * p.par_sp[s] : nullptr;
     }
-#ifdef ISLS_PROJECT_SET_STAGE                                      // opt-in here: measured 7 % slower for config 4's rows (151 vs 141 us:
-                                                                   // the fp64 kernel spills more); sls_admm.hip has it on (+13-19 %)
-    __shared__ T set_lds[kMaxSets * kSetLdsWords];
-    CSetLds<T> lsets[kMaxSets];
-    stage_sets_lds<T>(sets, lsets, p.nsets, D, set_lds);
-#else
-    CSet<T> (&lsets)[kMaxSets] = sets;
-#endif
     int it = 0;
     if (p.algorithm == ISLS_PROJ_ALG_ADMM && p.nsets == 1 && sets[0].A == nullptr) {   // direct primitive
         T v[kMaxSetDim];
@@ -61,34 +53,27 @@ __global__ __launch_bounds__(BLOCK, (BLOCK <= 256 ? 2 : 1)) void project_rows_ke
         for (int j = 0; j < D; ++j) x[j] = v[j];
     } else {
         const int nw = (blockDim.x + 63) >> 6, wid = r >> 6;
-        // Workgroup-wide maxima once per inner iteration: two barriers per call (-DISLS_ONE_BARRIER: alternating buffers, one
-        // barrier, none for a single wavefront -- measured slower, see sls_admm.hip).
-        int par = 0;
+        // Workgroup-wide maxima once per inner iteration: two barriers per call (partials visible; buffer free again).  The set
+        // operands stay in global memory here: staging them in LDS as sls_admm.hip does measured 7 % slower for config 4's rows
+        // (151 vs 141 us: the fp64 kernel spills more).
         auto block_max = [&](T &a, T &b) {
             if (!row) { a = T(0); b = T(0); }
             a = wave_max(a);
             b = wave_max(b);
-#ifdef ISLS_ONE_BARRIER
-            if (nw == 1) return;
-#endif
-            if ((r & 63) == 0) { red[par][0][wid] = a; red[par][1][wid] = b; }
+            if ((r & 63) == 0) { red[0][wid] = a; red[1][wid] = b; }
             __syncthreads();
-            T ma = red[par][0][0], mb = red[par][1][0];
-            for (int w = 1; w < nw; ++w) { ma = red[par][0][w] > ma ? red[par][0][w] : ma; mb = red[par][1][w] > mb ? red[par][1][w] : mb; }
-#ifndef ISLS_ONE_BARRIER                                           // default: second barrier (see the comment at `par`)
+            T ma = red[0][0], mb = red[1][0];
+            for (int w = 1; w < nw; ++w) { ma = red[0][w] > ma ? red[0][w] : ma; mb = red[1][w] > mb ? red[1][w] : mb; }
             __syncthreads();
-#else
-            par ^= 1;
-#endif
             a = ma;
             b = mb;
         };
         if (p.algorithm == ISLS_PROJ_ALG_DYKSTRA)
-            it = dykstra_row<T, D>(x0, p.nsets, lsets, p.max_iter, p.threshold, x, block_max);
+            it = dykstra_row<T, D>(x0, p.nsets, sets, p.max_iter, p.threshold, x, block_max);
         else if (p.algorithm == ISLS_PROJ_ALG_SOC)
-            it = project_soc_row<T, D>(x0, lsets[0], p.rho, p.max_iter, p.threshold, x, block_max);
+            it = project_soc_row<T, D>(x0, sets[0], p.rho, p.max_iter, p.threshold, x, block_max);
         else
-            it = project_set_convex_row<T, D>(x0, p.nsets, lsets, p.rho, p.max_iter, p.threshold, x, block_max);
+            it = project_set_convex_row<T, D>(x0, p.nsets, sets, p.rho, p.max_iter, p.threshold, x, block_max);
     }
     if (inr) {
         T *dst = p.y_out + (int64_t)pb * p.out_sp + (int64_t)r * p.out_sr;

@@ -18,9 +18,6 @@
 // younger ones are still travelling).
 #include "isls_common.hpp"
 
-// Ablation switch (wrong results by design; tools/ab_build.sh + tools/kbench.py): -DISLS_GAIN_EXP_NOFLUSH
-// drops the stores of the record image and of K -- the "gain pass without its stores" figure.
-
 namespace isls {
 
 constexpr int kGainDepth = 2;   // steps of A,B,C in flight per lane (a step takes ~2 us, far more than an HBM round trip; deeper rings
@@ -42,7 +39,6 @@ struct GainP {
     View<T> c0x, c0u, Qr, Rr;
     const T *xhat, *uhat, *zx, *lx, *zu, *lu;
     T *kff;
-    int rev;                       // 1: the grid walks the trajectory blocks from the last to the first
     const T *lin_par;              // LIN form (isls_gain_args.lin_on): the model's parameters, batch stride lin_par_sb
     int64_t lin_par_sb;
 };
@@ -140,7 +136,7 @@ __global__ __launch_bounds__(64, ISLS_GAIN_OCC) void riccati_gain_kernel(GainP<T
     __shared__ __align__(16) T img[2 * IMG];
 
     const int lane = threadIdx.x;
-    const int bx = p.rev ? (int)gridDim.x - 1 - (int)blockIdx.x : (int)blockIdx.x;   // trajectory block of this wavefront
+    const int bx = blockIdx.x;                                 // trajectory block of this wavefront
     const bool inslot = lane / G < TPW;
     const int s = inslot ? lane / G : TPW - 1, i = inslot ? lane - (lane / G) * G : G - 1;   // surplus lanes repeat the last lane
     const int b = bx * TPW + s;
@@ -170,10 +166,7 @@ __global__ __launch_bounds__(64, ISLS_GAIN_OCC) void riccati_gain_kernel(GainP<T
     const bool has_cux = p.Cux.p != nullptr;
     // (when the slot's lanes tile an array exactly -- n = 6, m = 3: 36 = 4 x 9, 18 = 2 x 9 -- no element needs the clamp and the
     // lane's loads are ONE base plus compile-time offsets: one address register per array instead of one per load)
-#ifndef ISLS_GAIN_EXACT
-#define ISLS_GAIN_EXACT 1
-#endif
-    constexpr bool A_EXACT = ISLS_GAIN_EXACT && (NX * NX) % G == 0, B_EXACT = ISLS_GAIN_EXACT && (NX * NU) % G == 0;
+    constexpr bool A_EXACT = (NX * NX) % G == 0, B_EXACT = (NX * NU) % G == 0;
     const T *pA[JA], *pB[JB];
 #pragma unroll
     for (int j = 0; j < JA; ++j) { const int e = i + G * j; pA[j] = p.A.at(bb, 0) + (A_EXACT ? e : (e < NX * NX ? e : NX * NX - 1)); }
@@ -295,9 +288,9 @@ __global__ __launch_bounds__(64, ISLS_GAIN_OCC) void riccati_gain_kernel(GainP<T
         const int64_t oa = (int64_t)t * a_st, ob = (int64_t)t * b_st;
         if constexpr (LIN == 0) {
 #pragma unroll
-            for (int j = 0; j < JA; ++j) g.ra[j] = ISLS_NT_GAIN_LD ? ld_stream(pA[j] + oa) : pA[j][oa];
+            for (int j = 0; j < JA; ++j) g.ra[j] = pA[j][oa];
 #pragma unroll
-            for (int j = 0; j < JB; ++j) g.rb[j] = ISLS_NT_GAIN_LD ? ld_stream(pB[j] + ob) : pB[j][ob];
+            for (int j = 0; j < JB; ++j) g.rb[j] = pB[j][ob];
         }
         const T *cl = pcl + (int64_t)t * cl_st, *cr = pcr + (int64_t)t * cr_st;
 #pragma unroll
@@ -361,18 +354,13 @@ __global__ __launch_bounds__(64, ISLS_GAIN_OCC) void riccati_gain_kernel(GainP<T
         if (j < JP) {
             if constexpr (REC) {
                 V2 *dr = reinterpret_cast<V2 *>(recg + (int64_t)tq * (TPW * RSW) + fd[j < JP ? j : 0]);
-                if constexpr (ISLS_NT_GAIN_ST) st_stream(dr, fl[j < JP ? j : 0]);
-                else *dr = fl[j < JP ? j : 0];
+                st_stream(dr, fl[j < JP ? j : 0]);
             }
         } else if (j < JP + JK) {
             const int jj = j - JP < JK ? (j - JP >= 0 ? j - JP : 0) : 0;
             T *dk = p.K + kgo[jj] + (int64_t)tq * (NU * NX);
-            if constexpr (KPAIRS) {
-                if constexpr (ISLS_NT_GAIN_ST) st_stream(reinterpret_cast<V2 *>(dk), fk[jj]);
-                else *reinterpret_cast<V2 *>(dk) = fk[jj];
-            } else {
-                *dk = fk1[jj];
-            }
+            if constexpr (KPAIRS) st_stream(reinterpret_cast<V2 *>(dk), fk[jj]);
+            else *dk = fk1[jj];
         }
     };
     // the JP + JK stores take evenly spaced places among the 3 NX blocks of the step's three accumulation loops
@@ -380,7 +368,6 @@ __global__ __launch_bounds__(64, ISLS_GAIN_OCC) void riccati_gain_kernel(GainP<T
     static_assert(NSEND <= NPOS, "at most one store per block");
     auto send_at = [&](int tq, auto POS) {
         constexpr int pos = decltype(POS)::value;
-#ifndef ISLS_GAIN_EXP_NOFLUSH
         static_for<NSEND>([&](auto JJ) {
             constexpr int j = decltype(JJ)::value;
             if constexpr ((j * NPOS) / NSEND == pos) {
@@ -389,7 +376,6 @@ __global__ __launch_bounds__(64, ISLS_GAIN_OCC) void riccati_gain_kernel(GainP<T
                 __builtin_amdgcn_sched_barrier(0);
             }
         });
-#endif
     };
     auto step = [&](int t, Stage &g, int q, auto FLUSH) {
         constexpr bool flush_prev = decltype(FLUSH)::value;
@@ -568,19 +554,6 @@ __global__ __launch_bounds__(64, ISLS_GAIN_OCC) void riccati_gain_kernel(GainP<T
         }
         const int64_t o = bN + t;
         // the lane's column of [Phi | B]: x-lane i -> Phi[:, i] = A[:, i] + B K[:, i]; u-lane r -> B[:, r] (its K column is zero)
-#ifndef ISLS_GAIN_REREAD_B
-#define ISLS_GAIN_REREAD_B 0
-#endif
-        // (-DISLS_GAIN_REREAD_B=1: B_t from the slot's LDS again here instead of registers kept since (2): 402 -> 394 registers,
-        // no faster with the feed-forward pass inside (208-213 us both) and 6 us slower without (172 vs 166 us); capping the
-        // kernel at 256 registers -- -DISLS_GAIN_OCC=2 -- spills 456 B into scratch and takes 385 us: its real pressure is ~370)
-        T Bq[NX][NU];
-        if constexpr (ISLS_GAIN_REREAD_B && LIN == 0) {
-#pragma unroll
-            for (int k = 0; k < NX; ++k)
-#pragma unroll
-                for (int r = 0; r < NU; ++r) Bq[k][r] = ABs[k * W + NX + r];
-        }
         T phc[NX];
         static_for<NX>([&](auto KK) {
             constexpr int k = decltype(KK)::value;
@@ -589,7 +562,7 @@ __global__ __launch_bounds__(64, ISLS_GAIN_OCC) void riccati_gain_kernel(GainP<T
                 ph += (k < NU ? l_b0 : l_b1) * Kc[k % NU];        // row k of B has one entry
             } else {
 #pragma unroll
-                for (int r = 0; r < NU; ++r) ph += (ISLS_GAIN_REREAD_B ? Bq[k][r] : Fr[k][NX + r]) * Kc[r];
+                for (int r = 0; r < NU; ++r) ph += Fr[k][NX + r] * Kc[r];
             }
             phc[k] = ph;
             if constexpr (flush_prev) send_at(t + 1, std::integral_constant<int, 2 * NX + k>{});
@@ -703,10 +676,6 @@ __global__ __launch_bounds__(64, ISLS_GAIN_OCC) void riccati_gain_kernel(GainP<T
                 for (int r = 0; r < NU; ++r) sacc += Kc[r] * Quu[r][c];
                 Wr[c] = sacc;
             }
-#ifndef ISLS_GAIN_JOSEPH2
-#define ISLS_GAIN_JOSEPH2 1
-#endif
-#if ISLS_GAIN_JOSEPH2
             // the same four terms with (K'Quu) K and Qux'K under one sum: ((K'Quu)_i. + Qux_.i) . K_.j + K_.i . Qux_.j -- the first
             // bracket is the residual of Quu K = -Qux, so the value keeps the form's insensitivity to the rounding of K (two
             // multiply-adds per (r, j) instead of three)
@@ -723,21 +692,6 @@ __global__ __launch_bounds__(64, ISLS_GAIN_OCC) void riccati_gain_kernel(GainP<T
                 }
                 rec[vdst + j] = (M[j] + t3) + t12;
             }
-#else
-#pragma unroll
-            for (int j = 0; j < NX; ++j) {
-                T t1 = T(0), t2 = T(0), t3 = T(0);
-#pragma unroll
-                for (int r = 0; r < NU; ++r) {
-                    const T kj = Kr[r][j];
-                    t1 += Wr[r] * kj;                          // (K'Quu) K
-                    t2 += rhs[r] * kj;                         // Qux' K
-                    t3 += Kc[r] * Qxr[r][j];                   // K' Qux
-                }
-                const T vn = (MODE == ISLS_SOLVE_CHOL) ? ((M[j] + t1) + t2) + t3 : ((M[j] + t2) + t3) + t1;
-                rec[vdst + j] = vn;
-            }
-#endif
         }
     };
 
@@ -760,12 +714,10 @@ __global__ __launch_bounds__(64, ISLS_GAIN_OCC) void riccati_gain_kernel(GainP<T
         step(tb, ring[RD - 1], 1, std::true_type{});
         tlast = tb;
     }
-#ifndef ISLS_GAIN_EXP_NOFLUSH
     if (tlast >= 0) {                                          // the last step's image
 #pragma unroll
         for (int j = 0; j < JP + JK; ++j) send(tlast, j);
     }
-#endif
     if (valid && i == 0 && !pd_ok && p.status) atomicOr(&p.status[b], ISLS_ST_NOT_PD);
 }
 
@@ -789,10 +741,8 @@ int launch_gain(const isls_gain_args &a, hipStream_t s, const isls_ff_args *ff, 
     p.K = (T *)a.K; p.Quu = (T *)a.Quu; p.fac = (T *)a.fac; p.Qux = (T *)a.Qux; p.rec = (T *)a.rec;
     p.status = a.status; p.active = a.active;
     p.xhat = p.uhat = p.zx = p.lx = p.zu = p.lu = nullptr; p.kff = nullptr;
-    static const int rev_mode = [] { const char *e = getenv("ISLS_GAIN_REV"); return e ? atoi(e) : 0; }();   // EXPERIMENT
-    p.rev = rev_mode ? 1 : 0;
     // model-structured form (isls_gain_args.lin_on): on the record forms the drivers use; the caller switches it off by not
-    // giving the hint (isls.Engine: use_model_structure / ISLS_FF_LEAN=0, for the gain pass and its readers together)
+    // giving the hint (isls.Engine.use_model_structure, for the gain pass and its readers together)
     if (ff && ff->rec == a.rec && a.rec && (ff->lin_on != 0) != (a.lin_on != 0)) return ISLS_ERR_ARG;   // one layout for writer and reader
     // lin_on also selects the LEAN record layout, which the feed-forward passes of the same hint read: no silent fall-back
     bool lin_di = false, lean_arm = false, lean_car = false;

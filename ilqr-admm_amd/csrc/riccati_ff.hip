@@ -342,7 +342,7 @@ int launch_ff(const isls_ff_args &a, hipStream_t s)
     const bool rowc = (!a.Qr.p || a.Qr.st == 0) && (!a.Rr.p || a.Rr.st == 0);
 #define CALL(NX_, NU_)                                                                                 \
     {                                                                                                  \
-        p.tpw = pick_tpw(a.B, kWave / (NX_ + NU_), "ISLS_FF_TPW");                                     \
+        p.tpw = kWave / (NX_ + NU_);            /* fuller wavefronts win (B = 4096) */                 \
         const int grid = (a.B + p.tpw - 1) / p.tpw;                                                    \
         if (segmented && rowc)                                                                         \
             hipLaunchKernelGGL((riccati_ff_kernel<T, NX_, NU_, kFfSegDepth, kFfSegOcc, kFfSegGroup, true>), dim3(grid, p.nseg), dim3(64), 0, s, p); \

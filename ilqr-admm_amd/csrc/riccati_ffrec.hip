@@ -40,7 +40,6 @@ struct FfRecP {
     const T *rec;                  // [ceil(B/TPW)][N][TPW][RW]: the records of a wavefront's trajectories are contiguous per step
     T *k;
     const int32_t *active;
-    int rev;                       // 1: the grid walks the trajectory blocks from the last to the first (see launch_ff_record)
     const T *Qr_term;              // nullable: weight block of the terminal step (isls_ff_args.Qr_term), batch stride Qr.sb
     int ncol;                      // feedback columns in one launch (blockIdx.z): zx, lx, zu, lu, k, vseg hold ncol blocks, c0 acts on column 0
     // model-structured form (isls_ff_args.lin_on): only [K | fac] of a record is read; A'v and B'v come from the model
@@ -48,9 +47,10 @@ struct FfRecP {
     int64_t lin_par_sb;
 };
 
+// First form of the pass: Qr / Rr rows that vary with the time step (time-invariant ones take riccati_ffrec2_kernel below).
 // FG: ring entries are refilled in groups of FG consecutive steps -- one burst of FG records (FG x 648 B at n=6, m=3) per
 // trajectory instead of FG separate requests (larger DRAM bursts; same idea as kFfGroup in riccati_ff.hip)
-template <typename T, int NX, int NU, int D, int OCC, int FG, bool ROWC>
+template <typename T, int NX, int NU, int D, int OCC, int FG>
 __global__ __launch_bounds__(64, OCC) void riccati_ffrec_kernel(FfRecP<T> p)
 {
     constexpr int G = NX + NU, W = NX + NU, MAXTPW = kWave / G;
@@ -106,7 +106,7 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec_kernel(FfRecP<T> p)
 
     struct Stage {
         V2 rr[JR];
-        T c0, hv, zv, lv, rrow[ROWC ? 1 : NX];
+        T c0, hv, zv, lv, rrow[NX];
     };
     auto fetch_vec = [&](int t, Stage &g) {
         g.c0 = pc0[(int64_t)t * c0st];
@@ -115,26 +115,19 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec_kernel(FfRecP<T> p)
             g.zv = pz[e];
             g.lv = pl[e];
             g.hv = ph ? ph[e] : T(0);
-            if constexpr (!ROWC) {
-                const T *q = prow + (int64_t)t * rowst;
+            const T *q = prow + (int64_t)t * rowst;
 #pragma unroll
-                for (int j = 0; j < NX; ++j) g.rrow[j] = q[j < lim ? j : lim - 1];
-            }
+            for (int j = 0; j < NX; ++j) g.rrow[j] = q[j < lim ? j : lim - 1];
         } else {
             g.hv = g.zv = g.lv = T(0);
-            if constexpr (!ROWC) {
 #pragma unroll
-                for (int j = 0; j < NX; ++j) g.rrow[j] = T(0);
-            }
+            for (int j = 0; j < NX; ++j) g.rrow[j] = T(0);
         }
     };
     auto fetch = [&](int t, Stage &g) {
         const T *r = bR + (int64_t)t * BW;
 #pragma unroll
-        for (int j = 0; j < JR; ++j) {
-            if constexpr (ISLS_NT_FFREC) g.rr[j] = ld_stream(reinterpret_cast<const V2 *>(r + oR[j]));
-            else g.rr[j] = *reinterpret_cast<const V2 *>(r + oR[j]);
-        }
+        for (int j = 0; j < JR; ++j) g.rr[j] = ld_stream(reinterpret_cast<const V2 *>(r + oR[j]));
         fetch_vec(t, g);
     };
     // cx_i / cu_i = c0 + 2 * (row of Qr/Rr) . d       (isls/sls.py:132-137; O2 of SURVEY 8c)
@@ -148,9 +141,6 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec_kernel(FfRecP<T> p)
         }
         return hasreg ? c0v + T(2) * sacc : c0v;
     };
-    T rowc[NX];
-#pragma unroll
-    for (int j = 0; j < NX; ++j) rowc[j] = (ROWC && hasreg) ? prow[j < lim ? j : lim - 1] : T(0);
 
     // ---- terminal step: v = cx[N-1], k[N-1] = 0 (last segment); the others start from v_in = 0 ----------------------
     T vcur;
@@ -159,10 +149,7 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec_kernel(FfRecP<T> p)
         fetch_vec(N - 1, term);
         rec[D_OFF + i] = hasreg ? term.hv - (term.zv - term.lv) : T(0);
         slot_sync();
-        T rowt[NX];
-#pragma unroll
-        for (int j = 0; j < NX; ++j) rowt[j] = ROWC ? rowc[j] : term.rrow[ROWC ? 0 : j];
-        const T cterm = reg_grad(term.c0, rowt);
+        const T cterm = reg_grad(term.c0, term.rrow);
         vcur = last ? cterm : T(0);
         rec[xl ? V_OFF + i : DUMP_OFF] = vcur;
         if (valid && !xl && last) p.k[((int64_t)b * N + N - 1) * NU + iu] = T(0);
@@ -191,7 +178,7 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec_kernel(FfRecP<T> p)
             const T c0_now = g.c0;
             T row_now[NX];
 #pragma unroll
-            for (int j = 0; j < NX; ++j) row_now[j] = ROWC ? rowc[j] : g.rrow[ROWC ? 0 : j];
+            for (int j = 0; j < NX; ++j) row_now[j] = g.rrow[j];
             slot_sync();
             if constexpr (FG == 1) {
                 fetch(t - D > t_lo ? t - D : t_lo, g);             // refill (clamped, unconditional)
@@ -261,7 +248,8 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec_kernel(FfRecP<T> p)
 //   * every memory instruction is unconditional (lanes without a regularised block load c0 again, surplus lanes repeat the
 //     last lane, slots without a trajectory shadow the first valid one, every lane of a slot stores an entry of k_t), so
 //     the compiler's vmcnt bookkeeping stays exact and D steps of records really are in flight.
-// The sums of the dense form (LIN = 0) are those of riccati_ffrec_kernel in the same order: its results are bit-identical to it.
+// The sums of the dense form (LIN = 0) are those of riccati_ffrec_kernel in the same order: on time-invariant weights its
+// results are bit-identical to what that kernel computes.
 // LIN (isls_ff_args.lin_on): 0 = the whole record, Phi'v from its [Phi | B] block.  Otherwise A and B are the linearisation of a
 // built-in model whose structure the pass knows, the records are the LEAN ones the gain pass wrote under the same hint
 // ([K | fac | model words] at stride rec_lean_stride: 28 instead of 82 words per step at n = 6, m = 3; 42 instead of 150 at
@@ -299,7 +287,7 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec2_kernel(FfRecP<T> p)
     typedef T V2 __attribute__((ext_vector_type(2)));
 
     const int lane = threadIdx.x;
-    const int bx = p.rev ? (int)gridDim.x - 1 - (int)blockIdx.x : (int)blockIdx.x;   // trajectory block of this wavefront
+    const int bx = blockIdx.x;                                 // trajectory block of this wavefront
     const bool inslot = lane / G < TPW;
     const int s = inslot ? lane / G : TPW - 1, i = inslot ? lane - (lane / G) * G : G - 1;   // surplus lanes repeat the last lane
     const int b = bx * TPW + s;
@@ -379,10 +367,8 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec2_kernel(FfRecP<T> p)
         const int t = __builtin_amdgcn_readfirstlane(tq);
         const T *r = bR + (int64_t)t * BW;
 #pragma unroll
-        for (int j = 0; j < JR; ++j) {                          // the records stream through once per pass: 78 -> 71 us with `nt`
-            if constexpr (ISLS_NT_FFREC) g.rr[j] = ld_stream(reinterpret_cast<const V2 *>(r + oR[j]));
-            else g.rr[j] = *reinterpret_cast<const V2 *>(r + oR[j]);
-        }
+        for (int j = 0; j < JR; ++j)                            // the records stream through once per pass: 78 -> 71 us with `nt`
+            g.rr[j] = ld_stream(reinterpret_cast<const V2 *>(r + oR[j]));
         const uint32_t tu = (uint32_t)t;
         g.c0 = pc0[tu * c0st];
         g.hv = ph[tu * hst];
@@ -591,12 +577,6 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec2_kernel(FfRecP<T> p)
     if (seg > 0 && valid && xl) p.vseg[(((int64_t)col * p.B + b) * p.nseg + seg) * NX + i] = vcur;   // v0 at the segment start
 }
 
-static bool v2_on_()
-{
-    static const bool on = [] { const char *e = getenv("ISLS_FF_V2"); return !e || atoi(e) != 0; }();
-    return on;
-}
-
 #ifndef ISLS_FF2_LEAN_DEPTH
 #define ISLS_FF2_LEAN_DEPTH 3      // ring depth of the model-structured form (a third of the record words per entry)
 #endif
@@ -640,24 +620,19 @@ int launch_ff_record(const isls_ff_args &a, hipStream_t s)
     p.seg_len = segmented ? a.seg.seg_len : (a.N > 1 ? a.N - 1 : 1);
     p.vseg = segmented ? (T *)a.seg.v : nullptr;
     const bool rowc = (!a.Qr.p || a.Qr.st == 0) && (!a.Rr.p || a.Rr.st == 0);
-    // EXPERIMENT (ISLS_FF_REV = 1: every pass walks the blocks backwards; 2: consecutive passes alternate)
     p.Qr_term = (const T *)a.Qr_term;
-    if (p.Qr_term && !(rowc && v2_on_() && a.Qr.p)) return ISLS_ERR_UNSUPPORTED;
+    if (p.Qr_term && !(rowc && a.Qr.p)) return ISLS_ERR_UNSUPPORTED;
     p.ncol = a._pad > 1 ? a._pad : 1;
-    if (p.ncol > 1 && !(rowc && v2_on_())) return ISLS_ERR_UNSUPPORTED;   // columns ride on the one-hand-off kernel only
-    static const int rev_mode = [] { const char *e = getenv("ISLS_FF_REV"); return e ? atoi(e) : 0; }();
-    static int rev_count = 0;
-    p.rev = rev_mode == 1 ? 1 : (rev_mode == 2 ? (rev_count++ & 1) : 0);
+    if (p.ncol > 1 && !rowc) return ISLS_ERR_UNSUPPORTED;   // columns ride on the one-hand-off kernel only
 #ifndef ISLS_FF2_SEQ_DEPTH
 #define ISLS_FF2_SEQ_DEPTH 3
 #endif
 #ifndef ISLS_FF2_SEG_DEPTH
 #define ISLS_FF2_SEG_DEPTH 2
 #endif
-    const bool v2_on = v2_on_();
     // model-structured form (isls_ff_args.lin_on): the records are the LEAN ones the gain pass wrote under the same hint, which
-    // only the one-hand-off kernel reads -- time-varying weights, the time-parallel form (its operators come from the dense
-    // records) or ISLS_FF_V2 = 0 are ISLS_ERR_UNSUPPORTED, not a fall-back
+    // only the one-hand-off kernel reads -- time-varying weights or the time-parallel form (its operators come from the dense
+    // records) are ISLS_ERR_UNSUPPORTED, not a fall-back
     int lin = LIN_NONE;
     if (a.lin_on) {
         if (a.lin_model == ISLS_MODEL_DI) { if (a.n != 2 * a.m) return ISLS_ERR_ARG; lin = LIN_DI; }
@@ -665,12 +640,12 @@ int launch_ff_record(const isls_ff_args &a, hipStream_t s)
         else if (a.lin_model == ISLS_MODEL_CAR) { if (a.n != 4 || a.m != 2) return ISLS_ERR_ARG; lin = LIN_CAR; }
         else return ISLS_ERR_UNSUPPORTED;
         if (!a.lin_par) return ISLS_ERR_ARG;
-        if (!(rowc && v2_on) || segmented) return ISLS_ERR_UNSUPPORTED;
+        if (!rowc || segmented) return ISLS_ERR_UNSUPPORTED;
     }
     p.lin_par = (const T *)a.lin_par; p.lin_par_sb = a.lin_par_sb;
     // the one-hand-off kernel addresses a step of c0x / c0u with a 32-bit offset
     const int64_t c0lim = ((int64_t)1 << 31) / (a.N > 1 ? a.N - 1 : 1);
-    if (rowc && v2_on && (a.c0x.st < 0 || a.c0u.st < 0 || a.c0x.st >= c0lim || a.c0u.st >= c0lim)) return ISLS_ERR_UNSUPPORTED;
+    if (rowc && (a.c0x.st < 0 || a.c0u.st < 0 || a.c0x.st >= c0lim || a.c0u.st >= c0lim)) return ISLS_ERR_UNSUPPORTED;
 #define LAUNCH2(NX_, NU_, MODE_)                                                                                        \
     {                                                                                                                   \
         if (segmented) launch_ffrec2<T, NX_, NU_, ISLS_FF2_SEG_DEPTH, ISLS_FF2_SEG_DEPTH, (NX_ * NX_ > 64 ? 1 : 2), MODE_>(lin, dim3(grid, p.nseg, p.ncol), s, p); /* n = 9: 256 registers spill */ \
@@ -680,17 +655,13 @@ int launch_ff_record(const isls_ff_args &a, hipStream_t s)
     {                                                                                                                   \
         p.tpw = kWave / (NX_ + NU_);            /* the record layout is blocked by the gain pass's slots per wavefront */ \
         const int grid = (a.B + p.tpw - 1) / p.tpw;                                                                     \
-        if (rowc && v2_on) {                                                                                            \
+        if (rowc) {                                                                                                     \
             if (a.solve_mode == ISLS_SOLVE_CHOL) LAUNCH2(NX_, NU_, ISLS_SOLVE_CHOL)                                     \
             else LAUNCH2(NX_, NU_, ISLS_SOLVE_INV)                                                                      \
-        } else if (segmented && rowc)                                                                                   \
-            hipLaunchKernelGGL((riccati_ffrec_kernel<T, NX_, NU_, ISLS_FFREC_SEG_DEPTH, ISLS_FFREC_SEG_OCC, ISLS_FFREC_GROUP, true>), dim3(grid, p.nseg), dim3(64), 0, s, p);  \
-        else if (segmented)                                                                                             \
-            hipLaunchKernelGGL((riccati_ffrec_kernel<T, NX_, NU_, ISLS_FFREC_SEG_DEPTH, ISLS_FFREC_SEG_OCC, ISLS_FFREC_GROUP, false>), dim3(grid, p.nseg), dim3(64), 0, s, p); \
-        else if (rowc)                                                                                                  \
-            hipLaunchKernelGGL((riccati_ffrec_kernel<T, NX_, NU_, ISLS_FFREC_DEPTH, 1, ISLS_FFREC_GROUP, true>), dim3(grid), dim3(64), 0, s, p);   \
+        } else if (segmented)                                                                                           \
+            hipLaunchKernelGGL((riccati_ffrec_kernel<T, NX_, NU_, ISLS_FFREC_SEG_DEPTH, ISLS_FFREC_SEG_OCC, ISLS_FFREC_GROUP>), dim3(grid, p.nseg), dim3(64), 0, s, p); \
         else                                                                                                            \
-            hipLaunchKernelGGL((riccati_ffrec_kernel<T, NX_, NU_, ISLS_FFREC_DEPTH, 1, ISLS_FFREC_GROUP, false>), dim3(grid), dim3(64), 0, s, p);  \
+            hipLaunchKernelGGL((riccati_ffrec_kernel<T, NX_, NU_, ISLS_FFREC_DEPTH, 1, ISLS_FFREC_GROUP>), dim3(grid), dim3(64), 0, s, p);  \
     }
     ISLS_DISPATCH_DIMS(a.n, a.m, CALL)
 #undef CALL

@@ -27,11 +27,8 @@
 //             re-run steps [sg S, (sg+1) S) of candidate `ind` from its checkpoint, fetching K_t, k_t, xhat_t, uhat_t again.
 //             Either way the trajectory is collected in LDS (x over the dead records and checkpoints), leaves in one coalesced
 //             sweep, and the element-wise ADMM update of the outer driver rides on it.
+// -DISLS_DIAG prints cycle stamps of the phases.
 #pragma once
-// Ablation switches (wrong results by design; tools/ab_build.sh + tools/kbench.py): -DISLS_RO_EXP_NOREPLAY
-// (no winner replay), _NOREFILL (replay without its operand refills), _NOXCHG (no exchange of the control rows), _NOSTAGE
-// (no stage writes), _HALFLDS (the search reads every second operand pair from the LDS: 78.6 -> 72.3 us, i.e. the search is not
-// bound by the LDS pipeline); -DISLS_DIAG prints cycle stamps of the phases.
 
 #include <type_traits>
 
@@ -184,13 +181,6 @@ struct Model<T, 4, 2, ISLS_MODEL_TASSA> {      // Tassa car-parking [x, y, theta
 #ifndef ISLS_RO_SW
 #define ISLS_RO_SW 16
 #endif
-#ifndef ISLS_RO_HOIST_WR
-#define ISLS_RO_HOIST_WR 0
-#endif
-// EXPERIMENT (off): the augmented-Lagrangian operands of the u block read with the step's first batch of LDS reads instead of
-// behind `if (has_wr)` -- one exposed LDS round trip per step less, 12 registers more: the two-wavefront form of n = 6, m = 3
-// reaches 256 registers and spills 64 B, line search 70.2 -> 72.2 us, outer iteration +15-20 us (tools/kbench.py, same box)
-constexpr bool kHoistWr = ISLS_RO_HOIST_WR != 0;
 constexpr int kRolloutDepth = 2;   // steps of record words in flight per lane (D = 2..5 ran within 3 %: issue bound; 2 is leanest)
 constexpr int kMaxSeg = 16;        // winner replay: at most this many segments
 
@@ -243,25 +233,11 @@ struct alignas(sizeof(T)) RoVec {
     T v[W];
 };
 
-// one staging load of the search (W adjacent words); ISLS_NT_RO_LD: as a streaming access
+// one staging load of the search (W adjacent words)
 template <typename T, int W>
 __device__ __forceinline__ RoVec<T, W> ro_load(const char *ptr)
 {
-    if constexpr (ISLS_NT_RO_LD) {
-        RoVec<T, W> r;
-        if constexpr (W == 2) {
-            typedef T V2 __attribute__((ext_vector_type(2)));
-            typedef V2 V2u __attribute__((aligned(sizeof(T))));
-            const V2 v = ld_stream(reinterpret_cast<const V2u *>(ptr));
-            r.v[0] = v.x;
-            r.v[1] = v.y;
-        } else {
-            r.v[0] = ld_stream(reinterpret_cast<const T *>(ptr));
-        }
-        return r;
-    } else {
-        return *reinterpret_cast<const RoVec<T, W> *>(ptr);
-    }
+    return *reinterpret_cast<const RoVec<T, W> *>(ptr);
 }
 
 // CNT words of a record group (CNT even with pair loads: groups are padded) read back as aligned pairs: one ds_read_b128
@@ -274,11 +250,7 @@ __device__ __forceinline__ void ro_read(const T *src, T (&out)[CNT])
         static_assert(CNT % 2 == 0, "padded group");
 #pragma unroll
         for (int i = 0; i < CNT / 2; ++i) {
-#ifdef ISLS_RO_EXP_HALFLDS
-            const V2 v = *reinterpret_cast<const V2 *>(src + 2 * (i & ~1));   // ablation: every second pair read (wrong results)
-#else
             const V2 v = *reinterpret_cast<const V2 *>(src + 2 * i);
-#endif
             out[2 * i] = v.x;
             out[2 * i + 1] = v.y;
         }
@@ -402,9 +374,7 @@ __device__ __forceinline__ void ro_replay(const Model<T, NX, NU, MODEL> &model, 
                 const int i = i0 + d, t = t0 + i;
                 const bool in = wl && i < S && t < t1;
                 const WOp o = ring[d];
-#ifndef ISLS_RO_EXP_NOREFILL
                 ro_wfetch<T, NX, NU, RPL>(ring[d], wK, wk, wxh, wuh, i + WD, last);
-#endif
                 T uown[RPL], u[NU];
 #pragma unroll
                 for (int r = 0; r < RPL; ++r) {
@@ -413,11 +383,7 @@ __device__ __forceinline__ void ro_replay(const Model<T, NX, NU, MODEL> &model, 
                     for (int j = 0; j < NX; ++j) acc += fma(-xhm, o.xh[j], xw[j]) * o.K[r * NX + j];   // x - xhat, one rounding
                     uown[r] = fma(uhm, o.uh[r], acc + alpha_w * o.k[r]);                                // ... + uhat
                 }
-#ifdef ISLS_RO_EXP_NOXCHG
-                if constexpr (false) {
-#else
                 if constexpr (RL > 1) {                        // the segment's lanes swap their rows of u
-#endif
 #pragma unroll
                     for (int r = 0; r < RPL; ++r) ubw[r * ubs] = uown[r];
                     slot_sync();
@@ -428,11 +394,7 @@ __device__ __forceinline__ void ro_replay(const Model<T, NX, NU, MODEL> &model, 
 #pragma unroll
                     for (int r = 0; r < NU; ++r) u[r] = uown[r < RPL ? r : 0];
                 }
-#ifdef ISLS_RO_EXP_NOSTAGE
-                if constexpr (false) {
-#else
                 if constexpr (STAGE) {
-#endif
                     const bool own = in && c < nl;
                     const bool xown = own && (RL == 1 || r0 == 0);     // the first lane of a segment stores x_t, every lane its rows of u_t
                     T *sx = stage + (xown ? t * NX : sdump), *su = stage + (own ? uoff + t * NU + r0 : sdump);
@@ -682,17 +644,12 @@ __global__ __launch_bounds__(64, OCC) void rollout_kernel(RoP<T> p)
         }                                                                                                                   \
         /* u = (x - xhat) K' + alpha k + uhat            (isls.py:328-329) */                                               \
         T u[NU];                                                                                                            \
-        T rru_h[LY::even(NU)], rwr_h[LY::even(NU)];           /* kHoistWr: the AL operands of the u block ride in the first batch */ \
         {                                                                                                                   \
             T rK[LY::even(NU * NX)], rxh[LY::even(NX)], rk[LY::even(NU)], ruh[LY::even(NU)];                                \
             ro_read<W>(rec + O_K, rK);                                                                                      \
             ro_read<W>(rec + O_XH, rxh);                                                                                    \
             ro_read<W>(rec + O_KK, rk);                                                                                     \
             ro_read<W>(rec + O_UH, ruh);                                                                                    \
-            if constexpr (kHoistWr) {                                                                                       \
-                ro_read<W>(rec + O_RU, rru_h);                                                                              \
-                ro_read<W>(rec + O_WR, rwr_h);                                                                              \
-            }                                                                                                               \
             _Pragma("unroll") for (int r = 0; r < NU; ++r) {                                                                \
                 T acc = T(0);                                                                                               \
                 _Pragma("unroll") for (int j = 0; j < NX; ++j) acc += (x[j] - rxh[j]) * rK[r * NX + j];                     \
@@ -743,13 +700,11 @@ __global__ __launch_bounds__(64, OCC) void rollout_kernel(RoP<T> p)
         }                                                                                                                   \
         if (has_wr) {                                                                                                       \
             T rru[LY::even(NU)], rwr[LY::even(NU)];                                                                         \
-            if constexpr (!kHoistWr) {                                                                                      \
-                ro_read<W>(rec + O_RU, rru);                                                                                \
-                ro_read<W>(rec + O_WR, rwr);                                                                                \
-            }                                                                                                               \
+            ro_read<W>(rec + O_RU, rru);                                                                                    \
+            ro_read<W>(rec + O_WR, rwr);                                                                                    \
             _Pragma("unroll") for (int r = 0; r < NU; ++r) {                                                                \
-                const T df = u[r] - (kHoistWr ? rru_h[r] : rru[r]);                                                         \
-                ag1 += (df * df) * (kHoistWr ? rwr_h[r] : rwr[r]);                                                          \
+                const T df = u[r] - rru[r];                                                                                 \
+                ag1 += (df * df) * rwr[r];                                                                                  \
             }                                                                                                               \
         }                                                                                                                   \
         if (TAILF) {                                          /* dead (padding) steps leave the sums alone */               \
@@ -835,16 +790,11 @@ __global__ __launch_bounds__(64, OCC) void rollout_kernel(RoP<T> p)
     // the last segment compute on clamped operands and write the dump word), so the loads of the next iterations stay in
     // flight behind the current one.  x_t, u_t go to the stage in LDS (or straight to HBM when the stage does not fit the slot;
     // a trajectory that hit its prediction gets the same values again).
-#ifdef ISLS_RO_EXP_ALLMISS
-    const bool any_miss = true;                                // A/B build: the winner is always replayed
-#else
     const bool any_miss = !stage_on || __ballot(valid && ind != pred) != 0ull;   // uniform
-#endif
     // x_t is needed now unless the fused ADMM update only sweeps u and further ADMM iterations follow (then only a trajectory
     // that stops in this update is written out: decided behind the sweep)
     const bool x_early = !p.fa_on || p.fa_last || p.fa_zx != nullptr;   // uniform
     bool x_ready = true;
-#ifndef ISLS_RO_EXP_NOREPLAY
     if (any_miss) {
         const T alpha_w = absolute ? T(1) : p.alphas[ind];
         const T *pxh = has_xh ? p.xhat : nullptr, *puh = has_uh ? p.uhat : nullptr;
@@ -865,7 +815,6 @@ __global__ __launch_bounds__(64, OCC) void rollout_kernel(RoP<T> p)
     } else {
         x_ready = false;
     }
-#endif
 #ifdef ISLS_DIAG
     const unsigned long long twloop_ = __builtin_readcyclecounter();
 #endif

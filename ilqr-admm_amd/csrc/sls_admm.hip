@@ -30,7 +30,7 @@ __global__ __launch_bounds__(BLOCK, (BLOCK <= 256 ? (sizeof(T) == 4 ? (D >= 3 ? 
 {
     extern __shared__ __align__(16) unsigned char sls_smem[];
     T *rhs = reinterpret_cast<T *>(sls_smem);                  // [R][D]
-    __shared__ T red[2][2][16];                                // [parity][a / b][wavefront]
+    __shared__ T red[2][16];                                   // [a / b][wavefront]
     const int pb = blockIdx.x, r = threadIdx.x, R = p.R;
     const bool row = r < R;
     const int rr_i = row ? r : 0;
@@ -44,35 +44,21 @@ __global__ __launch_bounds__(BLOCK, (BLOCK <= 256 ? (sizeof(T) == 4 ? (D >= 3 ? 
         sets[s].b = p.b[s] ? p.b[s] + (int64_t)pb * p.b_sp[s] : nullptr;
         sets[s].par = p.par[s] ? p.par[s] + (int64_t)pb * p.par_sp[s] : nullptr;
     }
-#ifndef ISLS_NO_SET_STAGE                                          // set operands in LDS behind typed pointers (stage_sets_lds)
-    __shared__ T set_lds[kMaxSets * kSetLdsWords];
+    __shared__ T set_lds[kMaxSets * kSetLdsWords];            // set operands in LDS behind typed pointers (stage_sets_lds)
     CSetLds<T> lsets[kMaxSets];
     stage_sets_lds<T>(sets, lsets, p.nsets, D, set_lds);
-#else
-    CSet<T> (&lsets)[kMaxSets] = sets;
-#endif
     // workgroup-wide max (project_set_convex: once per inner iteration) and sum (residual norms); idle threads contribute
-    // zeros.  Two barriers per call (partials visible; buffer free again).  -DISLS_ONE_BARRIER builds the form with alternating
-    // buffers (one barrier per call, none for a one-wavefront problem): measured SLOWER on MI355X (config 5, B = 8192: DI-1D
-    // fp32 7505 vs 7794 it/s, DI-3D 3162 vs 3391; isls_admm's row projection 156 vs 150 us) -- the second barrier keeps the
-    // wavefronts of a workgroup in step through the set projections, whose loads then hit the same lines together.
-    int par = 0;
+    // zeros.  Two barriers per call (partials visible; buffer free again): the second barrier keeps the wavefronts of a workgroup
+    // in step through the set projections, whose loads then hit the same lines together (one barrier measured slower).
     auto block_max = [&](T &a, T &b) {
         if (!row) { a = T(0); b = T(0); }
         a = wave_max(a);
         b = wave_max(b);
-#ifdef ISLS_ONE_BARRIER
-        if (nw == 1) return;
-#endif
-        if ((r & 63) == 0) { red[par][0][wid] = a; red[par][1][wid] = b; }
+        if ((r & 63) == 0) { red[0][wid] = a; red[1][wid] = b; }
         __syncthreads();
-        T ma = red[par][0][0], mb = red[par][1][0];
-        for (int w = 1; w < nw; ++w) { ma = red[par][0][w] > ma ? red[par][0][w] : ma; mb = red[par][1][w] > mb ? red[par][1][w] : mb; }
-#ifndef ISLS_ONE_BARRIER
+        T ma = red[0][0], mb = red[1][0];
+        for (int w = 1; w < nw; ++w) { ma = red[0][w] > ma ? red[0][w] : ma; mb = red[1][w] > mb ? red[1][w] : mb; }
         __syncthreads();
-#else
-        par ^= 1;
-#endif
         a = ma;
         b = mb;
     };
@@ -80,18 +66,11 @@ __global__ __launch_bounds__(BLOCK, (BLOCK <= 256 ? (sizeof(T) == 4 ? (D >= 3 ? 
         if (!row) { a = T(0); b = T(0); }
         a = wave_sum(a);
         b = wave_sum(b);
-#ifdef ISLS_ONE_BARRIER
-        if (nw == 1) return;
-#endif
-        if ((r & 63) == 0) { red[par][0][wid] = a; red[par][1][wid] = b; }
+        if ((r & 63) == 0) { red[0][wid] = a; red[1][wid] = b; }
         __syncthreads();
         T sa = T(0), sb = T(0);
-        for (int w = 0; w < nw; ++w) { sa += red[par][0][w]; sb += red[par][1][w]; }
-#ifndef ISLS_ONE_BARRIER
+        for (int w = 0; w < nw; ++w) { sa += red[0][w]; sb += red[1][w]; }
         __syncthreads();
-#else
-        par ^= 1;
-#endif
         a = sa;
         b = sb;
     };

@@ -65,6 +65,7 @@ class _Timed:
 
 class Engine:
     profile_events = None
+    use_model_structure = True     # False: the passes keep the dense forms for every model (bench.py's general layout)
 
     def __init__(self, batch, N, x_dim, u_dim, dtype=torch.float64, device="cuda"):
         if not torch.cuda.is_available():
@@ -203,8 +204,8 @@ class Engine:
         # final end-effector position) reaches the record feed-forward passes as one block plus the terminal block
         # (isls_ff_args.Qr_term): they then run the one-hand-off kernel instead of loading a weight row per step
         self.Qr_ff, self.Qr_term = None, None
-        if (self.Qr is not None and self.Qr.ndim == 3 and self.Qr.shape[0] == N and N > 2 and bool((self.Qr[:-1] == self.Qr[:1]).all())
-                and os.environ.get("ISLS_FF_QR_TERM", "1") != "0"):
+        if (self.Qr is not None and self.Qr.ndim == 3 and self.Qr.shape[0] == N and N > 2
+                and bool((self.Qr[:-1] == self.Qr[:1]).all())):
             self.Qr_ff, self.Qr_term = self.Qr[:1].contiguous(), self.Qr[-1].contiguous()
         self.Rr = weights(rho_u, m) if has_u else None
         if has_x and self.Qr is None:
@@ -292,37 +293,31 @@ class Engine:
             capi.Kernels._set_lin(a, lin, self.B, self.dtype)
         return lin
 
-    def _structure_expected(self):
-        """Will the passes of this engine get the model hint, as far as can be told before A, B are linearised: a model whose
-        structure the passes know, no A, B handed in by a caller, the forms not switched off, time-invariant weights."""
-        if not self.fast_dims or not getattr(self, "use_model_structure", True) or getattr(self, "_ab_caller", False):
-            return False
-        if os.environ.get("ISLS_FF_LEAN", "1") == "0" or os.environ.get("ISLS_FF_V2", "1") == "0" or os.environ.get("ISLS_FF_RECORD", "1") == "0":
+    def _structure_applies(self):
+        """What every model-structured pass needs of the engine: the row-per-lane kernels for these dimensions, the forms not
+        switched off (use_model_structure), a model whose structure the passes know, and ADMM weights that are the same at
+        every step (Qr: or all but the last, which the passes take as the terminal block Qr_term)."""
+        if not self.fast_dims or not self.use_model_structure:
             return False
         if self.model not in (capi.MODEL_DI, capi.MODEL_ARM3R, capi.MODEL_CAR):
             return False
         inv = lambda W: W is None or W.ndim < 3 or W.shape[-3] == 1       # noqa: E731
-        Qr_ok = inv(self.Qr) or getattr(self, "Qr_term", None) is not None
-        return inv(self.Rr) and Qr_ok
+        return inv(self.Rr) and (inv(self.Qr) or getattr(self, "Qr_term", None) is not None)
+
+    def _structure_expected(self):
+        """Will the passes of this engine get the model hint, as far as can be told before A, B are linearised: the structured
+        forms apply and no A, B were handed in by a caller."""
+        return self._structure_applies() and not getattr(self, "_ab_caller", False)
 
     def ff_lin(self, rec, seg=None):
         """(model id, parameters) for isls_gain_args.lin_on / isls_ff_args.lin_on, or None.  The hint makes the gain pass write
         the LEAN records and the feed-forward passes read them, so it is given only when every pass on these records can take
-        the structured form: the packed records are in use, A and Bm are what isls_linearize wrote into the buffers the engine
-        holds now for the model set now, the model is one whose structure the passes know, the ADMM weights are the same at
-        every step (a terminal block apart), and the passes run sequentially (`seg`: the time-parallel form builds its
-        operators from the dense records).  ISLS_FF_LEAN=0 / use_model_structure = False switch the forms off."""
-        if rec is None or seg is not None or not self.fast_dims or not getattr(self, "use_model_structure", True):
-            return None
-        if os.environ.get("ISLS_FF_LEAN", "1") == "0" or os.environ.get("ISLS_FF_V2", "1") == "0":
-            return None
-        if self.model not in (capi.MODEL_DI, capi.MODEL_ARM3R, capi.MODEL_CAR) or self.model_par is None:
+        the structured form: the structured forms apply (_structure_applies), the packed records are in use, A and Bm are what
+        isls_linearize wrote into the buffers the engine holds now for the model set now, and the passes run sequentially
+        (`seg`: the time-parallel form builds its operators from the dense records)."""
+        if rec is None or seg is not None or not self._structure_applies() or self.model_par is None:
             return None
         if getattr(self, "_ab_made", None) != (self.model, self.A.data_ptr(), self.Bm.data_ptr()):
-            return None
-        inv = lambda W: W is None or W.ndim < 3 or W.shape[-3] == 1       # noqa: E731
-        Qr_ff, _ = self._ff_weights(rec)
-        if not (inv(self.Rr) and inv(Qr_ff)):
             return None
         return (self.model, self.model_par)
 
@@ -362,9 +357,9 @@ class Engine:
 
     def ff_record(self):
         """Packed step records [A + B K | B | K | fac] the gain pass writes for the feed-forward passes (isls_gain_args.rec /
-        isls_ff_args.rec), or None when switched off (ISLS_FF_RECORD=0).  Only the drivers that run the gain pass
+        isls_ff_args.rec), or None for the generic kernels, which have none.  Only the drivers that run the gain pass
         themselves right before the feed-forward passes use it: the records are stale once K / fac are replaced."""
-        if os.environ.get("ISLS_FF_RECORD", "1") == "0" or not self.fast_dims:
+        if not self.fast_dims:
             return None
         if getattr(self, "_ffrec", None) is None:
             self._ffrec = torch.zeros(capi.ff_record_elems(self.B, self.N, self.n, self.m), dtype=self.dtype, device=self.device)
@@ -399,7 +394,7 @@ class Engine:
     def _ff_weights(self, rec):
         """(Qr, Qr_term) operands of a feed-forward pass: the terminal-block form on the packed records when it applies"""
         rr_inv = self.Rr is None or self.Rr.ndim < 3 or self.Rr.shape[-3] == 1
-        if rec is not None and getattr(self, "Qr_term", None) is not None and rr_inv and os.environ.get("ISLS_FF_V2", "1") != "0":
+        if rec is not None and getattr(self, "Qr_term", None) is not None and rr_inv:
             return self.Qr_ff, self.Qr_term
         return self.Qr, None
 
@@ -481,7 +476,7 @@ class Engine:
                            u_sets=self.u_sets, u_col0=self.u_col0, u_work=self.u_work)
         self._outer_args = capi.OuterArgs(gain=gain, ff=ff, ro=ro, admm=admm, J=int(J), skip_gain=0, begin_done=int(bool(begin_done)))
         self._outer_rec, self._outer_seg = rec, seg
-        self._outer_lin_state = (getattr(self, "_ab_made", None), getattr(self, "use_model_structure", True))
+        self._outer_lin_state = (getattr(self, "_ab_made", None), self.use_model_structure)
         self._advance_args = None
         self._outer_args.log = capi._ptr(log)
         self._outer_args.outer_active = capi._ptr(self.outer_active)
@@ -492,7 +487,7 @@ class Engine:
         """gain -> J x [ff -> rollout/line-search -> ADMM update] on the current stream (no host sync)."""
         fn = getattr(library(), f"isls_ilqr_admm_outer_{self.sfx}")
         fn.restype = ctypes.c_int
-        state = (getattr(self, "_ab_made", None), getattr(self, "use_model_structure", True))
+        state = (getattr(self, "_ab_made", None), self.use_model_structure)
         if state != getattr(self, "_outer_lin_state", ()):     # A, Bm changed hands since the block was marshalled / last run
             self._apply_ff_lin((self._outer_args.gain, self._outer_args.ff), self._outer_rec, self._outer_seg)
             self._outer_lin_state = state
@@ -526,7 +521,7 @@ class Engine:
         trajectories still iterating.  Pair it with build_outer(..., begin_done=True).  `linearize=False` leaves A, B alone (a
         shared LTI pair).  The cost Hessians must be the batch-shared tables (written once by expand())."""
         K = capi.Kernels
-        if linearize and getattr(self, "use_model_structure", True) and self._ab_is_static():
+        if linearize and self.use_model_structure and self._ab_is_static():
             linearize = False                                  # the model's one linearisation is in place: nothing to rewrite
         key = (float(tol_cost), float(tol_osc), bool(linearize))
         if getattr(self, "_advance_args", None) is None or self._advance_args[0] != key:

@@ -104,8 +104,7 @@ class ColumnSolver:
         one-hand-off kernel's condition); ISLS_ADMM_FF_COLUMNS=0 keeps one launch per column."""
         e = self.e
         inv = lambda W: W is None or W.ndim < 3 or W.shape[-3] == 1                      # noqa: E731
-        return (self.rec is not None and inv(e.Qr) and inv(e.Rr) and os.environ.get("ISLS_ADMM_FF_COLUMNS", "1") != "0"
-                and os.environ.get("ISLS_FF_V2", "1") != "0")
+        return self.rec is not None and inv(e.Qr) and inv(e.Rr) and os.environ.get("ISLS_ADMM_FF_COLUMNS", "1") != "0"
 
     def x_step(self):
         """[d_x, phi_x], [d_u, phi_u] for the targets z - lmb: C feed-forward passes, then the column rollout.  A weight that
