@@ -204,6 +204,15 @@ ISLS_API int isls_dense_closed_loop_f32(const isls_dense_loop_args *a, void *str
 {
     return a ? launch_dense_closed_loop<float>(*a, (hipStream_t)stream) : ISLS_ERR_ARG;
 }
+ISLS_API int isls_sls_controller_f64(const isls_sls_controller_args *a, void *stream)
+{
+    return a ? launch_sls_controller<double>(*a, (hipStream_t)stream) : ISLS_ERR_ARG;
+}
+ISLS_API int isls_sls_controller_f32(const isls_sls_controller_args *a, void *stream)
+{
+    return a ? launch_sls_controller<float>(*a, (hipStream_t)stream) : ISLS_ERR_ARG;
+}
+ISLS_API int64_t isls_sls_controller_work_elems(int32_t B, int32_t N, int32_t n) { return sls_controller_work_elems(B, N, n); }
 ISLS_API int isls_columns_rollout_f64(const isls_columns_args *a, void *stream)
 {
     return a ? launch_columns_rollout<double>(*a, (hipStream_t)stream) : ISLS_ERR_ARG;

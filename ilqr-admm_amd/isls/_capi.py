@@ -25,6 +25,7 @@ MODEL_LTI, MODEL_ARM3R, MODEL_CAR, MODEL_DI, MODEL_TASSA = 0, 1, 2, 3, 4
 COST_VIA, COST_PHUBER = 0, 1
 RO_NAN_TO_1E5, RO_ACCEPT_TEST, RO_ABSOLUTE = 1, 2, 4
 PROJ_NONE, PROJ_BOX, PROJ_SETS = 0, 1, 2
+CTL_NOT_CAUSAL = 1
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.path.join(os.path.dirname(_HERE), "csrc", "libisls_hip.so")
@@ -158,6 +159,12 @@ class DenseLoopArgs(C.Structure):
                 ("x0", C.c_void_p), ("x_log", C.c_void_p), ("u_log", C.c_void_p)]
 
 
+class SlsControllerArgs(C.Structure):
+    _fields_ = [("B", C.c_int32), ("N", C.c_int32), ("n", C.c_int32), ("m", C.c_int32), ("A", View), ("Bm", View),
+                ("PHI_U", C.c_void_p), ("du", C.c_void_p), ("K", C.c_void_p), ("k", C.c_void_p), ("flags", C.c_void_p),
+                ("work", C.c_void_p)]
+
+
 class ColumnsAdmmArgs(C.Structure):
     _fields_ = [("B", C.c_int32), ("N", C.c_int32), ("n", C.c_int32), ("m", C.c_int32), ("C", C.c_int32), ("phase", C.c_int32),
                 ("relax", C.c_double), ("tol_abs", C.c_double), ("tol_rel", C.c_double),
@@ -187,9 +194,9 @@ class AdvanceArgs(C.Structure):
 
 # names every build of the library must export (checked by tests/test_capi_symbols.py)
 EXPORTED = [f"isls_{k}_{s}" for s in ("f64", "f32") for k in
-            ("riccati_gain", "riccati_ff", "riccati_gain_ff", "riccati_ff_prepare", "rollout_ls", "admm_update", "project_rows", "sls_admm", "sls_closed_loop", "columns_rollout", "columns_admm", "dense_closed_loop", "expand_quadratic", "linearize",
+            ("riccati_gain", "riccati_ff", "riccati_gain_ff", "riccati_ff_prepare", "rollout_ls", "admm_update", "project_rows", "sls_admm", "sls_closed_loop", "columns_rollout", "columns_admm", "dense_closed_loop", "sls_controller", "expand_quadratic", "linearize",
              "accept_step", "reduce_convergence", "reduce_convergence_table", "ilqr_admm_outer", "outer_advance", "columns_iteration")] + \
-           ["isls_ff_segments", "isls_ff_record_elems", "isls_version", "isls_dims_supported", "isls_dims_generic", "isls_error_string", "isls_timing_create",
+           ["isls_ff_segments", "isls_ff_record_elems", "isls_sls_controller_work_elems", "isls_version", "isls_dims_supported", "isls_dims_generic", "isls_error_string", "isls_timing_create",
             "isls_timing_destroy", "isls_timing_reset", "isls_timing_pause", "isls_timing_read_ms"]
 
 
@@ -297,6 +304,11 @@ def ff_record_elems(B, N, n, m):
     tpw = 64 // (n + m)
     model_words = 6 if (n, m) in ((9, 3), (4, 2)) else 0       # rec_model_words (csrc/isls_common.hpp): the arm's A[6:8, 0:3] / the car's six entries behind fac
     return -(-B // tpw) * tpw * N * ((n * n + 2 * n * m + m * m + model_words + 1) & ~1)   # record stride padded to an even word count
+
+
+def sls_controller_work_elems(B, N, n):
+    """isls_sls_controller_work_elems: the N(N-1)/2 blocks of Phi_x below its diagonal and xd [N, n], per problem."""
+    return B * (N * (N - 1) // 2 * n * n + N * n)
 
 
 def _record(rec, B, N, n, m):
@@ -639,6 +651,26 @@ class Kernels:
         a.xhat, a.uhat = _ptr(_dense(xhat, (N, n), "xhat")), _ptr(_dense(uhat, (N, m), "uhat"))
         a.x0, a.x_log, a.u_log = _ptr(_dense(x0, (M, n), "x0")), _ptr(x_log), _ptr(_dense(u_log, (M, N, m), "u_log"))
         return self._call("dense_closed_loop", _sfx(x_log), a, stream)
+
+    def sls_controller(self, A, Bm, PHI_U, du, K, k, flags, work, stream=None):
+        """isls_sls_controller: PHI_U / K [B, N m, N n], du / k [B, N m], flags int32 [B], A / Bm broadcastable views
+        [.,.,n,n] / [.,.,n,m], work >= sls_controller_work_elems(B, N, n) contiguous elements of the same dtype."""
+        B, R, Cn = PHI_U.shape
+        n = Bm.shape[-2]
+        m = Bm.shape[-1]
+        N = R // m
+        if R != N * m or Cn != N * n:
+            raise ValueError(f"PHI_U: shape {tuple(PHI_U.shape)} is not [B, N m, N n] for n={n}, m={m}")
+        a = SlsControllerArgs(B=B, N=N, n=n, m=m)
+        a.A, a.Bm = make_view(A, B, N, (n, n), "A"), make_view(Bm, B, N, (n, m), "B")
+        a.PHI_U, a.du = _ptr(_dense(PHI_U, (B, R, Cn), "PHI_U")), _ptr(_dense(du, (B, R), "du"))
+        a.K, a.k = _ptr(_dense(K, (B, R, Cn), "K")), _ptr(_dense(k, (B, R), "k"))
+        a.flags = _ptr(_dense(flags, (B,), "flags"))
+        size = work.numel() if _is_torch(work) else work.size
+        if size < sls_controller_work_elems(B, N, n) or not (work.is_contiguous() if _is_torch(work) else work.flags["C_CONTIGUOUS"]):
+            raise ValueError(f"work: needs a contiguous buffer of {sls_controller_work_elems(B, N, n)} elements")
+        a.work = _ptr(work)
+        return self._call("sls_controller", _sfx(PHI_U), a, stream)
 
     def columns_rollout(self, *args, stream=None, **kw):
         return self._call("columns_rollout", _sfx(args[6]), self.columns_args(*args, **kw), stream)

@@ -17,6 +17,13 @@ import torch
 from . import _capi as capi
 
 
+def as_numpy(x):
+    """float64 numpy copy of an array or a tensor (device tensors included)."""
+    if isinstance(x, torch.Tensor):
+        return x.detach().cpu().numpy().astype(np.float64)
+    return np.asarray(x, dtype=np.float64)
+
+
 def via_point_cost(sls, x, u, b):
     """SLSBase.compute_cost for the candidates of trajectory b: x [L,N,n], u [L,N,m] -> [L] (no 1/2)."""
     zs = sls.zs if sls.zs.ndim == 2 else sls.zs[b]

@@ -478,18 +478,28 @@ class iSLS(Base):
     isls_admm = _isls_admm                                      # isls/isls.py:503-712, DP form (robust.py)
 
     def controller(self, PHI_U, du):
-        """K = Phi_u Phi_x^-1, k = (I - K Su) du with the transfer matrices of the last linearisation (notebook-era
-        `iSLS.controller`, isls/sls.py:235-242 on `Base.AB`'s Sw / Su): dense host set-up per problem, as in the reference.
-        PHI_U [N m, N n] and du [N m] (leading batch axis when batched)."""
+        """K = Phi_u Phi_x^-1, k = (I - K Su) du with the dynamics of the last linearisation, engine.A / engine.Bm (notebook-era
+        `iSLS.controller`, isls/sls.py:235-242 on `Base.AB`'s Sw / Su): all problems in one device synthesis
+        (isls_sls_controller: block recursions through A_t, B_t instead of the dense transfer matrices and inverse), in fp64
+        whatever the solver's dtype.  PHI_U [N m, N n] and du [N m] (problem 0's dynamics) or with a leading batch axis, numpy
+        or torch tensors on the engine's device; numpy in gives numpy out, torch in gives device tensors.  Problems whose PHI_U
+        is not causal (flagged in self.controller_flags) take the dense host route, sls_dense.controller."""
         from . import sls_dense as dense
-        A, Bm = self.engine.A.cpu().numpy().astype(np.float64), self.engine.Bm.cpu().numpy().astype(np.float64)
-        PHI_U, du = np.asarray(PHI_U, dtype=np.float64), np.asarray(du, dtype=np.float64)
-        if self.batch == 1 and PHI_U.ndim == 2:
-            PHI_U, du = PHI_U[None], du[None]
-        Ks, ks = zip(*(dense.controller(*dense.transfer_matrices_ltv(np.broadcast_to(A[b], (self.N,) + A.shape[-2:]),
-                                                                   np.broadcast_to(Bm[b], (self.N,) + Bm.shape[-2:])), PHI_U[b], du[b])
-                       for b in range(self.batch)))
-        return (Ks[0], ks[0]) if self.batch == 1 else (np.stack(Ks), np.stack(ks))
+        from .sls_controller import synthesize
+        e = self.engine
+        A, Bm = e.A.to(torch.float64), e.Bm.to(torch.float64)    # [B or 1, N or 1, n, n], [B or 1, N or 1, n, m]
+        if (PHI_U.ndim if isinstance(PHI_U, torch.Tensor) else np.ndim(PHI_U)) == 2:
+            A, Bm = A[:1], Bm[:1]
+
+        def dense_one(b, P_, d_):
+            Ab, Bb = A[min(b, A.shape[0] - 1)].cpu().numpy(), Bm[min(b, Bm.shape[0] - 1)].cpu().numpy()
+            Sw, Su = dense.transfer_matrices_ltv(np.broadcast_to(Ab, (self.N,) + Ab.shape[-2:]),
+                                                 np.broadcast_to(Bb, (self.N,) + Bb.shape[-2:]))
+            return dense.controller(Sw, Su, P_, d_)
+        K, k, self.controller_flags = synthesize(e, A, Bm, PHI_U, du, dense_one)
+        if self.batch == 1 and K.ndim == 3:                     # one problem: unbatched results, as the host route returned them
+            K, k = K[0], k[0]
+        return K, k
 
     def get_trajectory_sls(self, x0, K, k, noise_scale=0, problem=0):
         """Monte-Carlo closed loop of the dense controller about the nominal of problem `problem` through the forward model
@@ -498,7 +508,7 @@ class iSLS(Base):
         if noise_scale or self._host_model:
             # process noise comes from numpy's global generator, one draw per step in the reference's order: host loop
             # through the (numpy-callable) forward model, isls/isls_base.py:28-42
-            K, k = np.asarray(K, dtype=np.float64), np.asarray(k, dtype=np.float64)
+            K, k = hostpath.as_numpy(K), hostpath.as_numpy(k)
             xn, un = e.xhat[problem].cpu().numpy().astype(np.float64), e.uhat[problem].cpu().numpy().astype(np.float64)
             n, m = self.x_dim, self.u_dim
 
@@ -515,7 +525,7 @@ class iSLS(Base):
         par = e.model_par if e.model_par.ndim == 1 else e.model_par[problem].contiguous()
         x_log = torch.zeros(M, self.N, self.x_dim, dtype=e.dtype, device=e.device)
         u_log = torch.zeros(M, self.N, self.u_dim, dtype=e.dtype, device=e.device)
-        e.kern.dense_closed_loop(e.model, par, dev(np.asarray(K)), dev(np.asarray(k)), dev(x0), x_log, u_log,
+        e.kern.dense_closed_loop(e.model, par, e._t(K), e._t(k), dev(x0), x_log, u_log,
                                  xhat=e.xhat[problem].contiguous(), uhat=e.uhat[problem].contiguous(),
                                  stream=torch.cuda.current_stream().cuda_stream)
         x, u = x_log.cpu().numpy().astype(np.float64), u_log.cpu().numpy().astype(np.float64)

@@ -16,7 +16,8 @@ Config 5 of BASELINE.json (system level synthesis with chance constraints on the
     ADMM_SLS                        the ADMM loop itself runs on the device for all problems of the batch in one launch
                                     (isls_sls_admm: x-step, project_set_convex over the rows, residuals, stop rules)
                                                                                             (isls/sls.py:319-454)
-    controller / get_trajectory_sls K = Phi_u Phi_x^-1 (host set-up) and the closed-loop Monte-Carlo rollout (device)
+    controller / get_trajectory_sls K = Phi_u Phi_x^-1 for the whole batch (device, isls_sls_controller) and the
+                                    closed-loop Monte-Carlo rollout (device)
                                                                                             (isls/sls.py:235-242, sls_base.py:91-105)
 
 solve_batch / ADMM_LQT_Batch return the batch form's results through the same Riccati kernels; replanning and the
@@ -146,7 +147,7 @@ class SLS(Base):
             # process noise comes from numpy's global generator, one draw per step in the reference's order
             # (isls/sls_base.py:76-89): a host loop, so that a seeded run reproduces the reference's trajectories
             from . import hostpath
-            K, k = np.asarray(K, dtype=np.float64), np.asarray(k, dtype=np.float64)
+            K, k = hostpath.as_numpy(K), hostpath.as_numpy(k)
             A, Bm = np.asarray(self.A, dtype=np.float64), np.asarray(self.B, dtype=np.float64)
             return hostpath.noisy_closed_loop(lambda x, u: x @ A.T + u @ Bm.T, x0, self.N, self.u_dim,
                                               lambda i, x_log: x_log[:, i] @ K[i].T + k[i], noise_scale)
@@ -319,13 +320,18 @@ class SLS(Base):
         return PHI_U, du
 
     def controller(self, PHI_U, du):
-        """K = Phi_u Phi_x^-1, k = (I - K Su) du (isls/sls.py:235-242); PHI_U / du may carry a leading batch axis."""
-        Sw, Su = self._transfer()
-        PHI_U, du = np.asarray(PHI_U, dtype=np.float64), np.asarray(du, dtype=np.float64)
-        if PHI_U.ndim == 3:
-            Ks, ks = zip(*(dense.controller(Sw, Su, P_, d_) for P_, d_ in zip(PHI_U, du)))
-            return np.stack(Ks), np.stack(ks)
-        return dense.controller(Sw, Su, PHI_U, du)
+        """K = Phi_u Phi_x^-1, k = (I - K Su) du (isls/sls.py:235-242) for PHI_U [N m, N n] / [B, N m, N n] and du [N m] /
+        [B, N m], numpy or torch tensors on the engine's device: all problems in one device synthesis (isls_sls_controller,
+        block recursions instead of the dense transfer matrices and inverse), in fp64 whatever the solver's dtype.  Numpy in
+        gives numpy out, torch in gives device tensors (they go straight into get_trajectory_sls).  Problems whose PHI_U is
+        not causal (flagged in self.controller_flags) take the dense host route, sls_dense.controller."""
+        assert self.A is not None, "Set the linear dynamics model by self.AB = [A,B] before calling this method."
+        from .sls_controller import synthesize
+        e = self.engine
+        A = torch.as_tensor(self.A, device=e.device).reshape(1, 1, self.x_dim, self.x_dim)
+        Bm = torch.as_tensor(self.B, device=e.device).reshape(1, 1, self.x_dim, self.u_dim)
+        K, k, self.controller_flags = synthesize(e, A, Bm, PHI_U, du, lambda b, P_, d_: dense.controller(*self._transfer(), P_, d_))
+        return K, k
 
     def ADMM_SLS(self, project_x=False, project_u=False, max_iter=5000, rho_x=0., rho_u=0., alpha=1., tol=1e-3,
                  verbose=False, log=False, rel_tol=1e-2):
@@ -404,7 +410,7 @@ class SLS(Base):
         dev = lambda a: e._t(np.ascontiguousarray(a))                                         # noqa: E731
         x_log = torch.zeros(M, N, n, dtype=e.dtype, device=e.device)
         u_log = torch.zeros(M, N, m, dtype=e.dtype, device=e.device)
-        e.kern.sls_closed_loop(dev(self.A), dev(self.B), dev(np.asarray(K)), dev(np.asarray(k)), dev(x0), x_log, u_log,
+        e.kern.sls_closed_loop(dev(self.A), dev(self.B), e._t(K), e._t(k), dev(x0), x_log, u_log,
                                stream=torch.cuda.current_stream().cuda_stream)
         return x_log.cpu().numpy().astype(np.float64), u_log.cpu().numpy().astype(np.float64)
 

@@ -427,6 +427,37 @@ int isls_sls_closed_loop_f32(int32_t M, int32_t N, int32_t n, int32_t m, const v
                              const void *k, const void *x0, void *x_log, void *u_log, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * SLS controller of a batch of problems: K = PHI_U Phi_x^-1, k = (I - K Su) du with Phi_x = Sw + Su PHI_U
+ * (replaces SLS.controller, isls/sls.py:235-242), without the dense Sw, Su or an inverse.  For a causal (block lower
+ * triangular) PHI_U, Phi_x is unit block lower triangular and
+ *   X_s[s] = I , X_s[l+1] = A_l X_s[l] + B_l PHI_U[l, s]             (block column s of Phi_x, l = s .. N-2)
+ *   K[t, s] = PHI_U[t, s] - sum_{l = s+1..t} K[t, l] X_s[l]           (s = t .. 0),   K[t, s] = 0 for s > t
+ *   xd_0 = 0 , xd_{t+1} = A_t xd_t + B_t du_t ,  k_t = du_t - sum_{l <= t} K[t, l] xd_l
+ * with the A_l, B_l of sls_dense.transfer_matrices_ltv (A_0 .. A_{N-2} are read).  Sums run in the order written, in the
+ * entry point's precision.  A PHI_U with a non-zero entry above the block diagonal gets ISLS_CTL_NOT_CAUSAL in flags[b]; its
+ * K, k are then NOT the controller (the caller takes the dense route for it).  1 <= n <= 16, 1 <= m <= 8, any N >= 1.
+ * ------------------------------------------------------------------------------------------- */
+#define ISLS_CTL_NOT_CAUSAL 1
+
+typedef struct isls_sls_controller_args {
+    int32_t B, N, n, m;
+    isls_view A, Bm;        /* [.,.,n,n], [.,.,n,m]: a shared LTI pair (sb = st = 0) or a linearisation per problem            */
+    const void *PHI_U;      /* [B, N m, N n] dense                                                                            */
+    const void *du;         /* [B, N m]                                                                                       */
+    void *K;                /* [B, N m, N n] out: every entry written, exact zeros above the block diagonal                   */
+    void *k;                /* [B, N m] out                                                                                   */
+    int32_t *flags;         /* [B] out: ISLS_CTL_NOT_CAUSAL or 0                                                              */
+    void *work;             /* caller-owned scratch of isls_sls_controller_work_elems(B, N, n) elements (the blocks of Phi_x
+                             * below its diagonal and xd); its size grows as B N^2 n^2 / 2, so large batches are cut into chunks */
+} isls_sls_controller_args;
+
+/* elements of the scratch buffer of isls_sls_controller_* (0 for invalid dimensions) */
+int64_t isls_sls_controller_work_elems(int32_t B, int32_t N, int32_t n);
+
+int isls_sls_controller_f64(const isls_sls_controller_args *a, void *stream);
+int isls_sls_controller_f32(const isls_sls_controller_args *a, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Feedback columns of iSLS.isls_admm (isls/isls.py:503-712) in DP form.
  * The reference solves, per outer iteration, the dense normal equations
  *   [d_u, phi_u] = (Su'Q Su + R + Su'Qr Su + Rr)^-1 (r_side + Su'Qr x_reg + Rr u_reg)      (isls.py:571,580-588)
