@@ -11,7 +11,6 @@ contiguous stream (A: N*n*n, K: N*m*n, x: N*n ... elements) that a wavefront slo
 (Riccati) or forwards (rollout) with one-step-ahead prefetch; shared tables (LTI A/B, via-point Q, box
 bounds, rho weights) are passed with zero batch/time strides and stay cache-resident.
 """
-import ctypes
 import os
 
 import numpy as np
@@ -39,6 +38,11 @@ def library():
 
 ALPHAS = 10.0 ** np.linspace(0.0, -5.0, 50)            # line-search grid, isls/isls_base.py:10-11
 
+# who wrote the A, Bm an engine holds (Engine._ab_src, None if nobody it knows of): isls_linearize for the model set now
+# (STATIC: a state-independent model's, written once for every trajectory) or a caller (AB setter, get_AB, a shared LTI pair).
+# The passes may take the model's structure (isls_gain_args.lin_on / isls_ff_args.lin_on) for the model's own linearisation only
+LINEARIZED, STATIC, CALLER = "linearized", "static", "caller"
+
 
 def _stream_ptr():
     return torch.cuda.current_stream().cuda_stream
@@ -49,14 +53,14 @@ class _Timed:
         self.eng, self.name = eng, name
 
     def __enter__(self):
-        ev = getattr(self.eng, "profile_events", None)
+        ev = self.eng.profile_events
         if ev is not None:
             self.a, self.b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             self.a.record()
         return self
 
     def __exit__(self, *exc):
-        ev = getattr(self.eng, "profile_events", None)
+        ev = self.eng.profile_events
         if ev is not None:
             self.b.record()
             ev.setdefault(self.name, []).append((self.a, self.b))
@@ -86,10 +90,12 @@ class Engine:
         zi = lambda *s: torch.zeros(*s, dtype=torch.int32, device=self.device)   # noqa: E731
         # nominal trajectory and its cost
         self.xhat, self.uhat, self.cost = z(B, N, n), z(B, N, m), z(B)
-        # linearisation and cost expansion
-        self.A, self.Bm = z(B, N, n, n), z(B, N, n, m)
+        # linearisation (the A, Bm properties and who wrote them) and cost expansion
+        self._A, self._Bm, self._ab_src = z(B, N, n, n), z(B, N, n, m), None
         self.Cxx, self.Cuu, self.c0x, self.c0u = z(B, N, n, n), z(B, N, m, m), z(B, N, n), z(B, N, m)
         self.Cux = None
+        self._Cxx_sh = self._Cuu_sh = self._c0_sh = None     # batch-shared Hessian tables (hessians()), made on first use ...
+        self._hess_dirty = True                              # ... and written by the next expand()
         # Riccati factors and gains
         self.K, self.Quu, self.fac, self.Qux, self.k = z(B, N, m, n), z(B, N, m, m), z(B, N, m, m), z(B, N, m, n), z(B, N, m)
         # x-step result (line-search winner)
@@ -111,13 +117,17 @@ class Engine:
         self.u_std = 0.0
         self.cost_model, self.cost_par = capi.COST_VIA, None
         self.allow_shared_hessian = True                      # front ends that write Cxx / Cuu themselves switch it off
-        self.Qr = self.Rr = self.wq = self.wr = None
+        self.Qr = self.Rr = self.wq = self.wr = self.Qr_ff = self.Qr_term = None      # ADMM weights: set_weights()
+        self._w_invariant, self._w_terminal = True, False
         self.x_lo = self.x_hi = self.u_lo = self.u_hi = None
         self.x_sets = self.u_sets = self.x_work = self.u_work = None
         self.x_col0 = self.u_col0 = 0
         self.relax = 1.0
         self.solve_mode = capi.SOLVE_CHOL
-        self._outer_args = None
+        # buffers made on first use, and the argument blocks cached over the engine's buffers
+        self._ffrec = self._seg_bufs = self._advance_args = None
+        self._rec_lean = False                               # the last gain pass wrote self._ffrec in the lean layout
+        self._outer_args = self._outer_rec = self._outer_seg = self._outer_lin_state = self._outer_log = None
 
     # ---- optional per-kernel-family event timing (bench.py) -------------------------------------------------
     def timed(self, name):
@@ -130,6 +140,36 @@ class Engine:
         torch.cuda.synchronize()
         return {k: (sum(a.elapsed_time(b) for a, b in v), len(v)) for k, v in (self.profile_events or {}).items()}
 
+    # ---- A, Bm and who wrote them ----------------------------------------------------------------------------
+    @property
+    def A(self):
+        return self._A
+
+    @A.setter
+    def A(self, t):
+        self._A = t
+        self._ab_stale()
+
+    @property
+    def Bm(self):
+        return self._Bm
+
+    @Bm.setter
+    def Bm(self, t):
+        self._Bm = t
+        self._ab_stale()
+
+    def _ab_stale(self):
+        """A, Bm are no linearisation of the model any more (new buffers, a new model; a caller's stay a caller's)"""
+        self._ab_src = CALLER if self._ab_src == CALLER else None
+        self._outer_args = self._advance_args = None
+
+    def ab_from_caller(self):
+        """A, Bm were written by somebody else (AB setter, get_AB callback): the dense records are the only valid form.  Only
+        an assignment of A / Bm is seen by the engine: after a write INTO the buffers (`eng.A.copy_(...)`) call this.  A cached
+        isls_outer_args block keeps its pointers; run_outer() rewrites its hint fields."""
+        self._ab_src = CALLER
+
     # ---- problem setup ---------------------------------------------------------------------------------
     def _t(self, x):
         if not isinstance(x, torch.Tensor):
@@ -141,8 +181,7 @@ class Engine:
     def set_model(self, model_id, par):
         """Built-in forward model (ISLS_MODEL_*); par is [P] (shared) or [B,P] (per trajectory)."""
         self.model, self.model_par = int(model_id), self._t(par)
-        self._outer_args = None
-        self._ab_made = self._ab_static = None                 # A, Bm no longer belong to the model in use
+        self._ab_stale()
 
     def set_quadratic_cost(self, zs, Qs, seq, u_std):
         """Via-point quadratic cost (Base.set_quadratic_cost, isls/base.py:81-89); zs [nvia,n] or [B,nvia,n]."""
@@ -177,6 +216,25 @@ class Engine:
         self.outer_active.fill_(1)
         self.status.zero_()
 
+    def set_weights(self, Qr, Rr):
+        """ADMM weights Qr [n,n] / [1|N,n,n] / [B,N,n,n], Rr likewise (or None) and what the passes take from them: the line
+        search's AL weights wq, wr, the terminal-block form (Qr_ff, Qr_term) and whether they are the same at every step."""
+        self.Qr, self.Rr = Qr, Rr
+        # (dx*dx)@Qr precedence (isls/isls.py:473,476): the AL weights are the row sums
+        self.wq = None if Qr is None else Qr.sum(-1).contiguous()
+        self.wr = None if Rr is None else Rr.sum(-1).contiguous()
+        # a state weight that is the same at every step but the LAST (a terminal constraint: the arm notebook's bound on the
+        # final end-effector position) reaches the record feed-forward passes as one block plus the terminal block
+        # (isls_ff_args.Qr_term): they then run the one-hand-off kernel instead of loading a weight row per step
+        self.Qr_ff = self.Qr_term = None
+        if Qr is not None and Qr.ndim == 3 and Qr.shape[0] == self.N and self.N > 2 and bool((Qr[:-1] == Qr[:1]).all()):
+            self.Qr_ff, self.Qr_term = Qr[:1].contiguous(), Qr[-1].contiguous()
+        q_fixed, r_fixed = (W is None or W.ndim < 3 or W.shape[-3] == 1 for W in (Qr, Rr))   # the same at every step
+        self._w_invariant = q_fixed and r_fixed                     # as they are (the column passes hand them over so)
+        self._w_terminal = self.Qr_term is not None and r_fixed     # in the terminal-block form
+        self._outer_args = None
+        self._hess_dirty = True
+
     def set_admm(self, rho_x=None, rho_u=None, x_box=None, u_box=None, relax=1.0, x_sets=None, u_sets=None):
         """ADMM weights (Base.compute_Rr_Qr, isls/base.py:55-79, dp=True form) and the constraint sets: boxes
         (lo, hi) or `isls.projections.ConvexSets` (project_set_convex over the time steps, on the device)."""
@@ -199,22 +257,13 @@ class Engine:
             return r                                   # [N,d,d] or [B,N,d,d]
 
         has_x, has_u = x_box is not None or x_sets is not None, u_box is not None or u_sets is not None
-        self.Qr = weights(rho_x, n) if has_x else None
-        # a state weight that is the same at every step but the LAST (a terminal constraint: the arm notebook's bound on the
-        # final end-effector position) reaches the record feed-forward passes as one block plus the terminal block
-        # (isls_ff_args.Qr_term): they then run the one-hand-off kernel instead of loading a weight row per step
-        self.Qr_ff, self.Qr_term = None, None
-        if (self.Qr is not None and self.Qr.ndim == 3 and self.Qr.shape[0] == N and N > 2
-                and bool((self.Qr[:-1] == self.Qr[:1]).all())):
-            self.Qr_ff, self.Qr_term = self.Qr[:1].contiguous(), self.Qr[-1].contiguous()
-        self.Rr = weights(rho_u, m) if has_u else None
-        if has_x and self.Qr is None:
+        Qr = weights(rho_x, n) if has_x else None
+        Rr = weights(rho_u, m) if has_u else None
+        if has_x and Qr is None:
             raise ValueError("project_x needs rho_x")
-        if has_u and self.Rr is None:
+        if has_u and Rr is None:
             raise ValueError("project_u needs rho_u")
-        # (dx*dx)@Qr precedence (isls/isls.py:473,476): the AL weights are the row sums
-        self.wq = None if self.Qr is None else self.Qr.sum(-1).contiguous()
-        self.wr = None if self.Rr is None else self.Rr.sum(-1).contiguous()
+        self.set_weights(Qr, Rr)
 
         def bounds(box, d):
             if box is None:
@@ -231,8 +280,6 @@ class Engine:
         self.zx, self.lx = (z(B, N, n), z(B, N, n)) if has_x else (None, None)
         self.zu, self.lu = (z(B, N, m), z(B, N, m)) if has_u else (None, None)
         self.relax = float(relax)
-        self._outer_args = None
-        self._hess_dirty = True
 
         def device_sets(cs, d):
             """ConvexSets -> (isls_project_args descriptor, first column, scratch) with the operands on the device."""
@@ -265,61 +312,29 @@ class Engine:
         static = self.model in (capi.MODEL_DI, capi.MODEL_LTI)
         self.kern.linearize(self.model, self.model_par, self.xhat, self.uhat, self.A, self.Bm,
                             active=None if static else self.outer_active, stream=_stream_ptr())
-        self._mark_ab_made()
-        self._ab_static = self._ab_made if static else None
-
-    # ---- whose A, Bm the buffers hold: the feed-forward passes may use the model's structure only for the model's own
-    # linearisation (isls_ff_args.lin_on), never for a caller's A, B
-    def _mark_ab_made(self):
-        self._ab_made = (self.model, self.A.data_ptr(), self.Bm.data_ptr())
-        self._ab_caller = False
-
-    def ab_from_caller(self):
-        """A, Bm were written by somebody else (AB setter, get_AB callback): the dense records are the only valid form.
-        A cached isls_outer_args block keeps its pointers; run_outer() rewrites its hint fields when this state has changed."""
-        self._ab_made = None
-        self._ab_static = None
-        self._ab_caller = True
-
-    def _ab_is_static(self):
-        """A, Bm hold the one linearisation of a state-independent model, written for every trajectory"""
-        st = getattr(self, "_ab_static", None)
-        return st is not None and st == (self.model, self.A.data_ptr(), self.Bm.data_ptr())
-
-    def _apply_ff_lin(self, blocks, rec, seg=None):
-        """(re)write the hint fields of marshalled isls_gain_args / isls_ff_args blocks for the state of A, Bm now"""
-        lin = self.ff_lin(rec, seg)
-        for a in blocks:
-            capi.Kernels._set_lin(a, lin, self.B, self.dtype)
-        return lin
+        self._ab_src = STATIC if static else LINEARIZED
 
     def _structure_applies(self):
         """What every model-structured pass needs of the engine: the row-per-lane kernels for these dimensions, the forms not
         switched off (use_model_structure), a model whose structure the passes know, and ADMM weights that are the same at
         every step (Qr: or all but the last, which the passes take as the terminal block Qr_term)."""
-        if not self.fast_dims or not self.use_model_structure:
-            return False
-        if self.model not in (capi.MODEL_DI, capi.MODEL_ARM3R, capi.MODEL_CAR):
-            return False
-        inv = lambda W: W is None or W.ndim < 3 or W.shape[-3] == 1       # noqa: E731
-        return inv(self.Rr) and (inv(self.Qr) or getattr(self, "Qr_term", None) is not None)
+        return (self.fast_dims and self.use_model_structure and self.model in (capi.MODEL_DI, capi.MODEL_ARM3R, capi.MODEL_CAR)
+                and (self._w_invariant or self._w_terminal))
 
     def _structure_expected(self):
         """Will the passes of this engine get the model hint, as far as can be told before A, B are linearised: the structured
         forms apply and no A, B were handed in by a caller."""
-        return self._structure_applies() and not getattr(self, "_ab_caller", False)
+        return self._structure_applies() and self._ab_src != CALLER
 
-    def ff_lin(self, rec, seg=None):
+    def ff_lin(self, rec, seg=None, weights_as_is=False):
         """(model id, parameters) for isls_gain_args.lin_on / isls_ff_args.lin_on, or None.  The hint makes the gain pass write
         the LEAN records and the feed-forward passes read them, so it is given only when every pass on these records can take
-        the structured form: the structured forms apply (_structure_applies), the packed records are in use, A and Bm are what
-        isls_linearize wrote into the buffers the engine holds now for the model set now, and the passes run sequentially
-        (`seg`: the time-parallel form builds its operators from the dense records)."""
-        if rec is None or seg is not None or not self._structure_applies() or self.model_par is None:
-            return None
-        if getattr(self, "_ab_made", None) != (self.model, self.A.data_ptr(), self.Bm.data_ptr()):
-            return None
-        return (self.model, self.model_par)
+        the structured form: the structured forms apply (_structure_applies; `weights_as_is`: the passes take Qr as it is,
+        the same at every step), the packed records are in use, A and Bm are what isls_linearize wrote for the model set now,
+        and the passes run sequentially (`seg`: the time-parallel form builds its operators from the dense records)."""
+        ok = (rec is not None and seg is None and self.model_par is not None and self._ab_src in (LINEARIZED, STATIC)
+              and self._structure_applies() and (self._w_invariant or not weights_as_is))
+        return (self.model, self.model_par) if ok else None
 
     def _shared_hessian(self):
         """True when the cost Hessians are the same arrays for every trajectory of the batch: via-point cost with a batch-
@@ -335,7 +350,7 @@ class Engine:
         writes that form), else the per-trajectory arrays."""
         if not self._shared_hessian():
             return self.Cxx, self.Cuu
-        if getattr(self, "_Cxx_sh", None) is None:
+        if self._Cxx_sh is None:
             z = lambda *sh: torch.zeros(*sh, dtype=self.dtype, device=self.device)   # noqa: E731
             self._Cxx_sh, self._Cuu_sh = z(1, self.N, self.n, self.n), z(1, self.N, self.m, self.m)
             self._c0_sh = (z(1, self.N, self.n), z(1, self.N, self.m))
@@ -349,7 +364,7 @@ class Engine:
                                    Cuu=self.Cuu if with_hessian and not shared else None,
                                    Qr=self.Qr, Rr=self.Rr, active=self.outer_active, cost_model=self.cost_model,
                                    cost_par=self.cost_par, q_nonzero=self.q_nonzero, stream=_stream_ptr())
-        if shared and getattr(self, "_hess_dirty", True):       # constants of the problem: written once per cost / weights
+        if shared and self._hess_dirty:                        # constants of the problem: written once per cost / weights
             Cxx, Cuu = self.hessians()
             self._hess_dirty = False
             self.kern.expand_quadratic(self.Qtab, self.ztab[:1] if self.ztab.ndim == 3 else self.ztab, self.seq, self.u_std,
@@ -361,29 +376,52 @@ class Engine:
         themselves right before the feed-forward passes use it: the records are stale once K / fac are replaced."""
         if not self.fast_dims:
             return None
-        if getattr(self, "_ffrec", None) is None:
+        if self._ffrec is None:
             self._ffrec = torch.zeros(capi.ff_record_elems(self.B, self.N, self.n, self.m), dtype=self.dtype, device=self.device)
         return self._ffrec
 
-    def gain(self, active=None, rec=None, seg=None, structured=True):
+    # ---- argument blocks of the passes, for the single launches below and for build_outer -------------------------
+    def _gain_block(self, active, rec, lin):
+        # with the records, nothing after this pass reads Quu / fac / Qux: the gain pass then skips those stores
+        full = rec is None
+        return capi.Kernels.gain_args(self.A, self.Bm, *self.hessians(), self.K, self.Quu if full else None,
+                                      self.fac if full else None, self.Qux if full else None, Cux=self.Cux,
+                                      solve_mode=self.solve_mode, status=self.status, active=active, rec=rec, lin=lin)
+
+    def _ff_block(self, active, rec, seg, lin):
+        # on the packed records the weights take the terminal-block form where it applies
+        Qr, Qr_term = (self.Qr_ff, self.Qr_term) if rec is not None and self._w_terminal else (self.Qr, None)
+        return capi.Kernels.ff_args(self.A, self.Bm, self.c0x, self.c0u, self.K, self.Quu, self.fac, self.Qux, self.k,
+                                    Qr=Qr, Qr_term=Qr_term, Rr=self.Rr, xhat=self.xhat, uhat=self.uhat, zx=self.zx, lx=self.lx,
+                                    zu=self.zu, lu=self.lu, solve_mode=self.solve_mode, active=active, seg=seg, rec=rec, lin=lin)
+
+    def _rollout_block(self, L, active, flags=0, cost_all=None):
+        return capi.Kernels.rollout_args(self.model, self.model_par, self.K, self.k, self.xhat, self.uhat, self.alphas[:L],
+                                         self.Qtab, self.ztab, self.seq, self.u_std, self.xx, self.xu, best=self.best,
+                                         cost_new=self.cost_new, cost_all=cost_all, wq=self.wq, wr=self.wr, zx=self.zx,
+                                         lx=self.lx, zu=self.zu, lu=self.lu, cost_cur=self.cost, flags=flags,
+                                         status=self.status, active=active, q_nonzero=self.q_nonzero,
+                                         cost_model=self.cost_model, cost_par=self.cost_par)
+
+    def _admm_block(self, tol_abs, tol_rel, active):
+        return capi.Kernels.admm_args(self.xx, self.xu, self.res, zx=self.zx, lx=self.lx, zu=self.zu, lu=self.lu,
+                                      x_lo=self.x_lo, x_hi=self.x_hi, u_lo=self.u_lo, u_hi=self.u_hi, relax=self.relax,
+                                      tol_abs=tol_abs, tol_rel=tol_rel, res_prev=self.res_prev, active=active,
+                                      iters=self.admm_iters, x_sets=self.x_sets, x_col0=self.x_col0, x_work=self.x_work,
+                                      u_sets=self.u_sets, u_col0=self.u_col0, u_work=self.u_work)
+
+    def gain(self, active=None, rec=None, seg=None, weights_as_is=False):
         """Gain pass; with `rec` the caller promises to run its feed-forward passes on the records, and Quu / fac / Qux
         (which only those passes would read) are not written.  `seg`: the segment plan those passes will use (ff_lin);
-        `structured=False`: the caller's passes cannot take the model-structured form (it hands them other weights)."""
-        full = rec is None
-        lin = self.ff_lin(rec, seg) if structured else None
-        self._rec_layout = (None if rec is None else rec.data_ptr(), lin is not None)   # which records, lean or dense
-        self.kern.riccati_gain(self.A, self.Bm, *self.hessians(), self.K, self.Quu if full else None,
-                               self.fac if full else None, self.Qux if full else None,
-                               Cux=self.Cux, solve_mode=self.solve_mode, status=self.status, active=active, rec=rec,
-                               lin=lin, stream=_stream_ptr())
+        `weights_as_is`: the caller's passes take Qr, Rr as they are, not in the terminal-block form."""
+        lin = self.ff_lin(rec, seg, weights_as_is)
+        self._rec_lean = lin is not None
+        self.kern._call("riccati_gain", self.sfx, self._gain_block(active, rec, lin), _stream_ptr())
 
     def rec_lin(self, rec, seg=None):
         """The hint for a feed-forward pass on `rec` as the last gain pass left it: lean records need the structured form (and
         raise when it does not apply any more), dense ones the dense form."""
-        if rec is None:
-            return None
-        ptr, lean = getattr(self, "_rec_layout", (None, False))
-        if ptr != rec.data_ptr() or not lean:
+        if rec is None or not self._rec_lean:
             return None
         lin = self.ff_lin(rec, seg)
         if lin is None:
@@ -391,38 +429,19 @@ class Engine:
                                  "read (weights, segments or A, B changed since): run the gain pass again")
         return lin
 
-    def _ff_weights(self, rec):
-        """(Qr, Qr_term) operands of a feed-forward pass: the terminal-block form on the packed records when it applies"""
-        rr_inv = self.Rr is None or self.Rr.ndim < 3 or self.Rr.shape[-3] == 1
-        if rec is not None and getattr(self, "Qr_term", None) is not None and rr_inv:
-            return self.Qr_ff, self.Qr_term
-        return self.Qr, None
-
     def feedforward(self, active=None, seg=None, rec=None):
-        Qr, Qr_term = self._ff_weights(rec)
-        self.kern.riccati_ff(self.A, self.Bm, self.c0x, self.c0u, self.K, self.Quu, self.fac, self.Qux, self.k,
-                             Qr=Qr, Qr_term=Qr_term, Rr=self.Rr, xhat=self.xhat, uhat=self.uhat, zx=self.zx, lx=self.lx,
-                             zu=self.zu, lu=self.lu, solve_mode=self.solve_mode, active=active, seg=seg, rec=rec,
-                             lin=self.rec_lin(rec, seg), stream=_stream_ptr())
+        self.kern._call("riccati_ff", self.sfx, self._ff_block(active, rec, seg, self.rec_lin(rec, seg)), _stream_ptr())
 
     def rollout(self, L, flags=0, cost_all=None, active=None):
-        self.kern.rollout_ls(self.model, self.model_par, self.K, self.k, self.xhat, self.uhat, self.alphas[:L],
-                             self.Qtab, self.ztab, self.seq, self.u_std, self.xx, self.xu, best=self.best,
-                             cost_new=self.cost_new, cost_all=cost_all, wq=self.wq, wr=self.wr, zx=self.zx,
-                             lx=self.lx, zu=self.zu, lu=self.lu, cost_cur=self.cost, flags=flags,
-                             status=self.status, active=active, q_nonzero=self.q_nonzero, cost_model=self.cost_model,
-                             cost_par=self.cost_par, stream=_stream_ptr())
+        self.kern._call("rollout_ls", self.sfx, self._rollout_block(L, active, flags, cost_all), _stream_ptr())
 
     def admm_update(self, tol_abs, tol_rel, active=None):
-        self.kern.admm_update(self.xx, self.xu, self.res, zx=self.zx, lx=self.lx, zu=self.zu, lu=self.lu,
-                              x_lo=self.x_lo, x_hi=self.x_hi, u_lo=self.u_lo, u_hi=self.u_hi, relax=self.relax,
-                              tol_abs=tol_abs, tol_rel=tol_rel, res_prev=self.res_prev, active=active,
-                              iters=self.admm_iters, x_sets=self.x_sets, x_col0=self.x_col0, x_work=self.x_work,
-                              u_sets=self.u_sets, u_col0=self.u_col0, u_work=self.u_work, stream=_stream_ptr())
+        self.kern._call("admm_update", self.sfx, self._admm_block(tol_abs, tol_rel, active), _stream_ptr())
 
     # ---- time-parallel feed-forward pass (isls_ffseg): operators from the gain pass, reused by J ADMM iterations
-    def ff_seg(self, nseg_requested=None):
-        """Segment descriptor over engine-owned buffers, or None for the sequential recursion."""
+    def ff_seg(self, nseg_requested=None, ncol=1, weights_as_is=False):
+        """Segment descriptor over engine-owned buffers, or None for the sequential recursion.  `ncol`: columns per trajectory
+        the passes solve (ColumnSolver); `weights_as_is`: the passes take Qr, Rr as they are (ff_lin)."""
         if not self.fast_dims:
             return None                                        # the generic kernels recurse sequentially
         if nseg_requested is None:
@@ -433,12 +452,15 @@ class Engine:
             # 30 us in four segments).  Where the model-structured passes apply (ff_lin) they exist for the sequential
             # recursion only and carry the cheaper gain pass with them: outer iteration at n=6, m=3 (tools/kbench.py, one box)
             # B=256: 504 us segmented / 511 us structured, 512: 517 / 510, 1024: 553 / 535, 1536: 608 / 559 -- sequential from 512.
+            # The C columns of B problems stream like a batch of C B trajectories: at 4 x 1024 arm columns the structured
+            # sequential pass takes 83 us, the dense one in four segments 107 us.
             seq_from = 512 if self._structure_expected() else 2048
-            nseg_requested = int(os.environ.get("ISLS_FF_NSEG", "1" if self.B >= seq_from else "4"))
+            seq = self.B >= seq_from or (ncol * self.B >= 2048 and self.ff_lin(self.ff_record(), None, weights_as_is) is not None)
+            nseg_requested = int(os.environ.get("ISLS_FF_NSEG", "1" if seq else "4"))
         nseg, seg_len = self.kern.ff_segments(self.N, nseg_requested)
         if nseg < 2:
             return None
-        if getattr(self, "_seg_bufs", None) is None or self._seg_bufs[1].shape[1] != nseg:
+        if self._seg_bufs is None or self._seg_bufs[1].shape[1] != nseg:
             z = lambda *shape: torch.zeros(*shape, dtype=self.dtype, device=self.device)
             self._seg_bufs = (z(self.B, self.N, self.m, self.n), z(self.B, nseg, self.n, self.n), z(self.B, nseg, self.n))
         return capi.Kernels.ff_seg(*self._seg_bufs, seg_len)
@@ -451,51 +473,32 @@ class Engine:
     def build_outer(self, L, J, tol_abs=0.0, tol_rel=0.0, log=None, ff_nseg=None, begin_done=False):
         """Marshal the argument block of isls_ilqr_admm_outer once; it stays valid while buffers are not re-allocated.
         begin_done: the caller ends every outer iteration with `advance()`, which also makes the ADMM restart of the next one."""
-        K = capi.Kernels
         rec = self.ff_record()
         seg = self.ff_seg(ff_nseg)
-        # with the records, nothing in this driver reads Quu / fac / Qux: the gain pass then skips those stores
-        full = rec is None
-        gain = K.gain_args(self.A, self.Bm, *self.hessians(), self.K, self.Quu if full else None, self.fac if full else None,
-                           self.Qux if full else None, Cux=self.Cux, solve_mode=self.solve_mode, status=self.status,
-                           active=self.admm_active, rec=rec, lin=self.ff_lin(rec, seg))
-        Qr_ff, Qr_term = self._ff_weights(rec)
-        ff = K.ff_args(self.A, self.Bm, self.c0x, self.c0u, self.K, self.Quu, self.fac, self.Qux, self.k,
-                       Qr=Qr_ff, Qr_term=Qr_term, Rr=self.Rr, xhat=self.xhat, uhat=self.uhat, zx=self.zx, lx=self.lx, zu=self.zu,
-                       lu=self.lu, solve_mode=self.solve_mode, active=self.admm_active, seg=seg, rec=rec,
-                       lin=self.ff_lin(rec, seg))
-        ro = K.rollout_args(self.model, self.model_par, self.K, self.k, self.xhat, self.uhat, self.alphas[:L],
-                            self.Qtab, self.ztab, self.seq, self.u_std, self.xx, self.xu, best=self.best,
-                            cost_new=self.cost_new, wq=self.wq, wr=self.wr, zx=self.zx, lx=self.lx, zu=self.zu,
-                            lu=self.lu, cost_cur=self.cost, flags=0, status=self.status, active=self.admm_active,
-                            q_nonzero=self.q_nonzero, cost_model=self.cost_model, cost_par=self.cost_par)
-        admm = K.admm_args(self.xx, self.xu, self.res, zx=self.zx, lx=self.lx, zu=self.zu, lu=self.lu,
-                           x_lo=self.x_lo, x_hi=self.x_hi, u_lo=self.u_lo, u_hi=self.u_hi, relax=self.relax,
-                           tol_abs=tol_abs, tol_rel=tol_rel, res_prev=self.res_prev, active=self.admm_active,
-                           iters=self.admm_iters, x_sets=self.x_sets, x_col0=self.x_col0, x_work=self.x_work,
-                           u_sets=self.u_sets, u_col0=self.u_col0, u_work=self.u_work)
-        self._outer_args = capi.OuterArgs(gain=gain, ff=ff, ro=ro, admm=admm, J=int(J), skip_gain=0, begin_done=int(bool(begin_done)))
-        self._outer_rec, self._outer_seg = rec, seg
-        self._outer_lin_state = (getattr(self, "_ab_made", None), self.use_model_structure)
+        lin = self.ff_lin(rec, seg)
+        act = self.admm_active
+        self._outer_args = capi.OuterArgs(gain=self._gain_block(act, rec, lin), ff=self._ff_block(act, rec, seg, lin),
+                                          ro=self._rollout_block(L, act), admm=self._admm_block(tol_abs, tol_rel, act),
+                                          J=int(J), skip_gain=0, begin_done=int(bool(begin_done)), log=capi._ptr(log),
+                                          outer_active=capi._ptr(self.outer_active))
+        self._outer_rec, self._outer_seg, self._outer_log = rec, seg, log
+        self._outer_lin_state = (self._ab_src, self.use_model_structure)
         self._advance_args = None
-        self._outer_args.log = capi._ptr(log)
-        self._outer_args.outer_active = capi._ptr(self.outer_active)
-        self._outer_log = log
         return self._outer_args
 
     def run_outer(self):
         """gain -> J x [ff -> rollout/line-search -> ADMM update] on the current stream (no host sync)."""
-        fn = getattr(library(), f"isls_ilqr_admm_outer_{self.sfx}")
-        fn.restype = ctypes.c_int
-        state = (getattr(self, "_ab_made", None), self.use_model_structure)
-        if state != getattr(self, "_outer_lin_state", ()):     # A, Bm changed hands since the block was marshalled / last run
-            self._apply_ff_lin((self._outer_args.gain, self._outer_args.ff), self._outer_rec, self._outer_seg)
+        if self._outer_args is None:
+            raise capi.IslsError("no isls_outer_args block for the engine's buffers as they are now: call build_outer()")
+        state = (self._ab_src, self.use_model_structure)
+        if state != self._outer_lin_state:                     # A, Bm changed hands since the block was marshalled / last run
+            lin = self.ff_lin(self._outer_rec, self._outer_seg)
+            for a in (self._outer_args.gain, self._outer_args.ff):
+                capi.Kernels._set_lin(a, lin, self.B, self.dtype)
             self._outer_lin_state = state
         if self._outer_rec is not None:                        # the driver's gain pass leaves the records in this layout
-            self._rec_layout = (self._outer_rec.data_ptr(), bool(self._outer_args.gain.lin_on))
-        rc = fn(ctypes.byref(self._outer_args), ctypes.c_void_p(_stream_ptr()))
-        if rc != capi.OK:
-            raise capi.IslsError(f"isls_ilqr_admm_outer_{self.sfx} -> {rc}")
+            self._rec_lean = bool(self._outer_args.gain.lin_on)
+        self.kern._call("ilqr_admm_outer", self.sfx, self._outer_args, _stream_ptr())
 
     def accept_x_step(self, tol_cost=-1.0, tol_osc=-1.0):
         """nominal_values <- last x-step of the ADMM (isls/isls.py:488), cost_log tail and the outer stop
@@ -521,13 +524,13 @@ class Engine:
         trajectories still iterating.  Pair it with build_outer(..., begin_done=True).  `linearize=False` leaves A, B alone (a
         shared LTI pair).  The cost Hessians must be the batch-shared tables (written once by expand())."""
         K = capi.Kernels
-        if linearize and self.use_model_structure and self._ab_is_static():
+        if linearize and self.use_model_structure and self._ab_src == STATIC:
             linearize = False                                  # the model's one linearisation is in place: nothing to rewrite
         key = (float(tol_cost), float(tol_osc), bool(linearize))
-        if getattr(self, "_advance_args", None) is None or self._advance_args[0] != key:
+        if self._advance_args is None or self._advance_args[0] != key:
             if not self._shared_hessian():
                 raise capi.IslsError("Engine.advance() serves the batch-shared cost Hessians; use accept_x_step / linearize / expand")
-            if getattr(self, "_hess_dirty", True):
+            if self._hess_dirty:
                 self.expand()                                  # writes the shared Hessian tables once
             acc = K.accept_args(self.xx, self.xu, self.cost_new, self.xhat, self.uhat, self.cost, cost_hist=self.cost_hist,
                                 hist_len=self.hist_len, tol_cost=tol_cost, tol_osc=tol_osc, outer_active=self.outer_active)
@@ -537,8 +540,8 @@ class Engine:
             self._advance_args = (key, K.advance_args(acc, lin, exp, admm_active=self.admm_active, iters=self.admm_iters,
                                                       lx=self.lx, lu=self.lu, res_prev=self.res_prev))
         self.kern.outer_advance(self._advance_args[1], self.sfx, stream=_stream_ptr())
-        if linearize:
-            self._mark_ab_made()                               # the launch linearised the trajectories still iterating
+        if linearize and self._ab_src != STATIC:
+            self._ab_src = LINEARIZED                          # the launch linearised the trajectories still iterating
 
     def reduce(self, table=None, rank=0):
         """[sum cost, max prim, max dual, #active, #failed] of the local shard, left on the device: in `out5`, or straight

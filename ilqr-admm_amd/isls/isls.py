@@ -101,15 +101,14 @@ class iSLS(Base):
         e = self.engine
         # a linearisation of the same shape as the one in use is copied INTO the buffers the engine already holds: argument blocks
         # and captured HIP graphs (isls_admm) keep raw device pointers, and a get_AB callback delivers a fresh array per outer
-        # iteration -- replacing the tensors would leave those pointers on freed memory
+        # iteration -- replacing the tensors would leave those pointers on freed memory (the engine drops its own cached blocks)
         for name, new in (("A", e._t(A)), ("Bm", e._t(B))):
             old = getattr(e, name)
             if old is not None and old.shape == new.shape and old.is_contiguous():
                 old.copy_(new)
             else:
                 setattr(e, name, new)
-                e._outer_args = None
-        e.ab_from_caller()
+        e.ab_from_caller()                                      # written in place or not, a caller's A, B
         self._user_AB = True
 
     @property

@@ -68,16 +68,9 @@ class ColumnSolver:
                     raise ValueError(f"project_{key} needs rho_{key}")
                 self.blocks[key]["W"] = W
         self.rec = e.ff_record()
-        self.seg = e.ff_seg()                                   # planned before the gain pass: it decides the records' layout
-        inv = lambda W: W is None or W.ndim < 3 or W.shape[-3] == 1                      # noqa: E731
-        structured = inv(e.Qr) and inv(e.Rr)                    # x_step hands e.Qr, e.Rr over as they are
-        if (self.seg is not None and structured and self.C * e.B >= 2048 and "ISLS_FF_NSEG" not in os.environ
-                and e.ff_lin(self.rec, None) is not None):
-            # the C columns of B problems stream like a batch of C B trajectories, and the model-structured form exists for the
-            # sequential recursion only (the segment operators come from the dense records): at 4 x 1024 arm columns the
-            # structured sequential pass takes 83 us, the dense one in four segments 107 us
-            self.seg = None
-        e.gain(active=active, rec=self.rec, seg=self.seg, structured=structured)
+        # the segment plan is made before the gain pass: it decides the records' layout.  x_step hands e.Qr, e.Rr over as they are
+        self.seg = e.ff_seg(ncol=self.C, weights_as_is=True)
+        e.gain(active=active, rec=self.rec, seg=self.seg, weights_as_is=True)
         self.seg_cols = None
         if self.seg is not None:
             e.feedforward_prepare(self.seg, active=active, rec=self.rec)
@@ -102,9 +95,7 @@ class ColumnSolver:
     def _columns_in_one_launch(self):
         """The C passes ride in one launch on the packed records when the ADMM weights do not depend on the time step (the
         one-hand-off kernel's condition); ISLS_ADMM_FF_COLUMNS=0 keeps one launch per column."""
-        e = self.e
-        inv = lambda W: W is None or W.ndim < 3 or W.shape[-3] == 1                      # noqa: E731
-        return self.rec is not None and inv(e.Qr) and inv(e.Rr) and os.environ.get("ISLS_ADMM_FF_COLUMNS", "1") != "0"
+        return self.rec is not None and self.e._w_invariant and os.environ.get("ISLS_ADMM_FF_COLUMNS", "1") != "0"
 
     def x_step(self):
         """[d_x, phi_x], [d_u, phi_u] for the targets z - lmb: C feed-forward passes, then the column rollout.  A weight that
@@ -322,7 +313,7 @@ def isls_admm(self, dim, get_AB=None, get_Cs=None, project_x=False, project_u=Fa
     def captured_pointers():
         """device addresses a recorded ADMM iteration reads or writes through engine attributes a callback may replace"""
         ts = [e.A, e.Bm, e.c0x, e.c0u, e.K, e.Qr, e.Rr, e.xhat, e.uhat, e.xx, e.xu, e.Qtab, e.ztab, e.model_par, e.cost_par,
-              cs.rec, cs.Cuu] + (list(e._seg_bufs) if getattr(e, "_seg_bufs", None) is not None and cs.seg is not None else [])
+              cs.rec, cs.Cuu] + (list(e._seg_bufs) if cs.seg is not None else [])
         return tuple(None if t is None else t.data_ptr() for t in ts)
 
     mark = getattr(self, "_bench_mark", None)                                   # bench.py: t1 behind the first outer iteration (the

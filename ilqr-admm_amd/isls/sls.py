@@ -84,8 +84,8 @@ class SLS(Base):
         e = self.engine
         B, N, n, m = self.batch, self.N, self.x_dim, self.u_dim
         z = lambda *s: torch.zeros(*s, dtype=e.dtype, device=e.device)   # noqa: E731
-        e.Qr = None if Qr is None else e._t(np.asarray(Qr))
-        e.Rr = None if Rr is None else e._t(np.stack([np.asarray(r) for r in Rr]) if isinstance(Rr, (list, tuple)) else np.asarray(Rr))
+        e.set_weights(None if Qr is None else e._t(np.asarray(Qr)),
+                      None if Rr is None else e._t(np.stack([np.asarray(r) for r in Rr]) if isinstance(Rr, (list, tuple)) else np.asarray(Rr)))
         if Qr is not None:
             assert xr is not None
             e.zx, e.lx = e._t(self._batched(np.asarray(xr).reshape(-1, N, n) if np.ndim(xr) > 1 else np.asarray(xr).reshape(N, n), 2)), z(B, N, n)
