@@ -314,6 +314,7 @@ ISLS_API const char *isls_error_string(int code)
         case ISLS_ERR_ARG: return "bad argument (null pointer or dimension)";
         case ISLS_ERR_UNSUPPORTED: return "unsupported (n,m) pair, model, projection or L";
         case ISLS_ERR_LAUNCH: return "HIP launch failed";
+        case ISLS_ERR_COMPILE: return "user model: run-time compile failed (isls_user_model_log) or hiprtc not found";
         default: return "unknown";
     }
 }

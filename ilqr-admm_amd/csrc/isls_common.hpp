@@ -11,9 +11,13 @@
 // Nothing in here assumes a dispatch order or an XCD placement.
 #pragma once
 
+#ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#else
+typedef struct ihipStream_t *hipStream_t;   // run-time compilation of a user model (user_model.hip): device code only
+#endif
 
 #include <type_traits>
 #include <utility>
@@ -267,10 +271,12 @@ template <typename T> int launch_outer_begin(int32_t B, int32_t N, int32_t n, in
                                              const int32_t *outer_active, void *lx, void *lu, void *res_prev,
                                              int32_t *iters, hipStream_t s);
 
+#ifndef __HIPCC_RTC__
 inline int check_launch()
 {
     return hipGetLastError() == hipSuccess ? ISLS_OK : ISLS_ERR_LAUNCH;
 }
+#endif
 
 // Supported (n, m) pairs: the reference notebooks' systems and every get_double_integrator_AB(nb_dim <= 3,
 // nb_deriv <= 3) system (isls/utils.py:266-276: n = nb_dim * nb_deriv, m = nb_dim).  The kernels are templates over the
@@ -289,6 +295,14 @@ inline int check_launch()
         else if (n_ == 3 && m_ == 3) { CALL(3, 3); }    \
         else return ISLS_ERR_UNSUPPORTED;               \
     }
+// template id of the run-time compiled user models (user_model.hpp): their kernels show up as rollout_kernel<T, n, m, 99, JM, OCC>
+constexpr int ISLS_MODEL_USER = 99;
+#ifndef __HIPCC_RTC__
+// user models (isls_user_model_create: ids >= ISLS_MODEL_USER_BASE): user_model.hip launches their kernels from the module of the
+// model, compiled at run time, with the launch plans of the built-ins
+inline bool is_user_model(int model) { return model >= ISLS_MODEL_USER_BASE; }
+template <typename T> int launch_linearize_user(const isls_linearize_args &a, hipStream_t s);
+#endif
 inline bool dims_supported(int n, int m)
 {
 #define ISLS_DIMS_TEST_(NX_, NU_) if (n == NX_ && m == NU_) return true;

@@ -342,6 +342,7 @@ static int linearize_params(const isls_linearize_args &a, LinP<T> &p, size_t *ta
 template <typename T>
 int launch_linearize(const isls_linearize_args &a, hipStream_t s)
 {
+    if (is_user_model(a.model)) return launch_linearize_user<T>(a, s);     // user_model.hip: forward-mode dual numbers
     LinP<T> p;
     size_t tab_words = 0;
     const int rc = linearize_params<T>(a, p, &tab_words);
@@ -570,7 +571,17 @@ int launch_advance(const isls_advance_args &a, hipStream_t s)
     size_t tab_words = 0;
     p.has_lin = a.lin.A != nullptr;
     p.has_exp = a.exp.c0x != nullptr;
+    // a user model's linearisation is a launch of its own module: the advance runs without it, and the linearisation follows on
+    // the same stream for the trajectories still iterating (outer_active after the stop rules), about the nominal just written
+    const bool user_lin = p.has_lin && is_user_model(a.lin.model);
+    isls_linearize_args ulin = a.lin;
     int rc;
+    if (user_lin) {
+        if (a.lin.B != ac.B || a.lin.N != ac.N || a.lin.n != ac.n || a.lin.m != ac.m) return ISLS_ERR_ARG;
+        if (!a.lin.model_par || !a.lin.Bm || !a.lin.xhat || !a.lin.uhat) return ISLS_ERR_ARG;
+        ulin.active = ac.outer_active;
+        p.has_lin = 0;
+    }
     if (p.has_lin) {
         if ((rc = linearize_params<T>(a.lin, p.lin, &tab_words)) != ISLS_OK) return rc;
         if (a.lin.B != ac.B || a.lin.N != ac.N || a.lin.n != ac.n || a.lin.m != ac.m) return ISLS_ERR_ARG;
@@ -586,7 +597,8 @@ int launch_advance(const isls_advance_args &a, hipStream_t s)
     }
     if (ac.B == 0) return ISLS_OK;
     hipLaunchKernelGGL((advance_kernel<T>), dim3(ac.B), dim3(64), tab_words * sizeof(T), s, p);
-    return check_launch();
+    if ((rc = check_launch()) != ISLS_OK || !user_lin) return rc;
+    return launch_linearize_user<T>(ulin, s);
 }
 template int launch_advance<double>(const isls_advance_args &, hipStream_t);
 template int launch_advance<float>(const isls_advance_args &, hipStream_t);

@@ -1,5 +1,6 @@
 // rollout.hip -- dispatcher of the line-search rollout (kernel template: rollout_kernel.hpp; one translation unit per
-// (n, m, model) family: rollout_family.hip compiled with -DISLS_FAM_*), plus the Monte-Carlo closed loop of a dense controller.
+// (n, m, model) family: rollout_family.hip compiled with -DISLS_FAM_*), plus the Monte-Carlo closed loop of a dense controller
+// (kernel: rollout_kernel.hpp).  User models (ids >= ISLS_MODEL_USER_BASE) go to user_model.hip.
 #include "rollout_kernel.hpp"
 
 namespace isls {
@@ -65,6 +66,11 @@ int launch_rollout(const isls_rollout_args &a, hipStream_t s, const isls_admm_ar
         p.fa_res = (T *)f.res; p.fa_res_prev = (T *)f.res_prev; p.fa_active = f.active; p.fa_iters = f.iters;
     }
     int rc = ISLS_ERR_UNSUPPORTED;
+    if (is_user_model(a.model)) {                              // user_model.hip: the same plan, the model's own module
+        rc = launch_rollout_user<T>(p, a, s, fused != nullptr);
+        if (did_fuse) *did_fuse = rc == ISLS_OK && p.fa_on != 0;
+        return rc;
+    }
 #define FAMILY(NX_, NU_, MODEL_) \
     if (a.n == NX_ && a.m == NU_ && a.model == MODEL_) rc = launch_rollout_family<T, NX_, NU_, MODEL_>(p, a, s, fused != nullptr, nullptr);
     FAMILY(4, 2, ISLS_MODEL_LTI)
@@ -88,48 +94,6 @@ int launch_rollout(const isls_rollout_args &a, hipStream_t s, const isls_admm_ar
 template int launch_rollout<double>(const isls_rollout_args &, hipStream_t, const isls_admm_args *, bool *, bool);
 template int launch_rollout<float>(const isls_rollout_args &, hipStream_t, const isls_admm_args *, bool *, bool);
 
-// ---------------------------------------------------------------------------------------------------------------------
-// Monte-Carlo closed loop of a dense causal controller about a nominal (iSLSBase.get_trajectory_sls,
-// isls/isls_base.py:28-42): one thread per initial state, the state history is the thread's own x_log row.
-// ---------------------------------------------------------------------------------------------------------------------
-template <typename T>
-struct DenseLoopP {
-    int M, N;
-    const T *par, *K, *k, *xhat, *uhat, *x0;
-    T *x_log, *u_log;
-};
-
-template <typename T, int NX, int NU, int MODEL>
-__global__ __launch_bounds__(64) void dense_closed_loop_kernel(DenseLoopP<T> p)
-{
-    extern __shared__ __align__(16) unsigned char dl_smem[];
-    Model<T, NX, NU, MODEL> mdl;
-    mdl.load(p.par, reinterpret_cast<T *>(dl_smem), threadIdx.x, 64);
-    __syncthreads();
-    const int s = blockIdx.x * 64 + threadIdx.x;
-    if (s >= p.M) return;
-    const int N = p.N;
-    T *xs = p.x_log + (int64_t)s * N * NX, *us = p.u_log + (int64_t)s * N * NU;
-    T x[NX], u[NU], xn[NX];
-#pragma unroll
-    for (int j = 0; j < NX; ++j) x[j] = p.x0[(int64_t)s * NX + j];
-    for (int i = 0; i < N; ++i) {
-#pragma unroll
-        for (int j = 0; j < NX; ++j) xs[i * NX + j] = x[j];
-#pragma unroll
-        for (int r = 0; r < NU; ++r) {
-            const T *Kr = p.K + (int64_t)(i * NU + r) * N * NX;
-            T acc = T(0);
-            for (int j = 0; j < (i + 1) * NX; ++j) acc += (xs[j] - (p.xhat ? p.xhat[j] : T(0))) * Kr[j];
-            u[r] = (acc + p.k[i * NU + r]) + (p.uhat ? p.uhat[i * NU + r] : T(0));
-            us[i * NU + r] = u[r];
-        }
-        mdl.step(x, u, xn);
-#pragma unroll
-        for (int j = 0; j < NX; ++j) x[j] = xn[j];
-    }
-}
-
 template <typename T>
 int launch_dense_closed_loop(const isls_dense_loop_args &a, hipStream_t s)
 {
@@ -140,6 +104,7 @@ int launch_dense_closed_loop(const isls_dense_loop_args &a, hipStream_t s)
     p.par = (const T *)a.model_par; p.K = (const T *)a.K; p.k = (const T *)a.k;
     p.xhat = (const T *)a.xhat; p.uhat = (const T *)a.uhat; p.x0 = (const T *)a.x0;
     p.x_log = (T *)a.x_log; p.u_log = (T *)a.u_log;
+    if (is_user_model(a.model)) return launch_dense_closed_loop_user<T>(p, a, s);
     const int grid = (a.M + 63) / 64;
 #define LAUNCH(NX_, NU_, MODEL_)                                                                                          \
     hipLaunchKernelGGL((dense_closed_loop_kernel<T, NX_, NU_, MODEL_>), dim3(grid), dim3(64),                              \

@@ -947,17 +947,44 @@ __global__ __launch_bounds__(64, OCC) void rollout_kernel(RoP<T> p)
 #endif
 }
 
-// Launch of one (n, m, model) family: geometry of the winner replay, LDS budget, load-slot count.  Instantiated once per
-// family in rollout_<family>.hip; the dispatcher in rollout.hip picks the family.
-template <typename T, int NX, int NU, int MODEL>
-int launch_rollout_family(RoP<T> &p, const isls_rollout_args &a, hipStream_t s, bool want_fused, bool *stage_ok);
+// Run-time choices of a rollout launch: workgroups, dynamic LDS, and the (JM, OCC) instantiation of rollout_kernel.
+struct RoLaunch {
+    int grid;
+    size_t smem;
+    int jm, occ;                   // template arguments of the kernel to launch
+};
 
-#define ISLS_ROLLOUT_FAMILY_DECL(NX_, NU_, MODEL_)                                                                                         \
-    extern template int launch_rollout_family<double, NX_, NU_, MODEL_>(RoP<double> &, const isls_rollout_args &, hipStream_t, bool, bool *); \
-    extern template int launch_rollout_family<float, NX_, NU_, MODEL_>(RoP<float> &, const isls_rollout_args &, hipStream_t, bool, bool *);
+// The load-slot counts instantiated per occupancy class (index 0..3; a repeated value is the same kernel): 1, 2, 3 and the
+// family's maximum for its narrowest slots of that class.  The built-in families and the run-time compiled user models
+// (user_model.hip) instantiate exactly these, and ro_pick_jm below maps a launch's load-slot need onto them.
+template <int NX, int NU>
+__host__ __device__ constexpr int ro_jm_variant(int occ, int i)
+{
+    constexpr int J2MAX = (RoLayout<NX, NU>::MAXPAIRS + 15) / 16, J1MAX = (RoLayout<NX, NU>::MAXPAIRS + 7) / 8;
+    return occ == 2 ? (i == 0 ? 1 : i == 1 ? (J2MAX >= 2 ? 2 : 1) : J2MAX)
+                    : (i == 0 ? 1 : i == 1 ? (J1MAX >= 2 ? 2 : 1) : i == 2 ? (J1MAX >= 3 ? 3 : 1) : J1MAX);
+}
+template <int NX, int NU>
+__host__ __device__ constexpr int ro_pick_jm(int occ, int jm)
+{
+    if (occ == 2) {
+        if (jm <= 1) return ro_jm_variant<NX, NU>(2, 0);
+        if (jm <= 2) return ro_jm_variant<NX, NU>(2, 1);
+        return jm <= ro_jm_variant<NX, NU>(2, 2) ? ro_jm_variant<NX, NU>(2, 2) : 0;
+    }
+    if (jm <= 1) return ro_jm_variant<NX, NU>(1, 0);
+    if (jm <= 2) return ro_jm_variant<NX, NU>(1, 1);
+    if (jm <= 3) return ro_jm_variant<NX, NU>(1, 2);
+    return jm <= ro_jm_variant<NX, NU>(1, 3) ? ro_jm_variant<NX, NU>(1, 3) : 0;
+}
 
-template <typename T, int NX, int NU, int MODEL>
-int launch_rollout_family_impl(RoP<T> &p, const isls_rollout_args &a, hipStream_t s, bool want_fused, bool *stage_ok)
+#ifndef __HIPCC_RTC__
+// Launch plan of one (n, m) rollout: geometry of the winner replay, LDS budget, load-slot count, occupancy.  It depends on the
+// model only through its LDS words (MDLW), so a user model (no LDS words) gets the plan of the nonlinear built-ins of its
+// dimensions, decision for decision.  Fills p (tpw, seg_lanes, seg_len, nseg, stage_on, u_off; fa_on off when the stage does
+// not fit) and `out`.
+template <typename T, int NX, int NU, int MDLW>
+int plan_rollout(RoP<T> &p, const isls_rollout_args &a, bool want_fused, bool *stage_ok, RoLaunch &out)
 {
     using LY = RoLayout<NX, NU>;
     const int GL = a.L > 8 ? a.L : 8;
@@ -969,7 +996,6 @@ int launch_rollout_family_impl(RoP<T> &p, const isls_rollout_args &a, hipStream_
     // each, ro_replay).  An iteration of the one-lane form is a scattered gather (~4x the time of the row form's), so the
     // row form wins unless it gets far fewer segments
     bool stage_on = true;
-    constexpr int MDLW = Model<T, NX, NU, MODEL>::LDS_WORDS;
     auto smem_bytes = [&](int ns) { return (size_t)TPW * LY::slot_elems(a.L, GL, ns, a.N, stage_on, MDLW) * sizeof(T); };
     // the winner's trajectory is collected in LDS when that keeps the workgroup under 28 KB (>= 5 per CU) ...
     size_t lds_limit = 26 * 1024 + 512;                        // <= 26.5 KB per wavefront keeps 6 workgroups per CU
@@ -994,7 +1020,7 @@ int launch_rollout_family_impl(RoP<T> &p, const isls_rollout_args &a, hipStream_
             }
         }
     }
-    const int grid = (a.B + TPW - 1) / TPW;
+    out.grid = (a.B + TPW - 1) / TPW;
     p.tpw = TPW;
     auto fit = [&](int ns) {
         if (ns > a.N) ns = a.N;
@@ -1013,25 +1039,44 @@ int launch_rollout_family_impl(RoP<T> &p, const isls_rollout_args &a, hipStream_
     p.u_off = LY::u_off(a.L, p.nseg, a.N);
     if (stage_ok) *stage_ok = stage_on;
     if (!stage_on) p.fa_on = 0;                                 // the fused update reads x, u from the stage: the caller runs it as its own launch
-    const size_t smem = smem_bytes(p.nseg);
-    if (smem > 64 * 1024) return ISLS_ERR_UNSUPPORTED;
+    out.smem = smem_bytes(p.nseg);
+    if (out.smem > 64 * 1024) return ISLS_ERR_UNSUPPORTED;
     const bool absolute = (a.flags & ISLS_RO_ABSOLUTE) != 0;
     const int pairs = LY::pairs_needed(!absolute && a.xhat, !absolute && a.uhat, a.wq.p != nullptr, a.wq.p && a.wq.st != 0,
                                        a.wr.p != nullptr, a.wr.p && a.wr.st != 0);
-    const int jm = (pairs + GL - 1) / GL;
-    // instantiated load-slot counts: 1, 2, 3 and the family's maximum for its narrowest slots of that occupancy class
-    constexpr int J2MAX = (LY::MAXPAIRS + 15) / 16, J1MAX = (LY::MAXPAIRS + 7) / 8;
-    if (occ2) {
-        if (jm <= 1) hipLaunchKernelGGL((rollout_kernel<T, NX, NU, MODEL, 1, 2>), dim3(grid), dim3(64), smem, s, p);
-        else if (jm <= 2) hipLaunchKernelGGL((rollout_kernel<T, NX, NU, MODEL, (J2MAX >= 2 ? 2 : 1), 2>), dim3(grid), dim3(64), smem, s, p);
-        else if (jm <= J2MAX) hipLaunchKernelGGL((rollout_kernel<T, NX, NU, MODEL, J2MAX, 2>), dim3(grid), dim3(64), smem, s, p);
-        else return ISLS_ERR_UNSUPPORTED;
+    out.occ = occ2 ? 2 : 1;
+    out.jm = ro_pick_jm<NX, NU>(out.occ, (pairs + GL - 1) / GL);
+    return out.jm > 0 ? ISLS_OK : ISLS_ERR_UNSUPPORTED;
+}
+
+// Launch of one (n, m, model) family with hipLaunchKernelGGL.  Instantiated once per family in rollout_<family>.hip; the
+// dispatcher in rollout.hip picks the family.
+template <typename T, int NX, int NU, int MODEL>
+int launch_rollout_family(RoP<T> &p, const isls_rollout_args &a, hipStream_t s, bool want_fused, bool *stage_ok);
+
+#define ISLS_ROLLOUT_FAMILY_DECL(NX_, NU_, MODEL_)                                                                                         \
+    extern template int launch_rollout_family<double, NX_, NU_, MODEL_>(RoP<double> &, const isls_rollout_args &, hipStream_t, bool, bool *); \
+    extern template int launch_rollout_family<float, NX_, NU_, MODEL_>(RoP<float> &, const isls_rollout_args &, hipStream_t, bool, bool *);
+
+template <typename T, int NX, int NU, int MODEL>
+int launch_rollout_family_impl(RoP<T> &p, const isls_rollout_args &a, hipStream_t s, bool want_fused, bool *stage_ok)
+{
+    RoLaunch pl;
+    const int rc = plan_rollout<T, NX, NU, Model<T, NX, NU, MODEL>::LDS_WORDS>(p, a, want_fused, stage_ok, pl);
+    if (rc != ISLS_OK) return rc;
+    constexpr int V20 = ro_jm_variant<NX, NU>(2, 0), V21 = ro_jm_variant<NX, NU>(2, 1), V22 = ro_jm_variant<NX, NU>(2, 2);
+    constexpr int V10 = ro_jm_variant<NX, NU>(1, 0), V11 = ro_jm_variant<NX, NU>(1, 1), V12 = ro_jm_variant<NX, NU>(1, 2),
+                  V13 = ro_jm_variant<NX, NU>(1, 3);
+    const dim3 g(pl.grid), w(64);
+    if (pl.occ == 2) {
+        if (pl.jm == V20) hipLaunchKernelGGL((rollout_kernel<T, NX, NU, MODEL, V20, 2>), g, w, pl.smem, s, p);
+        else if (pl.jm == V21) hipLaunchKernelGGL((rollout_kernel<T, NX, NU, MODEL, V21, 2>), g, w, pl.smem, s, p);
+        else hipLaunchKernelGGL((rollout_kernel<T, NX, NU, MODEL, V22, 2>), g, w, pl.smem, s, p);
     } else {
-        if (jm <= 1) hipLaunchKernelGGL((rollout_kernel<T, NX, NU, MODEL, 1, 1>), dim3(grid), dim3(64), smem, s, p);
-        else if (jm <= 2) hipLaunchKernelGGL((rollout_kernel<T, NX, NU, MODEL, (J1MAX >= 2 ? 2 : 1), 1>), dim3(grid), dim3(64), smem, s, p);
-        else if (jm <= 3) hipLaunchKernelGGL((rollout_kernel<T, NX, NU, MODEL, (J1MAX >= 3 ? 3 : 1), 1>), dim3(grid), dim3(64), smem, s, p);
-        else if (jm <= J1MAX) hipLaunchKernelGGL((rollout_kernel<T, NX, NU, MODEL, J1MAX, 1>), dim3(grid), dim3(64), smem, s, p);
-        else return ISLS_ERR_UNSUPPORTED;
+        if (pl.jm == V10) hipLaunchKernelGGL((rollout_kernel<T, NX, NU, MODEL, V10, 1>), g, w, pl.smem, s, p);
+        else if (pl.jm == V11) hipLaunchKernelGGL((rollout_kernel<T, NX, NU, MODEL, V11, 1>), g, w, pl.smem, s, p);
+        else if (pl.jm == V12) hipLaunchKernelGGL((rollout_kernel<T, NX, NU, MODEL, V12, 1>), g, w, pl.smem, s, p);
+        else hipLaunchKernelGGL((rollout_kernel<T, NX, NU, MODEL, V13, 1>), g, w, pl.smem, s, p);
     }
     return check_launch();
 }
@@ -1047,5 +1092,68 @@ int launch_rollout_family_impl(RoP<T> &p, const isls_rollout_args &a, hipStream_
     {                                                                                                                                    \
         return launch_rollout_family_impl<float, NX_, NU_, MODEL_>(p, a, s, f, ok);                                                      \
     }
+#endif  // __HIPCC_RTC__
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Monte-Carlo closed loop of a dense causal controller about a nominal (iSLSBase.get_trajectory_sls,
+// isls/isls_base.py:28-42): one thread per initial state, the state history is the thread's own x_log row.
+// (Launched by rollout.hip for the built-in models and by user_model.hip for the run-time compiled ones.)
+// ---------------------------------------------------------------------------------------------------------------------
+template <typename T>
+struct DenseLoopP {
+    int M, N;
+    const T *par, *K, *k, *xhat, *uhat, *x0;
+    T *x_log, *u_log;
+};
+
+template <typename T, int NX, int NU, int MODEL>
+__global__ __launch_bounds__(64) void dense_closed_loop_kernel(DenseLoopP<T> p)
+{
+    extern __shared__ __align__(16) unsigned char dl_smem[];
+    Model<T, NX, NU, MODEL> mdl;
+    mdl.load(p.par, reinterpret_cast<T *>(dl_smem), threadIdx.x, 64);
+    __syncthreads();
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= p.M) return;
+    const int N = p.N;
+    T *xs = p.x_log + (int64_t)s * N * NX, *us = p.u_log + (int64_t)s * N * NU;
+    T x[NX], u[NU], xn[NX];
+#pragma unroll
+    for (int j = 0; j < NX; ++j) x[j] = p.x0[(int64_t)s * NX + j];
+    for (int i = 0; i < N; ++i) {
+#pragma unroll
+        for (int j = 0; j < NX; ++j) xs[i * NX + j] = x[j];
+#pragma unroll
+        for (int r = 0; r < NU; ++r) {
+            const T *Kr = p.K + (int64_t)(i * NU + r) * N * NX;
+            T acc = T(0);
+            for (int j = 0; j < (i + 1) * NX; ++j) acc += (xs[j] - (p.xhat ? p.xhat[j] : T(0))) * Kr[j];
+            u[r] = (acc + p.k[i * NU + r]) + (p.uhat ? p.uhat[i * NU + r] : T(0));
+            us[i * NU + r] = u[r];
+        }
+        mdl.step(x, u, xn);
+#pragma unroll
+        for (int j = 0; j < NX; ++j) x[j] = xn[j];
+    }
+}
+
+// arguments of user_linearize_kernel (user_model.hpp)
+template <typename T>
+struct UserLinP {
+    int B, N, nbt;                 // nbt: workgroups per trajectory
+    const T *par;
+    int64_t par_sb;
+    const T *xhat, *uhat;
+    T *A, *Bm;
+    const int32_t *active;
+};
+
+#ifndef __HIPCC_RTC__
+// the kernels of a user model (user_model.hip): the same plan, launched from the model's run-time compiled module
+template <typename T>
+int launch_rollout_user(RoP<T> &p, const isls_rollout_args &a, hipStream_t s, bool want_fused);
+template <typename T>
+int launch_dense_closed_loop_user(const DenseLoopP<T> &p, const isls_dense_loop_args &a, hipStream_t s);
+#endif
 
 }  // namespace isls

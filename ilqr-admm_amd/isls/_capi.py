@@ -18,10 +18,12 @@ except Exception:  # pragma: no cover
     torch = None
 
 ABI_VERSION = 107            # ISLS_VERSION of include/isls_hip.h these ctypes structs mirror
-OK, ERR_ARG, ERR_UNSUPPORTED, ERR_LAUNCH = 0, -1, -2, -3
+OK, ERR_ARG, ERR_UNSUPPORTED, ERR_LAUNCH, ERR_COMPILE = 0, -1, -2, -3, -4
 ST_NOT_PD, ST_NAN_COST, ST_LS_REJECT = 1, 2, 4
 SOLVE_CHOL, SOLVE_INV = 0, 1
 MODEL_LTI, MODEL_ARM3R, MODEL_CAR, MODEL_DI, MODEL_TASSA = 0, 1, 2, 3, 4
+MODEL_USER_BASE, USER_MAX_PAR = 1024, 16      # ids of user models (isls_user_model_create), parameters per model at most
+DTYPE_F64, DTYPE_F32 = 0, 1
 COST_VIA, COST_PHUBER = 0, 1
 RO_NAN_TO_1E5, RO_ACCEPT_TEST, RO_ABSOLUTE = 1, 2, 4
 PROJ_NONE, PROJ_BOX, PROJ_SETS = 0, 1, 2
@@ -195,9 +197,11 @@ class AdvanceArgs(C.Structure):
 # names every build of the library must export (checked by tests/test_capi_symbols.py)
 EXPORTED = [f"isls_{k}_{s}" for s in ("f64", "f32") for k in
             ("riccati_gain", "riccati_ff", "riccati_gain_ff", "riccati_ff_prepare", "rollout_ls", "admm_update", "project_rows", "sls_admm", "sls_closed_loop", "columns_rollout", "columns_admm", "dense_closed_loop", "sls_controller", "expand_quadratic", "linearize",
-             "accept_step", "reduce_convergence", "reduce_convergence_table", "ilqr_admm_outer", "outer_advance", "columns_iteration")] + \
+             "accept_step", "reduce_convergence", "reduce_convergence_table", "ilqr_admm_outer", "outer_advance", "columns_iteration",
+             "user_model_step")] + \
            ["isls_ff_segments", "isls_ff_record_elems", "isls_sls_controller_work_elems", "isls_version", "isls_dims_supported", "isls_dims_generic", "isls_error_string", "isls_timing_create",
-            "isls_timing_destroy", "isls_timing_reset", "isls_timing_pause", "isls_timing_read_ms"]
+            "isls_timing_destroy", "isls_timing_reset", "isls_timing_pause", "isls_timing_read_ms",
+            "isls_user_model_create", "isls_user_model_log", "isls_user_model_code", "isls_user_model_load"]
 
 
 SET_BOX, SET_SOC_UNIT, SET_SQUARE, SET_LINEAR, SET_QUADRATIC, SET_SHELL, SET_MULTILINEAR = 1, 2, 3, 4, 5, 6, 7
@@ -228,6 +232,11 @@ def load_hip_library(path=None):
     lib.isls_timing_pause.argtypes = [C.c_void_p, C.c_int]
     lib.isls_timing_read_ms.restype = C.c_double
     lib.isls_timing_read_ms.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    lib.isls_user_model_create.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
+    lib.isls_user_model_log.restype = C.c_int64
+    lib.isls_user_model_log.argtypes = [C.c_int32, C.c_char_p, C.c_int64]
+    lib.isls_user_model_code.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int64)]
+    lib.isls_user_model_load.argtypes = [C.c_int32, C.c_int32]
     return lib
 
 
@@ -255,6 +264,67 @@ def dims_generic(n, m):
 def supported_dims(n_max=16, m_max=8):
     """The (x_dim, u_dim) pairs the loaded library was built for."""
     return [(n, m) for n in range(1, n_max + 1) for m in range(1, m_max + 1) if dims_supported(n, m)]
+
+
+# ------------------------------------------------------------------------------------------------
+# user models: run-time compiled forward models (isls_user_model_*)
+# ------------------------------------------------------------------------------------------------
+_USER_LIB = None
+_USER_MODELS = {}            # (source, n, m, P) -> id: one compile per process
+
+
+def _user_lib():
+    global _USER_LIB
+    if _USER_LIB is None:
+        _USER_LIB = load_hip_library()
+    return _USER_LIB
+
+
+def user_model_log(model_id):
+    lib = _user_lib()
+    size = lib.isls_user_model_log(C.c_int32(model_id), None, 0)
+    buf = C.create_string_buffer(int(max(size, 0)) + 1)
+    lib.isls_user_model_log(C.c_int32(model_id), buf, len(buf))
+    return buf.value.decode(errors="replace")
+
+
+def user_model_create(source, n, m, n_par):
+    """Compile a user model for gfx950 (fp64 at once, fp32 on first use) and return its id; the same (source, n, m, n_par)
+    is compiled once per process.  IslsError carries the compile log."""
+    key = (str(source), int(n), int(m), int(n_par))
+    if key in _USER_MODELS:
+        return _USER_MODELS[key]
+    lib, mid = _user_lib(), C.c_int32(-1)
+    rc = lib.isls_user_model_create(key[0].encode(), key[1], key[2], key[3], C.byref(mid))
+    if rc == ERR_COMPILE:
+        raise IslsError(f"user model: compile failed\n{user_model_log(mid.value) if mid.value >= MODEL_USER_BASE else ''}")
+    if rc != OK:
+        raise IslsError(f"isls_user_model_create -> {rc}: {lib.isls_error_string(rc).decode()}")
+    _USER_MODELS[key] = mid.value
+    return mid.value
+
+
+def _dtype_code(dtype):
+    return DTYPE_F32 if dtype in (np.float32, "f32") or (torch is not None and dtype == torch.float32) else DTYPE_F64
+
+
+def user_model_code(model_id, dtype=np.float64):
+    """The model's gfx950 code object (a bare ELF) for dtype."""
+    lib, size = _user_lib(), C.c_int64(0)
+    rc = lib.isls_user_model_code(C.c_int32(model_id), _dtype_code(dtype), None, C.byref(size))
+    if rc == OK:
+        buf = C.create_string_buffer(size.value)
+        rc = lib.isls_user_model_code(C.c_int32(model_id), _dtype_code(dtype), buf, C.byref(size))
+    if rc != OK:
+        raise IslsError(f"isls_user_model_code -> {rc}\n{user_model_log(model_id)}")
+    return buf.raw
+
+
+def user_model_load(model_id, dtype=np.float64):
+    """Load the model's module onto the current device (outside any stream capture)."""
+    rc = _user_lib().isls_user_model_load(C.c_int32(model_id), _dtype_code(dtype))
+    if rc != OK:
+        raise IslsError(f"isls_user_model_load -> {rc}\n{user_model_log(model_id)}")
 
 
 # ------------------------------------------------------------------------------------------------
@@ -830,6 +900,19 @@ class Kernels:
         a.admm_active, a.iters, a.lx, a.lu, a.res_prev = _ptr(admm_active), _ptr(iters), _ptr(lx), _ptr(lu), _ptr(res_prev)
         a._keep = (accept, lin, exp)
         return a
+
+    def user_model_step(self, model_id, par, x, u, xn, stream=None):
+        """isls_user_model_step: xn [R,n] = f(x [R,n], u [R,m]) with par [P] (shared) or [R,P]."""
+        R, n = xn.shape
+        _dense(x, (R, n), "x"), _dense(u, (R, u.shape[1]), "u")
+        sb = 0 if par.ndim == 1 else int(_dense(par, (R, par.shape[1]), "par").shape[1])
+        fn = getattr(self.lib, f"{self.prefix}user_model_step_{_sfx(xn)}")
+        fn.restype = C.c_int
+        rc = fn(C.c_int32(model_id), C.c_int32(R), C.c_void_p(_ptr(par)), C.c_int64(sb), C.c_void_p(_ptr(x)), C.c_void_p(_ptr(u)),
+                C.c_void_p(_ptr(xn)), C.c_void_p(stream or 0))
+        if rc != OK:
+            raise IslsError(f"user_model_step -> {rc}")
+        return rc
 
     def outer_advance(self, adv, sfx, stream=None):
         return self._call("outer_advance", sfx, adv, stream)

@@ -179,8 +179,12 @@ class Engine:
         return torch.as_tensor(x, dtype=self.dtype, device=self.device).contiguous()
 
     def set_model(self, model_id, par):
-        """Built-in forward model (ISLS_MODEL_*); par is [P] (shared) or [B,P] (per trajectory)."""
+        """Built-in forward model (ISLS_MODEL_*) or a user model (models.Custom.model_id); par is [P] (shared) or [B,P] (per
+        trajectory)."""
         self.model, self.model_par = int(model_id), self._t(par)
+        if self.model >= capi.MODEL_USER_BASE:                # a user model: its module goes onto the device now, outside any capture
+            with torch.cuda.device(self.device):
+                capi.user_model_load(self.model, self.dtype)
         self._ab_stale()
 
     def set_quadratic_cost(self, zs, Qs, seq, u_std):

@@ -8,7 +8,8 @@
  *
  * Conventions
  *   - every pointer is a DEVICE pointer into caller-owned memory (torch tensors in our host code);
- *     the library allocates no device memory, keeps no global state, and is re-entrant per stream
+ *     the library allocates no device memory, keeps no global state (but the registry of user models,
+ *     isls_user_model_create), and is re-entrant per stream
  *     (the one process-wide input: experiment switches read from the environment once -- ISLS_*_TPW trajectories per
  *     wavefront, ISLS_GAIN_FF=0 / ISLS_FF_V2=0 / ISLS_COL_ROWS=0 select the previous form of a kernel; results do not
  *     depend on them beyond rounding);
@@ -42,6 +43,7 @@ extern "C" {
 #define ISLS_ERR_ARG (-1)
 #define ISLS_ERR_UNSUPPORTED (-2)
 #define ISLS_ERR_LAUNCH (-3)
+#define ISLS_ERR_COMPILE (-4)  /* isls_user_model_*: the run-time compile failed (log: isls_user_model_log) or hiprtc is absent */
 
 /* status[b] bits */
 #define ISLS_ST_NOT_PD 1     /* Quu not positive definite (reference: LinAlgError from dposv, isls/isls.py:296) */
@@ -65,6 +67,15 @@ extern "C" {
 #define ISLS_MODEL_TASSA 4  /* Tassa car-parking model, n=4 m=2 ; par = [dt, d]      (notebooks/Tutorial.ipynb cell 8):
                                f = dt v, b = f cos w + d - sqrt(d^2 - (f sin w)^2), x+ = x + b cos th, y+ = y + b sin th,
                                th+ = th + asin(f sin w / d), v+ = v + a dt ; state [x,y,th,v], control [w,a]              */
+
+/* User-written forward models (isls_user_model_create): ids >= ISLS_MODEL_USER_BASE name a registered user model.  The `model`
+ * fields of isls_rollout_args, isls_linearize_args (also inside isls_advance_args), isls_dense_loop_args and of the blocks that
+ * embed them take such an id like a built-in one; par = the model's n_par parameters ([n_par] shared, or per trajectory with
+ * model_par_sb = n_par).  Fast (n, m) pairs only (isls_dims_supported), cost model ISLS_COST_VIA; no model hint (lin_on). */
+#define ISLS_MODEL_USER_BASE 1024
+#define ISLS_USER_MAX_PAR 16        /* parameters of a user model, at most                                             */
+#define ISLS_DTYPE_F64 0
+#define ISLS_DTYPE_F32 1
 
 /* cost models of the line search and of the cost expansion */
 #define ISLS_COST_VIA 0     /* via-point quadratic (isls/sls_base.py:25-44): Qtab, ztab, seq, u_std                       */
@@ -685,7 +696,8 @@ int isls_ilqr_admm_outer_f32(const isls_outer_args *a, void *stream);
  *   1. `accept`  : isls_accept_step_* semantics (nominal <- x-step, cost log, the two stop rules -> outer_active);
  *   2. for the trajectories still iterating afterwards: admm_active <- 1, lambda <- 0, res_prev <- 1e6, iters <- 0 (the others:
  *      admm_active <- 0) -- the resets isls_ilqr_admm_outer_* starts with (pass begin_done = 1 there);
- *   3. `lin`     : isls_linearize_* about the new nominal   (lin.A == NULL: skipped; lin.active is ignored);
+ *   3. `lin`     : isls_linearize_* about the new nominal   (lin.A == NULL: skipped; lin.active is ignored; a user model's
+ *                  linearisation is a second launch on the same stream, behind the first);
  *   4. `exp`     : isls_expand_quadratic_* about it         (exp.c0x == NULL: skipped; exp.active is ignored).
  * Same results as the four calls in that order with active = accept.outer_active.  lin / exp normally name accept.xhat /
  * accept.uhat as their nominal.  admm_active, lx, lu, res_prev, iters are nullable.
@@ -702,6 +714,33 @@ typedef struct isls_advance_args {
 
 int isls_outer_advance_f64(const isls_advance_args *a, void *stream);
 int isls_outer_advance_f32(const isls_advance_args *a, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * User-written forward models, compiled at run time for gfx950 (hiprtc, dlopen-ed on the first create; nothing else in the
+ * library depends on it).  `source` defines
+ *     template <typename S, typename P> __device__ void step(const S *x, const S *u, const P *par, S *xn);
+ * in plain arithmetic on S (the contract: csrc/user_model_ad.hpp); no inline assembly, no __builtin_amdgcn_*.  It is
+ * compiled with S = T for the line search (the built-ins' rollout kernel template and launch plans), the closed loop and
+ * isls_user_model_step, and with S = a forward-mode dual number for isls_linearize_* (A_t, B_t without a get_AB).  The
+ * headers are read from the directory of libisls_hip.so.  The library keeps the registry of user models (process-wide, for
+ * the life of the process); it is the one piece of state it holds.
+ * ------------------------------------------------------------------------------------------- */
+/* Compiles `source` (fp64 now, fp32 on first use) and registers it: *id >= ISLS_MODEL_USER_BASE, also when the compile
+ * fails (ISLS_ERR_COMPILE; its log stays readable).  ISLS_ERR_UNSUPPORTED: (n, m) not a fast pair, n_par outside
+ * [0, ISLS_USER_MAX_PAR]; ISLS_ERR_ARG: a source with `asm` or `__builtin_amdgcn`.  Needs no GPU. */
+int isls_user_model_create(const char *source, int32_t n, int32_t m, int32_t n_par, int32_t *id);
+/* The compile log (NUL-terminated, truncated to len - 1 characters); returns its full length, or a negative ISLS_ERR_*. */
+int64_t isls_user_model_log(int32_t id, char *buf, int64_t len);
+/* The gfx950 code object of the model for dtype (ISLS_DTYPE_*): *len <- its size; copied to buf when buf != NULL and *len
+ * (on input) is large enough.  Compiles the dtype if it has not been yet. */
+int isls_user_model_code(int32_t id, int32_t dtype, void *buf, int64_t *len);
+/* Loads the model's module for dtype onto the current device (once; call it outside any stream capture). */
+int isls_user_model_load(int32_t id, int32_t dtype);
+/* xn[r] = f(x[r], u[r]) for R rows: x [R,n], u [R,m], par [n_par] (par_sb = 0) or [R,n_par] (par_sb = n_par) -> xn [R,n]. */
+int isls_user_model_step_f64(int32_t id, int32_t R, const void *par, int64_t par_sb, const void *x, const void *u, void *xn,
+                             void *stream);
+int isls_user_model_step_f32(int32_t id, int32_t R, const void *par, int64_t par_sb, const void *x, const void *u, void *xn,
+                             void *stream);
 
 int isls_version(void);
 /* 1 when the kernels are instantiated for state dimension n and control dimension m (the pairs are compile-time template
