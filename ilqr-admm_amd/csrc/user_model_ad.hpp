@@ -9,6 +9,11 @@
 //   comparisons    < <= > >= == != (on the value part: branches follow the nominal, as autograd does)
 //   functions      sin cos sqrt exp log tanh asin atan2 fabs, isls::sin_cos(a, s, c), isls::py_mod(a, b) (numpy's `%`)
 //   construction   S(1.5), S(0): a constant (zero derivative)
+// A plain number next to an S may be of any arithmetic type (`0.5 * x`, `isls::py_mod(x, 2)`, and for S = float
+// `isls::py_mod(x[0], x[1] * x[1] + 1.0)`, whose second argument is a double): it is converted to the scalar type of S.
+// sqrt at exactly 0: the derivative is 0 in every direction in which the argument's derivative is 0 (a constant, or a column of
+// the Jacobian the argument does not depend on) and +-inf in the others -- not the NaN of 0 * inf, which would poison the whole
+// Jacobian row.
 // Anything else (other math functions, integer casts of S, inline assembly) is outside the contract: a source that uses it
 // fails to compile for the dual type, and the compile error comes back to the caller with the log.
 #pragma once
@@ -140,8 +145,12 @@ __device__ __forceinline__ Dual<T, K> cos(const Dual<T, K> &a)
 template <typename T, int K>
 __device__ __forceinline__ Dual<T, K> sqrt(const Dual<T, K> &a)
 {
-    const T r = ::sqrt(a.v);
-    return chain(a, r, T(0.5) / r);
+    const T rt = ::sqrt(a.v), fp = T(0.5) / rt;
+    Dual<T, K> r;
+    r.v = rt;
+#pragma unroll
+    for (int k = 0; k < K; ++k) r.d[k] = a.d[k] == T(0) ? T(0) : fp * a.d[k];   // 0, not 0 * inf, at a.v = 0 (see the contract)
+    return r;
 }
 template <typename T, int K>
 __device__ __forceinline__ Dual<T, K> exp(const Dual<T, K> &a)
@@ -202,6 +211,23 @@ template <typename T, int K>
 __device__ __forceinline__ ad::Dual<T, K> py_mod(const ad::Dual<T, K> &a, typename ad::Dual<T, K>::scalar b)
 {
     return py_mod(a, ad::Dual<T, K>(b));
+}
+template <typename T, int K>
+__device__ __forceinline__ ad::Dual<T, K> py_mod(typename ad::Dual<T, K>::scalar a, const ad::Dual<T, K> &b)
+{
+    return py_mod(ad::Dual<T, K>(a), b);
+}
+// S = T with a plain number of another arithmetic type on either side (for S = float, `x + 1.0` is a double, and py_mod(float,
+// double) would be ambiguous between the two forms of isls_common.hpp): computed in float where one side is a float -- S is
+// float then -- and in double otherwise, as the dual forms above compute in the scalar type of S
+template <typename A, typename B,
+          typename = std::enable_if_t<std::is_arithmetic<A>::value && std::is_arithmetic<B>::value && !std::is_same<A, B>::value &&
+                                      (std::is_floating_point<A>::value || std::is_floating_point<B>::value)>>
+__device__ __forceinline__ std::conditional_t<std::is_same<A, float>::value || std::is_same<B, float>::value, float, double>
+py_mod(A a, B b)
+{
+    using R = std::conditional_t<std::is_same<A, float>::value || std::is_same<B, float>::value, float, double>;
+    return py_mod(R(a), R(b));
 }
 
 }  // namespace isls

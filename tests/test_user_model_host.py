@@ -1,6 +1,8 @@
 """User-written forward models (isls.models.Custom) on the CPU: they compile at run time for gfx950 without a GPU, their code
 objects hold every kernel the launches pick, their roll-out kernels need no more scratch than the built-in family of the same
-dimensions, and bad sources are refused with a clear error."""
+dimensions, and bad sources are refused with a clear error.  The contract zoo (user_models.ZOO: every operation the dual-number
+header offers, over the eight supported (n, m) pairs) compiles in both precisions, and its stored high-precision reference
+(tests/golden/g14_*.npz) is what its generator produces."""
 import ctypes
 import os
 import re
@@ -86,6 +88,54 @@ def test_arm_compiles_within_the_builtin_scratch(library_table):
     assert ks["_ZN4isls21user_linearize_kernelIdLi9ELi3EEEvNS_8UserLinPIT_EE"][".private_segment_fixed_size"] == 0
 
 
+@pytest.fixture(scope="module")
+def zoo():
+    made = {}
+
+    def get(name):
+        if name not in made:
+            n, m, src = um.ZOO[name][:3]
+            made[name] = models.Custom(n, m, np.zeros(um.NPAR[name]), src)
+        return made[name]
+    return get
+
+
+@pytest.mark.parametrize("name", sorted(um.ZOO))
+@pytest.mark.parametrize("dtype, T", [(np.float64, "d"), (np.float32, "f")])
+def test_zoo_compiles_in_both_precisions(zoo, name, dtype, T):
+    """Every form of the contract builds for S = T (line search, closed loop, step) and S = Dual<T, 1> (linearisation) in fp64
+    and fp32 -- for S = float a plain double next to an S (`x * x + 1.0` inside isls::py_mod or isls::sin_cos) is the case that
+    used to be ambiguous -- and the linearisation of every supported (n, m) pair keeps its dual numbers in registers."""
+    n, m = um.ZOO[name][:2]
+    ks = kernels_of(zoo(name).code(dtype))
+    lin = ks[f"_ZN4isls21user_linearize_kernelI{T}Li{n}ELi{m}EEEvNS_8UserLinPIT_EE"]
+    assert f"_ZN4isls16user_step_kernelI{T}Li{n}ELi{m}EEEviPKT_lS3_S3_PS1_" in ks
+    assert any(k.startswith(f"_ZN4isls24dense_closed_loop_kernelI{T}Li{n}ELi{m}ELi99E") for k in ks)
+    assert rollout_variants(ks, T, n, m, 99)
+    assert lin[".private_segment_fixed_size"] == 0 and lin.get(".vgpr_spill_count", 0) == 0, (name, lin)
+
+
+def test_zoo_covers_every_supported_pair():
+    assert sorted((v[0], v[1]) for v in um.ZOO.values()) == sorted(capi.supported_dims())
+
+
+def test_contract_fixture_is_what_the_generator_gives(golden):
+    """tests/golden/make_ad_contract.py, run again, reproduces every stored array bit for bit: points, parameter rows, 60-digit
+    values and central-difference Jacobians, the same-precision CPU baselines, and the sin_cos point set with its 200-bit
+    references."""
+    pytest.importorskip("mpmath")
+    import runpy
+    gen = runpy.run_path(os.path.join(ROOT, "tests", "golden", "make_ad_contract.py"))      # leaves no bytecode beside the fixtures
+    files = {"g14_ad_contract.npz": gen["contract_arrays"]()}
+    files.update({f"g14_sin_cos_{k}.npz": v for k, v in gen["sin_cos_arrays"]().items()})
+    for fname, arrs in files.items():
+        g = golden(fname)
+        assert sorted(g.files) == sorted(arrs), fname
+        for k, v in arrs.items():
+            assert g[k].dtype == np.asarray(v).dtype and np.array_equal(g[k], v, equal_nan=True), (fname, k)
+        assert os.path.getsize(os.path.join(ROOT, "tests", "golden", fname)) < 1 << 20
+
+
 def test_one_compile_per_source():
     a = models.Custom(4, 2, [0.1], um.CAR)
     b = models.Custom(4, 2, np.array([[0.1], [0.2]]), um.CAR)         # per-trajectory parameters: same program
@@ -101,6 +151,24 @@ def test_syntax_error_carries_the_log():
 def test_unknown_function_for_the_dual_type_is_a_compile_error():
     src = um.CAR.replace("isls::sin_cos(x[2], sn, cs);", "sn = erf(x[2]); cs = x[2];")
     with pytest.raises(capi.IslsError, match="compile failed"):
+        models.Custom(4, 2, [0.1], src)
+
+
+OUTSIDE = {"an integer cast of S": "int k = (int)x[2]; sn = x[2] * k; cs = x[2];",
+           "an S where an int is needed": "int k = x[2]; sn = x[2] * k; cs = x[2];",
+           "floor": "sn = floor(x[2]); cs = x[2];",
+           "pow": "sn = pow(x[2], 2.0); cs = x[2];",
+           "atan": "sn = atan(x[2]); cs = x[2];",
+           "fmod": "sn = fmod(x[2], 2.0); cs = x[2];"}
+
+
+@pytest.mark.parametrize("what", sorted(OUTSIDE))
+def test_outside_the_contract_is_a_compile_error_with_the_log(what):
+    """What the header names as outside the contract (integer casts of S, functions it does not list) compiles for S = T and
+    fails for the dual type: the error carries the compiler's log, which points into the user's source."""
+    src = um.CAR.replace("isls::sin_cos(x[2], sn, cs);", OUTSIDE[what])
+    assert src != um.CAR
+    with pytest.raises(capi.IslsError, match=r"compile failed\n(.|\n)*user_model:\d+:\d+: error:"):
         models.Custom(4, 2, [0.1], src)
 
 
