@@ -113,178 +113,54 @@ using namespace isls;
 
 #define ISLS_API extern "C" __attribute__((visibility("default")))
 
-#define DEFINE_ENTRY(name, args_t, launcher, kind)                                        \
-    ISLS_API int isls_##name##_f64(const args_t *a, void *stream)                          \
-    {                                                                                      \
-        if (!a) return ISLS_ERR_ARG;                                                       \
-        if (a->B == 0) return ISLS_OK; /* empty batch: nothing to check, nothing to do */  \
-        return launcher<double>(*a, (hipStream_t)stream);                                  \
-    }                                                                                      \
-    ISLS_API int isls_##name##_f32(const args_t *a, void *stream)                          \
-    {                                                                                      \
-        if (!a) return ISLS_ERR_ARG;                                                       \
-        if (a->B == 0) return ISLS_OK;                                                     \
-        return launcher<float>(*a, (hipStream_t)stream);                                   \
-    }
+// Both precisions of an entry point: the body sees T.
+#define ISLS_TYPED_PAIR(name, PARAMS, ...)                                   \
+    ISLS_API int isls_##name##_f64 PARAMS { using T = double; __VA_ARGS__ }  \
+    ISLS_API int isls_##name##_f32 PARAMS { using T = float; __VA_ARGS__ }
+// The pairs over one argument block.  EMPTY: the expression over `a` that means "empty batch: nothing to check, nothing to
+// do" (false: the launcher sees every call).
+#define ISLS_ENTRY(name, args_t, launcher, EMPTY)                            \
+    ISLS_TYPED_PAIR(name, (const args_t *a, void *stream),                   \
+                    if (!a) return ISLS_ERR_ARG;                             \
+                    if (EMPTY) return ISLS_OK;                               \
+                    return launcher<T>(*a, (hipStream_t)stream);)
 
-DEFINE_ENTRY(riccati_gain, isls_gain_args, launch_gain, 0)
-DEFINE_ENTRY(riccati_ff, isls_ff_args, launch_ff, 1)
-DEFINE_ENTRY(riccati_ff_prepare, isls_ff_prepare_args, launch_ff_prepare, 4)
-DEFINE_ENTRY(rollout_ls, isls_rollout_args, launch_rollout, 2)
-DEFINE_ENTRY(admm_update, isls_admm_args, launch_admm, 3)
+ISLS_ENTRY(riccati_gain, isls_gain_args, launch_gain, a->B == 0)
+ISLS_ENTRY(riccati_ff, isls_ff_args, launch_ff, a->B == 0)
+ISLS_ENTRY(riccati_ff_prepare, isls_ff_prepare_args, launch_ff_prepare, a->B == 0)
+ISLS_ENTRY(rollout_ls, isls_rollout_args, launch_rollout, a->B == 0)
+ISLS_ENTRY(admm_update, isls_admm_args, launch_admm, a->B == 0)
+ISLS_ENTRY(expand_quadratic, isls_expand_args, launch_expand, a->B == 0)
+ISLS_ENTRY(linearize, isls_linearize_args, launch_linearize, a->B == 0)
+ISLS_ENTRY(accept_step, isls_accept_args, launch_accept, a->B == 0)
+ISLS_ENTRY(project_rows, isls_project_args, launch_project, false)
+ISLS_ENTRY(sls_admm, isls_sls_admm_args, launch_sls_admm, false)
+ISLS_ENTRY(dense_closed_loop, isls_dense_loop_args, launch_dense_closed_loop, false)
+ISLS_ENTRY(sls_controller, isls_sls_controller_args, launch_sls_controller, false)
+ISLS_ENTRY(columns_rollout, isls_columns_args, launch_columns_rollout, false)
+ISLS_ENTRY(columns_admm, isls_columns_admm_args, launch_columns_admm, false)
+ISLS_ENTRY(columns_iteration, isls_columns_iteration_args, launch_columns_iteration, false)
+ISLS_ENTRY(outer_advance, isls_advance_args, launch_advance, false)
+ISLS_ENTRY(ilqr_admm_outer, isls_outer_args, outer_iteration, false)
 
-ISLS_API int isls_riccati_gain_ff_f64(const isls_gain_args *g, const isls_ff_args *ff, void *stream)
-{
-    if (!g || !ff) return ISLS_ERR_ARG;
-    if (g->B == 0) return ISLS_OK;
-    bool done = false;
-    const int rc = launch_gain<double>(*g, (hipStream_t)stream, ff, &done, /*require_ff=*/true);
-    return rc != ISLS_OK ? rc : (done ? ISLS_OK : ISLS_ERR_UNSUPPORTED);
-}
-ISLS_API int isls_riccati_gain_ff_f32(const isls_gain_args *g, const isls_ff_args *ff, void *stream)
-{
-    if (!g || !ff) return ISLS_ERR_ARG;
-    if (g->B == 0) return ISLS_OK;
-    bool done = false;
-    const int rc = launch_gain<float>(*g, (hipStream_t)stream, ff, &done, /*require_ff=*/true);
-    return rc != ISLS_OK ? rc : (done ? ISLS_OK : ISLS_ERR_UNSUPPORTED);
-}
+ISLS_TYPED_PAIR(riccati_gain_ff, (const isls_gain_args *g, const isls_ff_args *ff, void *stream),
+                if (!g || !ff) return ISLS_ERR_ARG;
+                if (g->B == 0) return ISLS_OK;
+                bool done = false;
+                const int rc = launch_gain<T>(*g, (hipStream_t)stream, ff, &done, /*require_ff=*/true);
+                return rc != ISLS_OK ? rc : (done ? ISLS_OK : ISLS_ERR_UNSUPPORTED);)
+ISLS_TYPED_PAIR(sls_closed_loop, (int32_t M, int32_t N, int32_t n, int32_t m, const void *A, const void *B, const void *K, const void *k,
+                                  const void *x0, void *x_log, void *u_log, void *stream),
+                return launch_sls_closed_loop<T>(M, N, n, m, A, B, K, k, x0, x_log, u_log, (hipStream_t)stream);)
+ISLS_TYPED_PAIR(reduce_convergence, (int32_t B, const void *cost, const void *res, const int32_t *active, const int32_t *status,
+                                     void *out5, void *stream),
+                return launch_reduce<T>(B, cost, res, active, status, out5, (hipStream_t)stream);)
+ISLS_TYPED_PAIR(reduce_convergence_table, (int32_t B, const void *cost, const void *res, const int32_t *active, const int32_t *status,
+                                           void *table, int32_t rank, int32_t world, void *stream),
+                if (rank < 0) return ISLS_ERR_ARG;
+                return launch_reduce<T>(B, cost, res, active, status, table, (hipStream_t)stream, rank, world);)
 
-ISLS_API int isls_expand_quadratic_f64(const isls_expand_args *a, void *stream)
-{
-    if (a && a->B == 0) return ISLS_OK;
-    return a ? launch_expand<double>(*a, (hipStream_t)stream) : ISLS_ERR_ARG;
-}
-ISLS_API int isls_expand_quadratic_f32(const isls_expand_args *a, void *stream)
-{
-    if (a && a->B == 0) return ISLS_OK;
-    return a ? launch_expand<float>(*a, (hipStream_t)stream) : ISLS_ERR_ARG;
-}
-ISLS_API int isls_linearize_f64(const isls_linearize_args *a, void *stream)
-{
-    if (a && a->B == 0) return ISLS_OK;
-    return a ? launch_linearize<double>(*a, (hipStream_t)stream) : ISLS_ERR_ARG;
-}
-ISLS_API int isls_linearize_f32(const isls_linearize_args *a, void *stream)
-{
-    if (a && a->B == 0) return ISLS_OK;
-    return a ? launch_linearize<float>(*a, (hipStream_t)stream) : ISLS_ERR_ARG;
-}
-ISLS_API int isls_project_rows_f64(const isls_project_args *a, void *stream)
-{
-    return a ? launch_project<double>(*a, (hipStream_t)stream) : ISLS_ERR_ARG;
-}
-ISLS_API int isls_project_rows_f32(const isls_project_args *a, void *stream)
-{
-    return a ? launch_project<float>(*a, (hipStream_t)stream) : ISLS_ERR_ARG;
-}
-ISLS_API int isls_sls_admm_f64(const isls_sls_admm_args *a, void *stream)
-{
-    return a ? launch_sls_admm<double>(*a, (hipStream_t)stream) : ISLS_ERR_ARG;
-}
-ISLS_API int isls_sls_admm_f32(const isls_sls_admm_args *a, void *stream)
-{
-    return a ? launch_sls_admm<float>(*a, (hipStream_t)stream) : ISLS_ERR_ARG;
-}
-ISLS_API int isls_sls_closed_loop_f64(int32_t M, int32_t N, int32_t n, int32_t m, const void *A, const void *B, const void *K,
-                                      const void *k, const void *x0, void *x_log, void *u_log, void *stream)
-{
-    return launch_sls_closed_loop<double>(M, N, n, m, A, B, K, k, x0, x_log, u_log, (hipStream_t)stream);
-}
-ISLS_API int isls_sls_closed_loop_f32(int32_t M, int32_t N, int32_t n, int32_t m, const void *A, const void *B, const void *K,
-                                      const void *k, const void *x0, void *x_log, void *u_log, void *stream)
-{
-    return launch_sls_closed_loop<float>(M, N, n, m, A, B, K, k, x0, x_log, u_log, (hipStream_t)stream);
-}
-ISLS_API int isls_dense_closed_loop_f64(const isls_dense_loop_args *a, void *stream)
-{
-    return a ? launch_dense_closed_loop<double>(*a, (hipStream_t)stream) : ISLS_ERR_ARG;
-}
-ISLS_API int isls_dense_closed_loop_f32(const isls_dense_loop_args *a, void *stream)
-{
-    return a ? launch_dense_closed_loop<float>(*a, (hipStream_t)stream) : ISLS_ERR_ARG;
-}
-ISLS_API int isls_sls_controller_f64(const isls_sls_controller_args *a, void *stream)
-{
-    return a ? launch_sls_controller<double>(*a, (hipStream_t)stream) : ISLS_ERR_ARG;
-}
-ISLS_API int isls_sls_controller_f32(const isls_sls_controller_args *a, void *stream)
-{
-    return a ? launch_sls_controller<float>(*a, (hipStream_t)stream) : ISLS_ERR_ARG;
-}
 ISLS_API int64_t isls_sls_controller_work_elems(int32_t B, int32_t N, int32_t n) { return sls_controller_work_elems(B, N, n); }
-ISLS_API int isls_columns_rollout_f64(const isls_columns_args *a, void *stream)
-{
-    return a ? launch_columns_rollout<double>(*a, (hipStream_t)stream) : ISLS_ERR_ARG;
-}
-ISLS_API int isls_columns_rollout_f32(const isls_columns_args *a, void *stream)
-{
-    return a ? launch_columns_rollout<float>(*a, (hipStream_t)stream) : ISLS_ERR_ARG;
-}
-ISLS_API int isls_columns_admm_f64(const isls_columns_admm_args *a, void *stream)
-{
-    return a ? launch_columns_admm<double>(*a, (hipStream_t)stream) : ISLS_ERR_ARG;
-}
-ISLS_API int isls_columns_admm_f32(const isls_columns_admm_args *a, void *stream)
-{
-    return a ? launch_columns_admm<float>(*a, (hipStream_t)stream) : ISLS_ERR_ARG;
-}
-ISLS_API int isls_columns_iteration_f64(const isls_columns_iteration_args *a, void *stream)
-{
-    return a ? launch_columns_iteration<double>(*a, (hipStream_t)stream) : ISLS_ERR_ARG;
-}
-ISLS_API int isls_columns_iteration_f32(const isls_columns_iteration_args *a, void *stream)
-{
-    return a ? launch_columns_iteration<float>(*a, (hipStream_t)stream) : ISLS_ERR_ARG;
-}
-ISLS_API int isls_accept_step_f64(const isls_accept_args *a, void *stream)
-{
-    if (a && a->B == 0) return ISLS_OK;
-    return a ? launch_accept<double>(*a, (hipStream_t)stream) : ISLS_ERR_ARG;
-}
-ISLS_API int isls_accept_step_f32(const isls_accept_args *a, void *stream)
-{
-    if (a && a->B == 0) return ISLS_OK;
-    return a ? launch_accept<float>(*a, (hipStream_t)stream) : ISLS_ERR_ARG;
-}
-ISLS_API int isls_outer_advance_f64(const isls_advance_args *a, void *stream)
-{
-    return a ? launch_advance<double>(*a, (hipStream_t)stream) : ISLS_ERR_ARG;
-}
-ISLS_API int isls_outer_advance_f32(const isls_advance_args *a, void *stream)
-{
-    return a ? launch_advance<float>(*a, (hipStream_t)stream) : ISLS_ERR_ARG;
-}
-ISLS_API int isls_reduce_convergence_f64(int32_t B, const void *cost, const void *res, const int32_t *active,
-                                         const int32_t *status, void *out5, void *stream)
-{
-    return launch_reduce<double>(B, cost, res, active, status, out5, (hipStream_t)stream);
-}
-ISLS_API int isls_reduce_convergence_f32(int32_t B, const void *cost, const void *res, const int32_t *active,
-                                         const int32_t *status, void *out5, void *stream)
-{
-    return launch_reduce<float>(B, cost, res, active, status, out5, (hipStream_t)stream);
-}
-ISLS_API int isls_reduce_convergence_table_f64(int32_t B, const void *cost, const void *res, const int32_t *active,
-                                               const int32_t *status, void *table, int32_t rank, int32_t world, void *stream)
-{
-    if (rank < 0) return ISLS_ERR_ARG;
-    return launch_reduce<double>(B, cost, res, active, status, table, (hipStream_t)stream, rank, world);
-}
-ISLS_API int isls_reduce_convergence_table_f32(int32_t B, const void *cost, const void *res, const int32_t *active,
-                                               const int32_t *status, void *table, int32_t rank, int32_t world, void *stream)
-{
-    if (rank < 0) return ISLS_ERR_ARG;
-    return launch_reduce<float>(B, cost, res, active, status, table, (hipStream_t)stream, rank, world);
-}
-ISLS_API int isls_ilqr_admm_outer_f64(const isls_outer_args *a, void *stream)
-{
-    return a ? outer_iteration<double>(*a, (hipStream_t)stream) : ISLS_ERR_ARG;
-}
-ISLS_API int isls_ilqr_admm_outer_f32(const isls_outer_args *a, void *stream)
-{
-    return a ? outer_iteration<float>(*a, (hipStream_t)stream) : ISLS_ERR_ARG;
-}
 
 ISLS_API int32_t isls_ff_segments(int32_t N, int32_t nseg_requested, int32_t *seg_len)
 {

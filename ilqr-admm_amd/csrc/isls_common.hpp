@@ -278,22 +278,19 @@ inline int check_launch()
 }
 #endif
 
-// Supported (n, m) pairs: the reference notebooks' systems and every get_double_integrator_AB(nb_dim <= 3,
-// nb_deriv <= 3) system (isls/utils.py:266-276: n = nb_dim * nb_deriv, m = nb_dim).  The kernels are templates over the
-// dimensions (rows live in registers); a further pair is one line here, one in rollout.hip and one in the Makefile.
-#define ISLS_FOR_EACH_DIMS(X) X(6, 3) X(2, 1) X(4, 2) X(9, 3) X(3, 1) X(6, 2) X(2, 2) X(3, 3)
-#define ISLS_DISPATCH_DIMS(n, m, CALL)                  \
-    {                                                   \
-        const int n_ = (n), m_ = (m);                   \
-        if (n_ == 6 && m_ == 3) { CALL(6, 3); }         \
-        else if (n_ == 2 && m_ == 1) { CALL(2, 1); }    \
-        else if (n_ == 4 && m_ == 2) { CALL(4, 2); }    \
-        else if (n_ == 9 && m_ == 3) { CALL(9, 3); }    \
-        else if (n_ == 3 && m_ == 1) { CALL(3, 1); }    \
-        else if (n_ == 6 && m_ == 2) { CALL(6, 2); }    \
-        else if (n_ == 2 && m_ == 2) { CALL(2, 2); }    \
-        else if (n_ == 3 && m_ == 3) { CALL(3, 3); }    \
-        else return ISLS_ERR_UNSUPPORTED;               \
+// Supported (n, m) pairs and (n, m, model) families: families.def lists them, everything here, in rollout.hip and in the
+// Makefile is derived from it.  The kernels are templates over the dimensions (rows live in registers); a further pair is one
+// line in each list of families.def (rollout.hip checks that every pair has its ISLS_MODEL_LTI family), plus a Model<>
+// specialisation (rollout_kernel.hpp) for a family that is not LTI.
+#include "families.def"
+#define ISLS_DIMS_APPLY_(NX_, NU_, X) X(NX_, NU_)
+#define ISLS_FOR_EACH_DIMS(X) ISLS_FOR_EACH_DIMS_ARG(ISLS_DIMS_APPLY_, X)
+#define ISLS_DISPATCH_CASE_(NX_, NU_, CALL) if (n_ == NX_ && m_ == NU_) { CALL(NX_, NU_); } else
+#define ISLS_DISPATCH_DIMS(n, m, CALL)                                  \
+    {                                                                   \
+        const int n_ = (n), m_ = (m);                                   \
+        ISLS_FOR_EACH_DIMS_ARG(ISLS_DISPATCH_CASE_, CALL)               \
+        return ISLS_ERR_UNSUPPORTED;                                    \
     }
 // template id of the run-time compiled user models (user_model.hpp): their kernels show up as rollout_kernel<T, n, m, 99, JM, OCC>
 constexpr int ISLS_MODEL_USER = 99;
@@ -303,7 +300,7 @@ constexpr int ISLS_MODEL_USER = 99;
 inline bool is_user_model(int model) { return model >= ISLS_MODEL_USER_BASE; }
 template <typename T> int launch_linearize_user(const isls_linearize_args &a, hipStream_t s);
 #endif
-inline bool dims_supported(int n, int m)
+constexpr bool dims_supported(int n, int m)
 {
 #define ISLS_DIMS_TEST_(NX_, NU_) if (n == NX_ && m == NU_) return true;
     ISLS_FOR_EACH_DIMS(ISLS_DIMS_TEST_)

@@ -1,24 +1,31 @@
 // rollout.hip -- dispatcher of the line-search rollout (kernel template: rollout_kernel.hpp; one translation unit per
-// (n, m, model) family: rollout_family.hip compiled with -DISLS_FAM_*), plus the Monte-Carlo closed loop of a dense controller
+// (n, m, model) family of families.def: rollout_family.hip compiled with -DISLS_FAM_*), plus the Monte-Carlo closed loop of a dense controller
 // (kernel: rollout_kernel.hpp).  User models (ids >= ISLS_MODEL_USER_BASE) go to user_model.hip.
 #include "rollout_kernel.hpp"
 
 namespace isls {
 
-ISLS_ROLLOUT_FAMILY_DECL(4, 2, ISLS_MODEL_LTI)
-ISLS_ROLLOUT_FAMILY_DECL(4, 2, ISLS_MODEL_CAR)
-ISLS_ROLLOUT_FAMILY_DECL(4, 2, ISLS_MODEL_DI)
-ISLS_ROLLOUT_FAMILY_DECL(4, 2, ISLS_MODEL_TASSA)
-ISLS_ROLLOUT_FAMILY_DECL(9, 3, ISLS_MODEL_LTI)
-ISLS_ROLLOUT_FAMILY_DECL(9, 3, ISLS_MODEL_ARM3R)
-ISLS_ROLLOUT_FAMILY_DECL(6, 3, ISLS_MODEL_LTI)
-ISLS_ROLLOUT_FAMILY_DECL(6, 3, ISLS_MODEL_DI)
-ISLS_ROLLOUT_FAMILY_DECL(2, 1, ISLS_MODEL_LTI)
-ISLS_ROLLOUT_FAMILY_DECL(2, 1, ISLS_MODEL_DI)
-ISLS_ROLLOUT_FAMILY_DECL(3, 1, ISLS_MODEL_LTI)
-ISLS_ROLLOUT_FAMILY_DECL(6, 2, ISLS_MODEL_LTI)
-ISLS_ROLLOUT_FAMILY_DECL(2, 2, ISLS_MODEL_LTI)
-ISLS_ROLLOUT_FAMILY_DECL(3, 3, ISLS_MODEL_LTI)
+ISLS_FOR_EACH_FAMILY(ISLS_ROLLOUT_FAMILY_DECL)
+
+constexpr bool family_listed(int n, int m, int model)
+{
+#define ISLS_FAMILY_TEST_(NX_, NU_, MODEL_) if (n == NX_ && m == NU_ && model == MODEL_) return true;
+    ISLS_FOR_EACH_FAMILY(ISLS_FAMILY_TEST_)
+#undef ISLS_FAMILY_TEST_
+    return false;
+}
+// families.def: the rollout of a pair dispatches over its families, and every pair the other kernels serve has its LTI rollout
+constexpr bool family_table_consistent()
+{
+#define ISLS_FAMILY_PAIR_(NX_, NU_, MODEL_) if (!dims_supported(NX_, NU_)) return false;
+    ISLS_FOR_EACH_FAMILY(ISLS_FAMILY_PAIR_)
+#undef ISLS_FAMILY_PAIR_
+#define ISLS_PAIR_LTI_(NX_, NU_) if (!family_listed(NX_, NU_, ISLS_MODEL_LTI)) return false;
+    ISLS_FOR_EACH_DIMS(ISLS_PAIR_LTI_)
+#undef ISLS_PAIR_LTI_
+    return true;
+}
+static_assert(family_table_consistent(), "families.def: a family's (n, m) is not in the pair list, or a pair has no ISLS_MODEL_LTI family");
 
 template <typename T>
 int launch_rollout(const isls_rollout_args &a, hipStream_t s, const isls_admm_args *fused, bool *did_fuse, bool last)
@@ -73,20 +80,7 @@ int launch_rollout(const isls_rollout_args &a, hipStream_t s, const isls_admm_ar
     }
 #define FAMILY(NX_, NU_, MODEL_) \
     if (a.n == NX_ && a.m == NU_ && a.model == MODEL_) rc = launch_rollout_family<T, NX_, NU_, MODEL_>(p, a, s, fused != nullptr, nullptr);
-    FAMILY(4, 2, ISLS_MODEL_LTI)
-    FAMILY(4, 2, ISLS_MODEL_CAR)
-    FAMILY(4, 2, ISLS_MODEL_DI)
-    FAMILY(4, 2, ISLS_MODEL_TASSA)
-    FAMILY(9, 3, ISLS_MODEL_LTI)
-    FAMILY(9, 3, ISLS_MODEL_ARM3R)
-    FAMILY(6, 3, ISLS_MODEL_LTI)
-    FAMILY(6, 3, ISLS_MODEL_DI)
-    FAMILY(2, 1, ISLS_MODEL_LTI)
-    FAMILY(2, 1, ISLS_MODEL_DI)
-    FAMILY(3, 1, ISLS_MODEL_LTI)
-    FAMILY(6, 2, ISLS_MODEL_LTI)
-    FAMILY(2, 2, ISLS_MODEL_LTI)
-    FAMILY(3, 3, ISLS_MODEL_LTI)
+    ISLS_FOR_EACH_FAMILY(FAMILY)
 #undef FAMILY
     if (did_fuse) *did_fuse = rc == ISLS_OK && p.fa_on != 0;   // the family launcher drops the fused update when the stage does not fit
     return rc;
@@ -106,26 +100,15 @@ int launch_dense_closed_loop(const isls_dense_loop_args &a, hipStream_t s)
     p.x_log = (T *)a.x_log; p.u_log = (T *)a.u_log;
     if (is_user_model(a.model)) return launch_dense_closed_loop_user<T>(p, a, s);
     const int grid = (a.M + 63) / 64;
-#define LAUNCH(NX_, NU_, MODEL_)                                                                                          \
-    hipLaunchKernelGGL((dense_closed_loop_kernel<T, NX_, NU_, MODEL_>), dim3(grid), dim3(64),                              \
-                       sizeof(T) * (Model<T, NX_, NU_, MODEL_>::LDS_WORDS + 1), s, p)
-    if (a.n == 4 && a.m == 2 && a.model == ISLS_MODEL_LTI) LAUNCH(4, 2, ISLS_MODEL_LTI);
-    else if (a.n == 4 && a.m == 2 && a.model == ISLS_MODEL_CAR) LAUNCH(4, 2, ISLS_MODEL_CAR);
-    else if (a.n == 9 && a.m == 3 && a.model == ISLS_MODEL_LTI) LAUNCH(9, 3, ISLS_MODEL_LTI);
-    else if (a.n == 9 && a.m == 3 && a.model == ISLS_MODEL_ARM3R) LAUNCH(9, 3, ISLS_MODEL_ARM3R);
-    else if (a.n == 6 && a.m == 3 && a.model == ISLS_MODEL_LTI) LAUNCH(6, 3, ISLS_MODEL_LTI);
-    else if (a.n == 2 && a.m == 1 && a.model == ISLS_MODEL_LTI) LAUNCH(2, 1, ISLS_MODEL_LTI);
-    else if (a.n == 6 && a.m == 3 && a.model == ISLS_MODEL_DI) LAUNCH(6, 3, ISLS_MODEL_DI);
-    else if (a.n == 4 && a.m == 2 && a.model == ISLS_MODEL_DI) LAUNCH(4, 2, ISLS_MODEL_DI);
-    else if (a.n == 2 && a.m == 1 && a.model == ISLS_MODEL_DI) LAUNCH(2, 1, ISLS_MODEL_DI);
-    else if (a.n == 4 && a.m == 2 && a.model == ISLS_MODEL_TASSA) LAUNCH(4, 2, ISLS_MODEL_TASSA);
-    else if (a.n == 3 && a.m == 1 && a.model == ISLS_MODEL_LTI) LAUNCH(3, 1, ISLS_MODEL_LTI);
-    else if (a.n == 6 && a.m == 2 && a.model == ISLS_MODEL_LTI) LAUNCH(6, 2, ISLS_MODEL_LTI);
-    else if (a.n == 2 && a.m == 2 && a.model == ISLS_MODEL_LTI) LAUNCH(2, 2, ISLS_MODEL_LTI);
-    else if (a.n == 3 && a.m == 3 && a.model == ISLS_MODEL_LTI) LAUNCH(3, 3, ISLS_MODEL_LTI);
-    else return ISLS_ERR_UNSUPPORTED;
-#undef LAUNCH
-    return check_launch();
+#define FAMILY(NX_, NU_, MODEL_)                                                                                          \
+    if (a.n == NX_ && a.m == NU_ && a.model == MODEL_) {                                                                  \
+        hipLaunchKernelGGL((dense_closed_loop_kernel<T, NX_, NU_, MODEL_>), dim3(grid), dim3(64),                          \
+                           sizeof(T) * (Model<T, NX_, NU_, MODEL_>::LDS_WORDS + 1), s, p);                                 \
+        return check_launch();                                                                                            \
+    }
+    ISLS_FOR_EACH_FAMILY(FAMILY)
+#undef FAMILY
+    return ISLS_ERR_UNSUPPORTED;
 }
 template int launch_dense_closed_loop<double>(const isls_dense_loop_args &, hipStream_t);
 template int launch_dense_closed_loop<float>(const isls_dense_loop_args &, hipStream_t);

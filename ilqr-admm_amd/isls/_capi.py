@@ -194,7 +194,7 @@ class AdvanceArgs(C.Structure):
                 ("admm_active", C.c_void_p), ("iters", C.c_void_p), ("lx", C.c_void_p), ("lu", C.c_void_p), ("res_prev", C.c_void_p)]
 
 
-# names every build of the library must export (checked by tests/test_capi_symbols.py)
+# names every build of the library must export (checked by tests/test_capi_host.py)
 EXPORTED = [f"isls_{k}_{s}" for s in ("f64", "f32") for k in
             ("riccati_gain", "riccati_ff", "riccati_gain_ff", "riccati_ff_prepare", "rollout_ls", "admm_update", "project_rows", "sls_admm", "sls_closed_loop", "columns_rollout", "columns_admm", "dense_closed_loop", "sls_controller", "expand_quadratic", "linearize",
              "accept_step", "reduce_convergence", "reduce_convergence_table", "ilqr_admm_outer", "outer_advance", "columns_iteration",
@@ -214,7 +214,8 @@ class IslsError(RuntimeError):
 
 
 def load_hip_library(path=None):
-    """dlopen the HIP library; fail loudly (no CPU fallback exists by design)."""
+    """dlopen the HIP library and declare its functions that are not typed f64 / f32 pairs; fail loudly (no CPU fallback
+    exists by design).  A handle of its own per call: library() is the process-wide one."""
     path = path or os.environ.get("ISLS_HIP_LIB") or HIP_LIB_PATH       # env override: A/B builds when tuning
     if not os.path.exists(path):
         raise IslsError(f"{path} not found: build it with `python __graft_entry__.py` "
@@ -224,7 +225,15 @@ def load_hip_library(path=None):
     if lib.isls_version() != ABI_VERSION:                      # a stale build would read the argument blocks with another layout
         raise IslsError(f"{path} reports ABI version {lib.isls_version()}, this binding is for {ABI_VERSION}: rebuild it "
                         f"(`python __graft_entry__.py`)")
+    i32 = C.c_int32
     lib.isls_error_string.restype = C.c_char_p
+    lib.isls_dims_supported.restype = lib.isls_dims_generic.restype = i32
+    lib.isls_dims_supported.argtypes = lib.isls_dims_generic.argtypes = [i32, i32]
+    lib.isls_ff_segments.restype = i32
+    lib.isls_ff_segments.argtypes = [i32, i32, C.POINTER(i32)]
+    lib.isls_ff_record_elems.restype = lib.isls_sls_controller_work_elems.restype = C.c_int64
+    lib.isls_ff_record_elems.argtypes = [i32, i32, i32, i32]
+    lib.isls_sls_controller_work_elems.argtypes = [i32, i32, i32]
     lib.isls_timing_create.restype = C.c_void_p
     lib.isls_timing_destroy.restype = None
     lib.isls_timing_destroy.argtypes = [C.c_void_p]
@@ -240,25 +249,25 @@ def load_hip_library(path=None):
     return lib
 
 
-_DIMS_LIB = None
+_LIB = None
+
+
+def library():
+    """The process-wide handle of the HIP library (ISLS_HIP_LIB, else csrc/libisls_hip.so), loaded on first use."""
+    global _LIB
+    if _LIB is None:
+        _LIB = load_hip_library()
+    return _LIB
 
 
 def dims_supported(n, m):
     """True when the HIP library carries kernels for state dimension n and control dimension m (isls_dims_supported)."""
-    global _DIMS_LIB
-    if _DIMS_LIB is None:
-        _DIMS_LIB = load_hip_library()
-        _DIMS_LIB.isls_dims_supported.restype = C.c_int32
-    return bool(_DIMS_LIB.isls_dims_supported(C.c_int32(int(n)), C.c_int32(int(m))))
+    return bool(library().isls_dims_supported(int(n), int(m)))
 
 
 def dims_generic(n, m):
     """True when (n, m) is served at all: by the templated kernels or by the generic ones of csrc/generic.hip (n <= 16, m <= 8)."""
-    global _DIMS_LIB
-    if _DIMS_LIB is None:
-        _DIMS_LIB = load_hip_library()
-    _DIMS_LIB.isls_dims_generic.restype = C.c_int32
-    return bool(_DIMS_LIB.isls_dims_generic(C.c_int32(int(n)), C.c_int32(int(m))))
+    return bool(library().isls_dims_generic(int(n), int(m)))
 
 
 def supported_dims(n_max=16, m_max=8):
@@ -269,19 +278,11 @@ def supported_dims(n_max=16, m_max=8):
 # ------------------------------------------------------------------------------------------------
 # user models: run-time compiled forward models (isls_user_model_*)
 # ------------------------------------------------------------------------------------------------
-_USER_LIB = None
 _USER_MODELS = {}            # (source, n, m, P) -> id: one compile per process
 
 
-def _user_lib():
-    global _USER_LIB
-    if _USER_LIB is None:
-        _USER_LIB = load_hip_library()
-    return _USER_LIB
-
-
 def user_model_log(model_id):
-    lib = _user_lib()
+    lib = library()
     size = lib.isls_user_model_log(C.c_int32(model_id), None, 0)
     buf = C.create_string_buffer(int(max(size, 0)) + 1)
     lib.isls_user_model_log(C.c_int32(model_id), buf, len(buf))
@@ -294,7 +295,7 @@ def user_model_create(source, n, m, n_par):
     key = (str(source), int(n), int(m), int(n_par))
     if key in _USER_MODELS:
         return _USER_MODELS[key]
-    lib, mid = _user_lib(), C.c_int32(-1)
+    lib, mid = library(), C.c_int32(-1)
     rc = lib.isls_user_model_create(key[0].encode(), key[1], key[2], key[3], C.byref(mid))
     if rc == ERR_COMPILE:
         raise IslsError(f"user model: compile failed\n{user_model_log(mid.value) if mid.value >= MODEL_USER_BASE else ''}")
@@ -310,7 +311,7 @@ def _dtype_code(dtype):
 
 def user_model_code(model_id, dtype=np.float64):
     """The model's gfx950 code object (a bare ELF) for dtype."""
-    lib, size = _user_lib(), C.c_int64(0)
+    lib, size = library(), C.c_int64(0)
     rc = lib.isls_user_model_code(C.c_int32(model_id), _dtype_code(dtype), None, C.byref(size))
     if rc == OK:
         buf = C.create_string_buffer(size.value)
@@ -322,7 +323,7 @@ def user_model_code(model_id, dtype=np.float64):
 
 def user_model_load(model_id, dtype=np.float64):
     """Load the model's module onto the current device (outside any stream capture)."""
-    rc = _user_lib().isls_user_model_load(C.c_int32(model_id), _dtype_code(dtype))
+    rc = library().isls_user_model_load(C.c_int32(model_id), _dtype_code(dtype))
     if rc != OK:
         raise IslsError(f"isls_user_model_load -> {rc}\n{user_model_log(model_id)}")
 
@@ -357,14 +358,17 @@ def _sfx(x):
     raise TypeError(f"unsupported dtype {dt}")
 
 
+def _contiguous(x):
+    return x.is_contiguous() if _is_torch(x) else x.flags["C_CONTIGUOUS"]
+
+
 def _dense(x, shape, name):
     """Check a dense C-contiguous operand of exactly `shape`."""
     if x is None:
         return None
     if tuple(x.shape) != tuple(shape):
         raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(x.shape)}")
-    contiguous = x.is_contiguous() if _is_torch(x) else x.flags["C_CONTIGUOUS"]
-    if not contiguous:
+    if not _contiguous(x):
         raise ValueError(f"{name}: must be C-contiguous")
     return x
 
@@ -385,8 +389,7 @@ def _record(rec, B, N, n, m):
     if rec is None:
         return None
     size = rec.numel() if _is_torch(rec) else rec.size
-    contiguous = rec.is_contiguous() if _is_torch(rec) else rec.flags["C_CONTIGUOUS"]
-    if size < ff_record_elems(B, N, n, m) or not contiguous:
+    if size < ff_record_elems(B, N, n, m) or not _contiguous(rec):
         raise ValueError(f"rec: needs a contiguous buffer of {ff_record_elems(B, N, n, m)} elements")
     return rec
 
@@ -433,6 +436,13 @@ def _tab(x, B, core, name):
     return _ptr(x), int(np.prod(core))
 
 
+def _par(par, B, name):
+    """Model parameters [P] shared or [B, P] per trajectory: returns (ptr, batch stride in elements)."""
+    if par.ndim not in (1, 2) or (par.ndim == 2 and par.shape[0] != B) or not _contiguous(par):
+        raise ValueError(f"{name}: contiguous [P] or [B, P] with B={B}, got shape {tuple(par.shape)}")
+    return _ptr(par), (int(par.shape[1]) if par.ndim == 2 else 0)
+
+
 class Kernels:
     """Thin marshaling layer over one shared library exporting `<prefix><kernel>_<f64|f32>`."""
 
@@ -440,17 +450,21 @@ class Kernels:
         self.lib, self.prefix, self.with_stream = lib, prefix, with_stream
 
     # -- plumbing ---------------------------------------------------------------------------------
-    def _call(self, name, sfx, args, stream):
-        fn = getattr(self.lib, f"{self.prefix}{name}_{sfx}")
+    def _invoke(self, name, sfx, *argv, stream=None):
+        """Call <prefix><name>_<sfx>(*argv[, stream]); IslsError with the library's text for a code other than ISLS_OK."""
+        sym = f"{self.prefix}{name}_{sfx}"
+        fn = getattr(self.lib, sym)
         fn.restype = C.c_int
-        if self.with_stream:
-            rc = fn(C.byref(args), C.c_void_p(stream or 0))
-        else:
-            rc = fn(C.byref(args))
+        rc = fn(*argv, C.c_void_p(stream or 0)) if self.with_stream else fn(*argv)
         if rc != OK:
-            msg = {ERR_ARG: "bad argument", ERR_UNSUPPORTED: "unsupported (n,m)/model/L", ERR_LAUNCH: "launch failed"}
-            raise IslsError(f"{self.prefix}{name}_{sfx} -> {rc} ({msg.get(rc, '?')})")
+            text = getattr(self.lib, "isls_error_string", None)          # the oracle has none
+            if text is not None:
+                text.restype = C.c_char_p
+            raise IslsError(f"{sym} -> {rc}" + (f": {text(rc).decode()}" if text is not None else ""))
         return rc
+
+    def _call(self, name, sfx, args, stream):
+        return self._invoke(name, sfx, C.byref(args), stream=stream)
 
     # -- argument builders (also used to fill OuterArgs) --------------------------------------------
     @staticmethod
@@ -460,9 +474,10 @@ class Kernels:
             a.lin_on, a.lin_model, a.lin_par, a.lin_par_sb = 0, 0, None, 0
             return
         model, par = lin
-        if par.dtype != dtype or not par.is_contiguous() or par.ndim not in (1, 2) or (par.ndim == 2 and par.shape[0] != B):
+        if par.dtype != dtype:
             raise ValueError("lin parameters: contiguous [P] or [B, P] of the pass's dtype")
-        a.lin_on, a.lin_model, a.lin_par, a.lin_par_sb = 1, int(model), _ptr(par), (par.shape[1] if par.ndim == 2 else 0)
+        a.lin_on, a.lin_model = 1, int(model)
+        a.lin_par, a.lin_par_sb = _par(par, B, "lin parameters")
 
     @staticmethod
     def gain_args(A, Bm, Cxx, Cuu, K, Quu, fac, Qux, Cux=None, solve_mode=SOLVE_CHOL, status=None, active=None, rec=None, lin=None):
@@ -485,7 +500,9 @@ class Kernels:
                 lin=None):
         """lin = (model id, parameters [P] or [B, P]): A, Bm are isls_linearize's output for that model (isls_ff_args.lin_on)"""
         B, N, m, n = K.shape
-        a = FfArgs(B=B, N=N, n=n, m=m, solve_mode=solve_mode, _pad=int(ncol) if ncol and ncol > 1 else 0)
+        cols = int(ncol) if ncol and ncol > 1 else 0            # feedback columns: zx, lx, zu, lu, k are [C,B,N,.] blocks ...
+        lead = (cols, B) if cols else (B,)                      # ... read as C*B trajectories, and Quu / fac / Qux are not used
+        a = FfArgs(B=B, N=N, n=n, m=m, solve_mode=solve_mode, _pad=cols)
         if lin is not None and rec is None:
             raise ValueError("lin goes with the packed records")
         Kernels._set_lin(a, lin, B, K.dtype)
@@ -493,37 +510,22 @@ class Kernels:
             if Qr is None or tuple(Qr.shape) not in ((n, n), (1, n, n), (1, 1, n, n)):
                 raise ValueError("Qr_term goes with a batch-shared, time-invariant Qr block")
             a.Qr_term = _ptr(_dense(Qr_term, (n, n), "Qr_term"))
-        if ncol and ncol > 1:                                   # feedback columns: [C,B,N,.] blocks, checked as C*B trajectories
-            col = lambda t, d: None if t is None else _dense(t, (ncol, B, N, d), "column block").reshape(ncol * B, N, d)   # noqa: E731
-            zx, lx, zu, lu, k = col(zx, n), col(lx, n), col(zu, m), col(lu, m), col(k, m)
-            a.zx, a.lx, a.zu, a.lu, a.k = _ptr(zx), _ptr(lx), _ptr(zu), _ptr(lu), _ptr(k)
-            if Qr is not None and (zx is None or lx is None) or Rr is not None and (zu is None or lu is None):
-                raise ValueError("Qr / Rr given without z / l")
-            a.A, a.Bm = make_view(A, B, N, (n, n), "A"), make_view(Bm, B, N, (n, m), "B")
-            a.c0x, a.c0u = make_view(c0x, B, N, (n,), "c0x"), make_view(c0u, B, N, (m,), "c0u")
-            a.Qr, a.Rr = make_view(Qr, B, N, (n, n), "Qr"), make_view(Rr, B, N, (m, m), "Rr")
-            a.xhat, a.uhat = _ptr(_dense(xhat, (B, N, n), "xhat")), _ptr(_dense(uhat, (B, N, m), "uhat"))
-            a.K = _ptr(_dense(K, (B, N, m, n), "K"))
-            a.active = _ptr(active)
-            a.rec = _ptr(_record(rec, B, N, n, m))
-            if seg is not None:
-                a.seg = seg
-            return a
         if seg is not None:
             a.seg = seg
         a.A, a.Bm = make_view(A, B, N, (n, n), "A"), make_view(Bm, B, N, (n, m), "B")
         a.c0x, a.c0u = make_view(c0x, B, N, (n,), "c0x"), make_view(c0u, B, N, (m,), "c0u")
         a.Qr, a.Rr = make_view(Qr, B, N, (n, n), "Qr"), make_view(Rr, B, N, (m, m), "Rr")
-        if Qr is not None and (zx is None or lx is None):
-            raise ValueError("Qr given without zx/lx")
-        if Rr is not None and (zu is None or lu is None):
-            raise ValueError("Rr given without zu/lu")
+        for W, z, l, text in ((Qr, zx, lx, "Qr given without zx/lx"), (Rr, zu, lu, "Rr given without zu/lu")):
+            if W is not None and (z is None or l is None):
+                raise ValueError("Qr / Rr given without z / l" if cols else text)
         a.xhat, a.uhat = _ptr(_dense(xhat, (B, N, n), "xhat")), _ptr(_dense(uhat, (B, N, m), "uhat"))
-        a.zx, a.lx = _ptr(_dense(zx, (B, N, n), "zx")), _ptr(_dense(lx, (B, N, n), "lx"))
-        a.zu, a.lu = _ptr(_dense(zu, (B, N, m), "zu")), _ptr(_dense(lu, (B, N, m), "lu"))
-        a.K, a.Quu = _ptr(_dense(K, (B, N, m, n), "K")), _ptr(_dense(Quu, (B, N, m, m), "Quu"))
-        a.fac, a.Qux = _ptr(_dense(fac, (B, N, m, m), "fac")), _ptr(_dense(Qux, (B, N, m, n), "Qux"))
-        a.k = _ptr(_dense(k, (B, N, m), "k"))
+        a.zx, a.lx = _ptr(_dense(zx, lead + (N, n), "zx")), _ptr(_dense(lx, lead + (N, n), "lx"))
+        a.zu, a.lu = _ptr(_dense(zu, lead + (N, m), "zu")), _ptr(_dense(lu, lead + (N, m), "lu"))
+        a.k = _ptr(_dense(k, lead + (N, m), "k"))
+        a.K = _ptr(_dense(K, (B, N, m, n), "K"))
+        if not cols:
+            a.Quu = _ptr(_dense(Quu, (B, N, m, m), "Quu"))
+            a.fac, a.Qux = _ptr(_dense(fac, (B, N, m, m), "fac")), _ptr(_dense(Qux, (B, N, m, n), "Qux"))
         a.active = _ptr(active)
         a.rec = _ptr(_record(rec, B, N, n, m))
         return a
@@ -556,11 +558,7 @@ class Kernels:
         L = int(alphas.shape[0])
         nvia = int(Qtab.shape[-3])
         a = RolloutArgs(B=B, N=N, n=n, m=m, L=L, model=model, flags=flags, nvia=nvia, u_std=float(u_std))
-        if model_par.ndim == 1:
-            a.model_par, a.model_par_sb = _ptr(model_par), 0
-        else:
-            _dense(model_par, (B, model_par.shape[1]), "model_par")
-            a.model_par, a.model_par_sb = _ptr(model_par), model_par.shape[1]
+        a.model_par, a.model_par_sb = _par(model_par, B, "model_par")
         a.K, a.k = _ptr(_dense(K, (B, N, m, n), "K")), _ptr(_dense(k, (B, N, m), "k"))
         a.xhat, a.uhat = _ptr(_dense(xhat, (B, N, n), "xhat")), _ptr(_dense(uhat, (B, N, m), "uhat"))
         a.x0 = _ptr(_dense(x0, (B, n), "x0"))
@@ -626,11 +624,7 @@ class Kernels:
 
     def riccati_gain_ff(self, gain, ff, sfx, stream=None):
         """Gain pass + first feed-forward pass in one launch (argument blocks from gain_args / ff_args)."""
-        fn = getattr(self.lib, f"isls_riccati_gain_ff_{sfx}")
-        fn.restype = C.c_int
-        rc = fn(C.byref(gain), C.byref(ff), C.c_void_p(stream or 0))
-        if rc != OK:
-            raise IslsError(f"isls_riccati_gain_ff_{sfx} -> {rc}: {self.lib.isls_error_string(rc).decode()}")
+        self._invoke("riccati_gain_ff", sfx, C.byref(gain), C.byref(ff), stream=stream)
 
     @staticmethod
     def project_args(y_in, y_out, sets, rho=1.0, max_iter=200, threshold=1e-4, iters=None, active=None, cols=None,
@@ -737,7 +731,7 @@ class Kernels:
         a.K, a.k = _ptr(_dense(K, (B, R, Cn), "K")), _ptr(_dense(k, (B, R), "k"))
         a.flags = _ptr(_dense(flags, (B,), "flags"))
         size = work.numel() if _is_torch(work) else work.size
-        if size < sls_controller_work_elems(B, N, n) or not (work.is_contiguous() if _is_torch(work) else work.flags["C_CONTIGUOUS"]):
+        if size < sls_controller_work_elems(B, N, n) or not _contiguous(work):
             raise ValueError(f"work: needs a contiguous buffer of {sls_controller_work_elems(B, N, n)} elements")
         a.work = _ptr(work)
         return self._call("sls_controller", _sfx(PHI_U), a, stream)
@@ -806,13 +800,8 @@ class Kernels:
         m = u_log.shape[2]
         _dense(A, (n, n), "A"), _dense(Bm, (n, m), "B"), _dense(K, (N * m, N * n), "K"), _dense(k, (N * m,), "k")
         _dense(x0, (M, n), "x0"), _dense(u_log, (M, N, m), "u_log")
-        fn = getattr(self.lib, f"{self.prefix}sls_closed_loop_{_sfx(x_log)}")
-        fn.restype = C.c_int
-        args = [C.c_int32(M), C.c_int32(N), C.c_int32(n), C.c_int32(m)] + [C.c_void_p(_ptr(t)) for t in (A, Bm, K, k, x0, x_log, u_log)]
-        rc = fn(*args, C.c_void_p(stream or 0)) if self.with_stream else fn(*args)
-        if rc != OK:
-            raise IslsError(f"{self.prefix}sls_closed_loop -> {rc}")
-        return rc
+        return self._invoke("sls_closed_loop", _sfx(x_log), C.c_int32(M), C.c_int32(N), C.c_int32(n), C.c_int32(m),
+                            *(C.c_void_p(_ptr(t)) for t in (A, Bm, K, k, x0, x_log, u_log)), stream=stream)
 
     def riccati_ff_prepare(self, *args, stream=None, **kw):
         a = self.ff_prepare_args(*args, **kw)
@@ -820,10 +809,8 @@ class Kernels:
 
     def ff_segments(self, N, nseg_requested):
         """(nseg, seg_len) the library uses for a horizon of N steps."""
-        fn = self.lib.isls_ff_segments
-        fn.restype = C.c_int32
         seg_len = C.c_int32(0)
-        nseg = int(fn(C.c_int32(int(N)), C.c_int32(int(nseg_requested)), C.byref(seg_len)))
+        nseg = int(self.lib.isls_ff_segments(C.c_int32(int(N)), C.c_int32(int(nseg_requested)), C.byref(seg_len)))
         return nseg, int(seg_len.value)
 
     def rollout_ls(self, *args, stream=None, **kw):
@@ -863,10 +850,7 @@ class Kernels:
         B, N, n = xhat.shape
         m = uhat.shape[2]
         a = LinearizeArgs(B=B, N=N, n=n, m=m, model=model)
-        if model_par.ndim == 1:
-            a.model_par, a.model_par_sb = _ptr(model_par), 0
-        else:
-            a.model_par, a.model_par_sb = _ptr(model_par), model_par.shape[1]
+        a.model_par, a.model_par_sb = _par(model_par, B, "model_par")
         a.xhat, a.uhat = _ptr(_dense(xhat, (B, N, n), "xhat")), _ptr(_dense(uhat, (B, N, m), "uhat"))
         a.A, a.Bm = _ptr(_dense(A, (B, N, n, n), "A")), _ptr(_dense(Bm, (B, N, n, m), "B"))
         a.active = _ptr(active)
@@ -905,46 +889,27 @@ class Kernels:
         """isls_user_model_step: xn [R,n] = f(x [R,n], u [R,m]) with par [P] (shared) or [R,P]."""
         R, n = xn.shape
         _dense(x, (R, n), "x"), _dense(u, (R, u.shape[1]), "u")
-        sb = 0 if par.ndim == 1 else int(_dense(par, (R, par.shape[1]), "par").shape[1])
-        fn = getattr(self.lib, f"{self.prefix}user_model_step_{_sfx(xn)}")
-        fn.restype = C.c_int
-        rc = fn(C.c_int32(model_id), C.c_int32(R), C.c_void_p(_ptr(par)), C.c_int64(sb), C.c_void_p(_ptr(x)), C.c_void_p(_ptr(u)),
-                C.c_void_p(_ptr(xn)), C.c_void_p(stream or 0))
-        if rc != OK:
-            raise IslsError(f"user_model_step -> {rc}")
-        return rc
+        ptr, sb = _par(par, R, "par")
+        return self._invoke("user_model_step", _sfx(xn), C.c_int32(model_id), C.c_int32(R), C.c_void_p(ptr), C.c_int64(sb),
+                            C.c_void_p(_ptr(x)), C.c_void_p(_ptr(u)), C.c_void_p(_ptr(xn)), stream=stream)
 
     def outer_advance(self, adv, sfx, stream=None):
         return self._call("outer_advance", sfx, adv, stream)
 
-    def reduce_convergence(self, cost, res, active, status, out5, stream=None):
-        fn = getattr(self.lib, f"{self.prefix}reduce_convergence_{_sfx(out5)}")
-        fn.restype = C.c_int
+    def _reduce(self, name, cost, res, active, status, out, *tail, stream):
         B = int(cost.shape[0]) if cost is not None else int(res.shape[0])
-        argv = [C.c_int32(B), C.c_void_p(_ptr(cost)), C.c_void_p(_ptr(res)), C.c_void_p(_ptr(active)),
-                C.c_void_p(_ptr(status)), C.c_void_p(_ptr(out5))]
-        if self.with_stream:
-            argv.append(C.c_void_p(stream or 0))
-        rc = fn(*argv)
-        if rc != OK:
-            raise IslsError(f"reduce_convergence -> {rc}")
-        return rc
+        return self._invoke(name, _sfx(out), C.c_int32(B), *(C.c_void_p(_ptr(t)) for t in (cost, res, active, status, out)), *tail,
+                            stream=stream)
+
+    def reduce_convergence(self, cost, res, active, status, out5, stream=None):
+        return self._reduce("reduce_convergence", cost, res, active, status, out5, stream=stream)
 
     def reduce_convergence_table(self, cost, res, active, status, table, rank, stream=None):
         """isls_reduce_convergence_table: the shard's five numbers into row `rank` of the [W,5] table, other rows zeroed."""
         world = int(table.shape[0])
         _dense(table, (world, 5), "table")
-        fn = getattr(self.lib, f"{self.prefix}reduce_convergence_table_{_sfx(table)}")
-        fn.restype = C.c_int
-        B = int(cost.shape[0]) if cost is not None else int(res.shape[0])
-        argv = [C.c_int32(B), C.c_void_p(_ptr(cost)), C.c_void_p(_ptr(res)), C.c_void_p(_ptr(active)),
-                C.c_void_p(_ptr(status)), C.c_void_p(_ptr(table)), C.c_int32(int(rank)), C.c_int32(world)]
-        if self.with_stream:
-            argv.append(C.c_void_p(stream or 0))
-        rc = fn(*argv)
-        if rc != OK:
-            raise IslsError(f"reduce_convergence_table -> {rc}")
-        return rc
+        return self._reduce("reduce_convergence_table", cost, res, active, status, table, C.c_int32(int(rank)), C.c_int32(world),
+                            stream=stream)
 
     def outer(self, gain, ff, ro, admm, J, sfx, skip_gain=False, log=None, outer_active=None, begin_done=False, stream=None):
         a = OuterArgs(gain=gain, ff=ff, ro=ro, admm=admm, J=int(J), skip_gain=int(bool(skip_gain)), begin_done=int(bool(begin_done)))

@@ -18,22 +18,16 @@ import torch
 
 from . import _capi as capi
 
-_LIB = None
 _KERN = None
+library = capi.library
 
 
 def kernels():
     """The process-wide binding of csrc/libisls_hip.so (raises if it has not been built)."""
-    global _LIB, _KERN
+    global _KERN
     if _KERN is None:
-        _LIB = capi.load_hip_library()
-        _KERN = capi.Kernels(_LIB, prefix="isls_", with_stream=True)
+        _KERN = capi.Kernels(library(), prefix="isls_", with_stream=True)
     return _KERN
-
-
-def library():
-    kernels()
-    return _LIB
 
 
 ALPHAS = 10.0 ** np.linspace(0.0, -5.0, 50)            # line-search grid, isls/isls_base.py:10-11

@@ -56,8 +56,6 @@ def run(args):
     import ctypes
     from isls.engine import library
     lib = library()
-    lib.isls_timing_create.restype = ctypes.c_void_p
-    lib.isls_timing_read_ms.restype = ctypes.c_double
 
     def families(fn, tag):
         """per-family kernel time inside run_outer (HIP events of the C driver) while `fn` loops"""
