@@ -299,6 +299,9 @@ constexpr int ISLS_MODEL_USER = 99;
 // model, compiled at run time, with the launch plans of the built-ins
 inline bool is_user_model(int model) { return model >= ISLS_MODEL_USER_BASE; }
 template <typename T> int launch_linearize_user(const isls_linearize_args &a, hipStream_t s);
+// user costs (isls_user_cost_create: ids >= ISLS_COST_USER_BASE): user_cost.hip launches the kernels of the (cost, model) module
+inline bool is_user_cost(int cost_model) { return cost_model >= ISLS_COST_USER_BASE; }
+template <typename T> int launch_expand_user_cost(const isls_expand_args &a, void *Cux, hipStream_t s);
 #endif
 constexpr bool dims_supported(int n, int m)
 {

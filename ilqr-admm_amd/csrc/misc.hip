@@ -141,6 +141,9 @@ static int expand_params(const isls_expand_args &a, ExpP<T> &p)
 template <typename T>
 int launch_expand(const isls_expand_args &a, hipStream_t s)
 {
+    // a user cost: gradients and nominal cost through its own module; its Hessians include Cux, for which this block has no
+    // field (isls_user_cost_expand_* takes it)
+    if (is_user_cost(a.cost_model)) return (a.Cxx || a.Cuu) ? ISLS_ERR_ARG : launch_expand_user_cost<T>(a, nullptr, s);
     ExpP<T> p;
     const int rc = expand_params<T>(a, p);
     if (rc != ISLS_OK) return rc;
@@ -590,6 +593,9 @@ int launch_advance(const isls_advance_args &a, hipStream_t s)
         if (p.lin.uhat == p.uhat) p.lin.uhat = p.xu;
     }
     if (p.has_exp) {
+        // a user cost's expansion is a launch of its own module with an output this block does not name (Cux): the caller runs
+        // the advance without `exp` and isls_user_cost_expand_* behind it on the same stream (isls.Engine.advance does)
+        if (is_user_cost(a.exp.cost_model)) return ISLS_ERR_UNSUPPORTED;
         if ((rc = expand_params<T>(a.exp, p.exp)) != ISLS_OK) return rc;
         if (a.exp.B != ac.B || a.exp.N != ac.N || a.exp.n != ac.n || a.exp.m != ac.m) return ISLS_ERR_ARG;
         if (p.exp.xhat == p.xhat) p.exp.xhat = p.xx;

@@ -1,6 +1,7 @@
 // rollout.hip -- dispatcher of the line-search rollout (kernel template: rollout_kernel.hpp; one translation unit per
 // (n, m, model) family of families.def: rollout_family.hip compiled with -DISLS_FAM_*), plus the Monte-Carlo closed loop of a dense controller
-// (kernel: rollout_kernel.hpp).  User models (ids >= ISLS_MODEL_USER_BASE) go to user_model.hip.
+// (kernel: rollout_kernel.hpp).  User models (ids >= ISLS_MODEL_USER_BASE) go to user_model.hip, user costs (ids >=
+// ISLS_COST_USER_BASE) to user_cost.hip.
 #include "rollout_kernel.hpp"
 
 namespace isls {
@@ -54,8 +55,8 @@ int launch_rollout(const isls_rollout_args &a, hipStream_t s, const isls_admm_ar
     p.cost_cur = (const T *)a.cost_cur;
     p.cost_all = (T *)a.cost_all; p.cost_new = (T *)a.cost_new; p.x_out = (T *)a.x_out; p.u_out = (T *)a.u_out;
     p.best = a.best; p.status = a.status; p.active = a.active;
-    p.cost_model = a.cost_model; p.cpar = (const T *)a.cost_par;
-    if (a.cost_model != ISLS_COST_VIA && (a.cost_model != ISLS_COST_PHUBER || a.model != ISLS_MODEL_TASSA || !a.cost_par))
+    p.cost_model = a.cost_model; p.cpar = (const T *)a.cost_par; p.cpar_sb = 0;
+    if (!is_user_cost(a.cost_model) && a.cost_model != ISLS_COST_VIA && (a.cost_model != ISLS_COST_PHUBER || a.model != ISLS_MODEL_TASSA || !a.cost_par))
         return ISLS_ERR_UNSUPPORTED;
     p.nseg = 1; p.seg_len = a.N; p.stage_on = 0;             // set by the family launcher
     p.fa_on = 0;
@@ -73,6 +74,11 @@ int launch_rollout(const isls_rollout_args &a, hipStream_t s, const isls_admm_ar
         p.fa_res = (T *)f.res; p.fa_res_prev = (T *)f.res_prev; p.fa_active = f.active; p.fa_iters = f.iters;
     }
     int rc = ISLS_ERR_UNSUPPORTED;
+    if (is_user_cost(a.cost_model)) {                          // user_cost.hip: the same plan, the module of the (cost, model) pair
+        rc = launch_rollout_user_cost<T>(p, a, s, fused != nullptr);
+        if (did_fuse) *did_fuse = rc == ISLS_OK && p.fa_on != 0;
+        return rc;
+    }
     if (is_user_model(a.model)) {                              // user_model.hip: the same plan, the model's own module
         rc = launch_rollout_user<T>(p, a, s, fused != nullptr);
         if (did_fuse) *did_fuse = rc == ISLS_OK && p.fa_on != 0;

@@ -68,6 +68,22 @@ struct RoP {
     T *fa_zx, *fa_lx, *fa_zu, *fa_lu, *fa_res, *fa_res_prev;
     View<T> fa_xlo, fa_xhi, fa_ulo, fa_uhi;
     int32_t *fa_active, *fa_iters;
+    int64_t cpar_sb;               // a user cost's parameters: 0 = shared, else one row of that many words per trajectory
+};
+
+// ---- cost of the user's own (isls.costs.Custom) ---------------------------------------------------
+// A run-time compiled program that carries a user cost defines ISLS_USER_COST_NPAR before it includes this header and
+// specialises RoCost<T, NX, NU, true> (user_cost.hpp): the stage cost then replaces the via-point, pseudo-Huber and u_std terms
+// of the search.  The library's own build takes the primary template: no state, no code.
+#ifdef ISLS_USER_COST_NPAR
+constexpr bool kRoUserCost = true;
+#else
+constexpr bool kRoUserCost = false;
+#endif
+template <typename T, int NX, int NU, bool ON>
+struct RoCost {
+    __device__ __forceinline__ void load(const T *) {}
+    __device__ __forceinline__ T stage(const T (&)[NX], const T (&)[NU], int, int) const { return T(0); }
 };
 
 // ---- built-in forward models -------------------------------------------------
@@ -533,7 +549,10 @@ __global__ __launch_bounds__(64, OCC) void rollout_kernel(RoP<T> p)
     const T *Qtab = p.Qtab + (int64_t)bb * p.Qtab_sb, *ztab = p.ztab + (int64_t)bb * p.ztab_sb;
     const T ustd = p.u_std;
     // pseudo-Huber cost model: compiled into the kernels of the Tassa model only, selected at run time
-    constexpr bool kHasPH = MODEL == ISLS_MODEL_TASSA;
+    constexpr bool UC = kRoUserCost;                           // the user's stage cost instead (parameters in registers)
+    constexpr bool kHasPH = !UC && MODEL == ISLS_MODEL_TASSA;
+    RoCost<T, NX, NU, UC> ucost;
+    if constexpr (UC) ucost.load(p.cpar + (int64_t)bb * p.cpar_sb);
     const bool phuber = kHasPH && p.cost_model == ISLS_COST_PHUBER;
     T ph_cu[NU], ph_cx[NX], ph_px[NX], ph_cf[NX], ph_pf[NX];
 #pragma unroll
@@ -663,8 +682,9 @@ __global__ __launch_bounds__(64, OCC) void rollout_kernel(RoP<T> p)
             urw += uadv;                                                                                                    \
         }                                                                                                                   \
         T cst1 = cst, cu1 = cu, ag1 = ag;                                                                                   \
-        bool nz = use_mask ? t == next_q : live;              /* (x-z)'Q(x-z), skipped where Q_t == 0 (uniform test) */     \
-        if (use_mask && nz) next_q = ro_next_bit(qm0, qm1, qm2, qm3, t + 1);                                                \
+        bool nz = UC ? false : (use_mask ? t == next_q : live); /* (x-z)'Q(x-z), skipped where Q_t == 0 (uniform test) */   \
+        if (!UC && use_mask && nz) next_q = ro_next_bit(qm0, qm1, qm2, qm3, t + 1);                                         \
+        if constexpr (UC) cst1 += ucost.stage(x, u, t, N);    /* a user cost: the one term, cu stays 0 */                   \
         if (kHasPH && phuber) {                               /* sum_i cu_i u_i^2 + cx_i ph(x_i,px_i) (+ final term) */     \
             nz = false;                                                                                                     \
             _Pragma("unroll") for (int j = 0; j < NX; ++j)                                                                  \
@@ -686,7 +706,7 @@ __global__ __launch_bounds__(64, OCC) void rollout_kernel(RoP<T> p)
                 cst1 += dq[i] * acc;                                                                                        \
             }                                                                                                               \
         }                                                                                                                   \
-        if (!(kHasPH && phuber)) {                                                                                          \
+        if (!UC && !(kHasPH && phuber)) {                                                                                   \
             _Pragma("unroll") for (int r = 0; r < NU; ++r) cu1 += u[r] * (ustd * u[r]);                                     \
         }                                                                                                                   \
         if (has_wq) {                                                                                                       \
@@ -798,11 +818,15 @@ __global__ __launch_bounds__(64, OCC) void rollout_kernel(RoP<T> p)
     if (any_miss) {
         const T alpha_w = absolute ? T(1) : p.alphas[ind];
         const T *pxh = has_xh ? p.xhat : nullptr, *puh = has_uh ? p.uhat : nullptr;
+        // operands in flight of the row form's replay: four iterations; three in the nine-state kernels compiled for two waves per
+        // SIMD when they carry a user cost -- those sit at the 256-register cap and spill already (516 bytes in the built-in arm
+        // family), and with a stage cost inlined into the search the fourth stage pushed one variant or another 8 bytes past that
+        constexpr int WDR = (UC && OCC == 2 && NX >= 9) ? 3 : 4;
         if (p.seg_lanes > 1 && stage_on)
-            ro_replay<T, NX, NU, MODEL, NU, 4, true>(model, c, ind, valid, accept, stage_on, N, NSEG, S, bN, alpha_w, p.K, p.k, pxh, puh, ck,
+            ro_replay<T, NX, NU, MODEL, NU, WDR, true>(model, c, ind, valid, accept, stage_on, N, NSEG, S, bN, alpha_w, p.K, p.k, pxh, puh, ck,
                                                      stage, uoff, c_aug, GL, p.x_out, p.u_out);
         else if (p.seg_lanes > 1)
-            ro_replay<T, NX, NU, MODEL, NU, 4, false>(model, c, ind, valid, accept, stage_on, N, NSEG, S, bN, alpha_w, p.K, p.k, pxh, puh, ck,
+            ro_replay<T, NX, NU, MODEL, NU, WDR, false>(model, c, ind, valid, accept, stage_on, N, NSEG, S, bN, alpha_w, p.K, p.k, pxh, puh, ck,
                                                       stage, uoff, c_aug, GL, p.x_out, p.u_out);
         else if (stage_on)
             ro_replay<T, NX, NU, MODEL, 1, 2, true>(model, c, ind, valid, accept, stage_on, N, NSEG, S, bN, alpha_w, p.K, p.k, pxh, puh, ck,
@@ -1148,12 +1172,27 @@ struct UserLinP {
     const int32_t *active;
 };
 
+// arguments of user_expand_kernel (user_cost.hpp): the arrays of isls_expand_args plus Cux
+template <typename T>
+struct UserExpP {
+    int B, N, nbt;                 // nbt: workgroups per trajectory
+    const T *par;
+    int64_t par_sb;
+    const T *xhat, *uhat;          // nullable: 0
+    View<T> Qr, Rr;
+    T *Cxx, *Cuu, *Cux, *c0x, *c0u;   // Cxx, Cuu, Cux nullable
+    const int32_t *active;
+};
+
 #ifndef __HIPCC_RTC__
 // the kernels of a user model (user_model.hip): the same plan, launched from the model's run-time compiled module
 template <typename T>
 int launch_rollout_user(RoP<T> &p, const isls_rollout_args &a, hipStream_t s, bool want_fused);
 template <typename T>
 int launch_dense_closed_loop_user(const DenseLoopP<T> &p, const isls_dense_loop_args &a, hipStream_t s);
+// the line search with a user cost (user_cost.hip): the module of the (cost, model) pair, built-in model or user model
+template <typename T>
+int launch_rollout_user_cost(RoP<T> &p, const isls_rollout_args &a, hipStream_t s, bool want_fused);
 #endif
 
 }  // namespace isls

@@ -1,0 +1,140 @@
+// user_cost.hpp -- the device side of a user-written cost function (isls.costs.Custom), compiled at run time by hiprtc for gfx950
+// (user_cost.hip builds the program).  The program text is
+//     #include "user_cost_ad.hpp"
+//     [namespace isls_user { <a user model's step<S, P>> }   #define ISLS_USER_NPAR <P>]      -- with a models.Custom
+//     namespace isls_user_cost { <the user's stage<S, P>> }
+//     #define ISLS_USER_COST_NPAR <P>
+//     #include "user_cost.hpp"
+// and its name expressions instantiate, for one (cost, model, dtype): every (JM, OCC) variant of rollout_kernel that the launch
+// plan of a built-in model of the same dimensions can pick -- the built-ins' template as it is, with RoCost<..., true> below as
+// its stage cost --, user_expand_kernel and user_cost_value_kernel.
+#pragma once
+
+#ifndef ISLS_USER_COST_NPAR
+#error "ISLS_USER_COST_NPAR: the parameter count of the user cost"
+#endif
+
+#ifdef ISLS_USER_NPAR
+#include "user_model.hpp"
+#else
+#include "rollout_kernel.hpp"
+#endif
+#include "user_cost_ad.hpp"
+
+namespace isls {
+
+constexpr int kUserCostParWords = ISLS_USER_COST_NPAR > 0 ? ISLS_USER_COST_NPAR : 1;
+
+template <typename T>
+__device__ __forceinline__ void user_cost_par(const T *p, T (&par)[kUserCostParWords])
+{
+#pragma unroll
+    for (int i = 0; i < kUserCostParWords; ++i) par[i] = i < ISLS_USER_COST_NPAR ? p[i] : T(0);
+}
+
+// the stage cost of the line search: parameters in registers (no LDS words, so the launch plan is the built-ins')
+template <typename T, int NX, int NU>
+struct RoCost<T, NX, NU, true> {
+    T par[kUserCostParWords];
+    __device__ __forceinline__ void load(const T *p) { user_cost_par(p, par); }
+    __device__ __forceinline__ T stage(const T (&x)[NX], const T (&u)[NU], int t, int N) const
+    {
+        return ::isls_user_cost::stage<T, T>(x, u, par, t, N);
+    }
+};
+
+// (Arguments of user_expand_kernel: UserExpP, rollout_kernel.hpp.)
+// Gradient and Hessian of the stage cost along the nominal (isls_expand_args layout: Cxx [B,N,n,n], Cuu [B,N,m,m], Cux [B,N,m,n],
+// c0x [B,N,n], c0u [B,N,m]; Cxx += 2 Qr, Cuu += 2 Rr).  One lane per (step, pair i <= j of [x; u]): it evaluates stage() on a
+// hyper-dual number seeded with (e_i, e_j) and holds H_ij; the diagonal pairs also hold the gradient.  (All K (K + 1) / 2 second
+// derivatives in one lane would be a dual state of (K + 1)(K + 2) / 2 words per scalar: 91 at n = 9, m = 3.)
+// A workgroup takes S steps of one trajectory and walks their S * NP work items in sweeps of 64: up to 64 pairs (n + m <= 10)
+// S = 64 / NP steps fit one sweep; (9, 3) has 78 pairs, and S = 4 steps there make 312 items = 5 sweeps with 8 idle lane slots
+// (one step per workgroup would be 2 sweeps with 50 idle slots, i.e. 8 sweeps for the same four steps).
+// The entries meet in LDS as full symmetric blocks and leave as contiguous runs, one per output array.
+template <typename T, int NX, int NU>
+__global__ __launch_bounds__(64) void user_expand_kernel(UserExpP<T> p)
+{
+    constexpr int K = NX + NU, NP = K * (K + 1) / 2, S = NP <= kWave ? kWave / NP : 4;
+    __shared__ T tXX[S * NX * NX], tUU[S * NU * NU], tUX[S * NU * NX], tg[S * K];
+    const int b = blockIdx.x / p.nbt, t0 = (blockIdx.x - b * p.nbt) * S;
+    if (p.active && p.active[b] == 0) return;                 // uniform: the trajectory's arrays are left as they are
+    const int N = p.N;
+    const int64_t bN = (int64_t)b * N;
+    T par[kUserCostParWords];
+    user_cost_par(p.par + (int64_t)b * p.par_sb, par);
+    using D = ad::Dual2<T>;
+#pragma unroll 1
+    for (int w = threadIdx.x; w < S * NP; w += kWave) {
+        const int ts = w / NP, q = w - ts * NP, t = t0 + ts;
+        if (t >= N) continue;
+        // pair q -> (i, j), i <= j: row i of the upper triangle starts at i K - i (i - 1) / 2
+        int i = 0;
+#pragma unroll
+        for (int r = 1; r < K; ++r) i += q >= r * K - r * (r - 1) / 2 ? 1 : 0;
+        const int j = i + (q - (i * K - i * (i - 1) / 2));
+        D x[NX], u[NU];
+#pragma unroll
+        for (int e = 0; e < NX; ++e) x[e] = D(p.xhat ? p.xhat[(bN + t) * NX + e] : T(0), e == i ? T(1) : T(0), e == j ? T(1) : T(0), T(0));
+#pragma unroll
+        for (int e = 0; e < NU; ++e)
+            u[e] = D(p.uhat ? p.uhat[(bN + t) * NU + e] : T(0), NX + e == i ? T(1) : T(0), NX + e == j ? T(1) : T(0), T(0));
+        const D c = ::isls_user_cost::stage<D, T>(x, u, par, t, N);
+        if (i == j) tg[ts * K + i] = c.a;
+        if (j < NX) {                                          // i <= j < NX
+            const T *Q = p.Qr.p ? p.Qr.at(b, t) : nullptr;
+            tXX[(ts * NX + i) * NX + j] = c.ab + (Q ? T(2) * Q[i * NX + j] : T(0));
+            if (i != j) tXX[(ts * NX + j) * NX + i] = c.ab + (Q ? T(2) * Q[j * NX + i] : T(0));
+        } else if (i >= NX) {
+            const int iu = i - NX, ju = j - NX;
+            const T *R = p.Rr.p ? p.Rr.at(b, t) : nullptr;
+            tUU[(ts * NU + iu) * NU + ju] = c.ab + (R ? T(2) * R[iu * NU + ju] : T(0));
+            if (i != j) tUU[(ts * NU + ju) * NU + iu] = c.ab + (R ? T(2) * R[ju * NU + iu] : T(0));
+        } else {                                               // i < NX <= j: H_ux[j - NX, i]
+            tUX[(ts * NU + (j - NX)) * NX + i] = c.ab;
+        }
+    }
+    __syncthreads();
+    const int ns = N - t0 < S ? N - t0 : S;
+    if (p.Cxx) {
+        T *o = p.Cxx + (bN + t0) * NX * NX;
+        for (int e = threadIdx.x; e < ns * NX * NX; e += kWave) o[e] = tXX[e];
+    }
+    if (p.Cuu) {
+        T *o = p.Cuu + (bN + t0) * NU * NU;
+        for (int e = threadIdx.x; e < ns * NU * NU; e += kWave) o[e] = tUU[e];
+    }
+    if (p.Cux) {
+        T *o = p.Cux + (bN + t0) * NU * NX;
+        for (int e = threadIdx.x; e < ns * NU * NX; e += kWave) o[e] = tUX[e];
+    }
+    for (int e = threadIdx.x; e < ns * K; e += kWave) {
+        const int ts = e / K, i = e - ts * K;
+        if (i < NX) p.c0x[(bN + t0 + ts) * NX + i] = tg[e];
+        else p.c0u[(bN + t0 + ts) * NU + (i - NX)] = tg[e];
+    }
+}
+
+// cost[r] = sum_t stage(x[r,t], u[r,t], par, t, N) for R trajectories, one lane each, summed in the order of the line search
+// (isls_user_cost_value_*, and the nominal cost of an expansion); par [P] shared (par_sb = 0) or one row per trajectory
+template <typename T, int NX, int NU>
+__global__ __launch_bounds__(64) void user_cost_value_kernel(int R, int N, const T *par, int64_t par_sb, const T *x, const T *u, T *cost,
+                                                             const int32_t *active)
+{
+    const int r = blockIdx.x * kWave + threadIdx.x;
+    if (r >= R || (active && active[r] == 0)) return;
+    RoCost<T, NX, NU, true> c;
+    c.load(par + (int64_t)r * par_sb);
+    T sum = T(0);
+    for (int t = 0; t < N; ++t) {
+        T xr[NX], ur[NU];
+#pragma unroll
+        for (int i = 0; i < NX; ++i) xr[i] = x ? x[((int64_t)r * N + t) * NX + i] : T(0);
+#pragma unroll
+        for (int i = 0; i < NU; ++i) ur[i] = u ? u[((int64_t)r * N + t) * NU + i] : T(0);
+        sum += c.stage(xr, ur, t, N);
+    }
+    cost[r] = sum;
+}
+
+}  // namespace isls

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "rollout_kernel.hpp"
+#include "user_rtc.hpp"
 
 #ifndef ISLS_ROCM_PATH
 #define ISLS_ROCM_PATH "/opt/rocm"                           // the Makefile passes the ROCm of its hipcc
@@ -93,13 +94,7 @@ const Rtc &rtc()
 // ---- the registry ----------------------------------------------------------------------------------------------------------
 enum Fn { FN_LIN = 0, FN_LOOP, FN_STEP, FN_RO };             // FN_RO + variant: the rollout kernels
 
-struct Program {                                             // one dtype of a model
-    bool tried = false, ok = false;
-    std::vector<char> code;
-    std::vector<std::string> names, lowered;                 // name expressions (index: Fn) and their mangled names
-    std::vector<std::pair<int, int>> ro;                     // (JM, OCC) of the rollout variant FN_RO + i
-    std::map<int, std::pair<hipModule_t, std::vector<hipFunction_t>>> dev;   // device -> module, functions
-};
+using urtc::Program;
 
 struct UserModel {
     std::string source;
@@ -115,18 +110,6 @@ UserModel *find(int id)
 {
     const int k = id - ISLS_MODEL_USER_BASE;
     return (k >= 0 && k < (int)g_models.size()) ? g_models[k].get() : nullptr;
-}
-
-template <int NX, int NU>
-void ro_variants(std::vector<std::pair<int, int>> &v)
-{
-    for (int occ = 2; occ >= 1; --occ)
-        for (int i = 0; i < (occ == 2 ? 3 : 4); ++i) {
-            const std::pair<int, int> jo(ro_jm_variant<NX, NU>(occ, i), occ);
-            bool seen = false;
-            for (const auto &e : v) seen = seen || e == jo;
-            if (!seen) v.push_back(jo);
-        }
 }
 
 bool contains_word(const std::string &s, const char *w)
@@ -145,35 +128,72 @@ int compile(UserModel &um, int dtype)
 {
     Program &pg = um.prog[dtype];
     if (pg.tried) return pg.ok ? ISLS_OK : ISLS_ERR_COMPILE;
-    pg.tried = true;
-    const Rtc &r = rtc();
-    if (!r.ok) {
-        um.log += "libhiprtc.so could not be loaded: user models need hiprtc (ROCm)\n";
-        return ISLS_ERR_COMPILE;
-    }
-    const std::string csrc = dir_of(reinterpret_cast<const void *>(&find));
     const char *T = dtype == ISLS_DTYPE_F64 ? "double" : "float";
     const std::string dims = std::to_string(um.n) + ", " + std::to_string(um.m);
     pg.names = {std::string("isls::user_linearize_kernel<") + T + ", " + dims + ">",
                 std::string("isls::dense_closed_loop_kernel<") + T + ", " + dims + ", " + std::to_string(ISLS_MODEL_USER) + ">",
                 std::string("isls::user_step_kernel<") + T + ", " + dims + ">"};
-    pg.ro.clear();
-#define ISLS_UM_VARIANTS_(NX_, NU_) if (um.n == NX_ && um.m == NU_) ro_variants<NX_, NU_>(pg.ro);
-    ISLS_FOR_EACH_DIMS(ISLS_UM_VARIANTS_)
-#undef ISLS_UM_VARIANTS_
+    urtc::ro_variants_of(um.n, um.m, pg.ro);
     for (const auto &jo : pg.ro)
         pg.names.push_back(std::string("isls::rollout_kernel<") + T + ", " + dims + ", " + std::to_string(ISLS_MODEL_USER) + ", " +
                            std::to_string(jo.first) + ", " + std::to_string(jo.second) + ">");
-    // the model's step() gets always_inline: a call that is not inlined would take its arrays through scratch memory
-    const std::string src = "#include \"user_model_ad.hpp\"\nnamespace isls_user {\n"
-                            "#pragma clang attribute push(__attribute__((always_inline)), apply_to = function)\n"
-                            "#line 1 \"user_model\"\n" +
-                            um.source +
-                            "\n#pragma clang attribute pop\n}  // namespace isls_user\n#define ISLS_USER_NPAR " + std::to_string(um.npar) +
-                            "\n#include \"user_model.hpp\"\n";
+    const std::string src = "#include \"user_model_ad.hpp\"\n" + urtc::wrap_source("isls_user", "user_model", um.source) +
+                            "#define ISLS_USER_NPAR " + std::to_string(um.npar) + "\n#include \"user_model.hpp\"\n";
+    return urtc::compile_program(src, "user_model.hip", pg, um.log);
+}
+
+// the model's functions on the current device: compiled and loaded on first use (caller holds g_mu)
+int functions(UserModel &um, int dtype, const std::vector<hipFunction_t> **out, hipStream_t capture_check)
+{
+    const int rc = compile(um, dtype);
+    if (rc != ISLS_OK) return rc;
+    return urtc::load_program(um.prog[dtype], out, capture_check);
+}
+
+using urtc::dtype_of;
+using urtc::launch;
+
+// look up model `id` for a launch of dims (n, m) and get its functions
+template <typename T>
+int prepare(int id, int n, int m, hipStream_t s, UserModel **um, const std::vector<hipFunction_t> **fns)
+{
+    std::lock_guard<std::mutex> lk(g_mu);
+    *um = find(id);
+    if (!*um) return ISLS_ERR_ARG;
+    if ((*um)->n != n || (*um)->m != m) return ISLS_ERR_ARG;
+    return functions(**um, dtype_of<T>(), fns, s);
+}
+
+}  // namespace
+
+// ---- what user_cost.hip shares (user_rtc.hpp) --------------------------------------------------------------------------------
+namespace urtc {
+
+bool refused_source(const std::string &src)
+{
+    return contains_word(src, "asm") || contains_word(src, "__asm") || contains_word(src, "__asm__") ||
+           src.find("__builtin_amdgcn") != std::string::npos;
+}
+
+std::string wrap_source(const std::string &ns, const std::string &label, const std::string &body)
+{
+    return "namespace " + ns + " {\n#pragma clang attribute push(__attribute__((always_inline)), apply_to = function)\n#line 1 \"" +
+           label + "\"\n" + body + "\n#pragma clang attribute pop\n}  // namespace " + ns + "\n";
+}
+
+int compile_program(const std::string &src, const char *file, Program &pg, std::string &log)
+{
+    if (pg.tried) return pg.ok ? ISLS_OK : ISLS_ERR_COMPILE;
+    pg.tried = true;
+    const Rtc &r = rtc();
+    if (!r.ok) {
+        log += "libhiprtc.so could not be loaded: user models and costs need hiprtc (ROCm)\n";
+        return ISLS_ERR_COMPILE;
+    }
+    const std::string csrc = dir_of(reinterpret_cast<const void *>(&find));
     hiprtcProgram prog;
-    if (r.create(&prog, src.c_str(), "user_model.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) {
-        um.log += "hiprtcCreateProgram failed\n";
+    if (r.create(&prog, src.c_str(), file, 0, nullptr, nullptr) != HIPRTC_SUCCESS) {
+        log += "hiprtcCreateProgram failed\n";
         return ISLS_ERR_COMPILE;
     }
     for (const auto &nm : pg.names) r.add_name(prog, nm.c_str());
@@ -185,7 +205,7 @@ int compile(UserModel &um, int dtype)
     size_t ls = 0;
     if (r.log_size(prog, &ls) == HIPRTC_SUCCESS && ls > 1) {
         std::string lg(ls, '\0');
-        if (r.log(prog, &lg[0]) == HIPRTC_SUCCESS) um.log += lg.c_str();
+        if (r.log(prog, &lg[0]) == HIPRTC_SUCCESS) log += lg.c_str();
     }
     bool ok = cr == HIPRTC_SUCCESS;
     size_t cs = 0;
@@ -210,12 +230,9 @@ int compile(UserModel &um, int dtype)
     return ok ? ISLS_OK : ISLS_ERR_COMPILE;
 }
 
-// the model's functions on the current device: compiled and loaded on first use (caller holds g_mu)
-int functions(UserModel &um, int dtype, const std::vector<hipFunction_t> **out, hipStream_t capture_check)
+int load_program(Program &pg, const std::vector<hipFunction_t> **out, hipStream_t capture_check)
 {
-    int rc = compile(um, dtype);
-    if (rc != ISLS_OK) return rc;
-    Program &pg = um.prog[dtype];
+    if (!pg.ok) return ISLS_ERR_COMPILE;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return ISLS_ERR_LAUNCH;
     auto it = pg.dev.find(dev);
@@ -238,27 +255,25 @@ int functions(UserModel &um, int dtype, const std::vector<hipFunction_t> **out, 
     return ISLS_OK;
 }
 
-template <typename T>
-constexpr int dtype_of() { return sizeof(T) == 8 ? ISLS_DTYPE_F64 : ISLS_DTYPE_F32; }
-
-// look up model `id` for a launch of dims (n, m) and get its functions
-template <typename T>
-int prepare(int id, int n, int m, hipStream_t s, UserModel **um, const std::vector<hipFunction_t> **fns)
-{
-    std::lock_guard<std::mutex> lk(g_mu);
-    *um = find(id);
-    if (!*um) return ISLS_ERR_ARG;
-    if ((*um)->n != n || (*um)->m != m) return ISLS_ERR_ARG;
-    return functions(**um, dtype_of<T>(), fns, s);
-}
-
 int launch(hipFunction_t f, int grid, size_t smem, hipStream_t s, void **args)
 {
     if (grid <= 0) return ISLS_OK;
     return hipModuleLaunchKernel(f, grid, 1, 1, 64, 1, 1, (unsigned)smem, s, args, nullptr) == hipSuccess ? ISLS_OK : ISLS_ERR_LAUNCH;
 }
 
-}  // namespace
+int user_model_info(int id, std::string *source, int *n, int *m, int *npar)
+{
+    std::lock_guard<std::mutex> lk(g_mu);
+    const UserModel *um = find(id);
+    if (!um) return ISLS_ERR_ARG;
+    if (source) *source = um->source;
+    if (n) *n = um->n;
+    if (m) *m = um->m;
+    if (npar) *npar = um->npar;
+    return ISLS_OK;
+}
+
+}  // namespace urtc
 
 // ---- launches (dispatched from rollout.hip / misc.hip on a.model >= ISLS_MODEL_USER_BASE) -----------------------------------
 template <typename T>
@@ -356,9 +371,7 @@ ISLS_API int isls_user_model_create(const char *source, int32_t n, int32_t m, in
     if (!dims_supported(n, m) || n_par < 0 || n_par > ISLS_USER_MAX_PAR) return ISLS_ERR_UNSUPPORTED;
     const std::string src(source);
     // a model is plain arithmetic: no hand-written ISA through this door
-    if (contains_word(src, "asm") || contains_word(src, "__asm") || contains_word(src, "__asm__") ||
-        src.find("__builtin_amdgcn") != std::string::npos)
-        return ISLS_ERR_ARG;
+    if (urtc::refused_source(src)) return ISLS_ERR_ARG;
     std::lock_guard<std::mutex> lk(g_mu);
     auto um = std::make_unique<UserModel>();
     um->source = src; um->n = n; um->m = m; um->npar = n_par;

@@ -25,6 +25,7 @@ MODEL_LTI, MODEL_ARM3R, MODEL_CAR, MODEL_DI, MODEL_TASSA = 0, 1, 2, 3, 4
 MODEL_USER_BASE, USER_MAX_PAR = 1024, 16      # ids of user models (isls_user_model_create), parameters per model at most
 DTYPE_F64, DTYPE_F32 = 0, 1
 COST_VIA, COST_PHUBER = 0, 1
+COST_USER_BASE = 1024                          # ids of user costs (isls_user_cost_create)
 RO_NAN_TO_1E5, RO_ACCEPT_TEST, RO_ABSOLUTE = 1, 2, 4
 PROJ_NONE, PROJ_BOX, PROJ_SETS = 0, 1, 2
 CTL_NOT_CAUSAL = 1
@@ -83,7 +84,7 @@ class RolloutArgs(C.Structure):
                 ("cost_cur", C.c_void_p), ("cost_all", C.c_void_p), ("best", C.c_void_p),
                 ("cost_new", C.c_void_p), ("x_out", C.c_void_p), ("u_out", C.c_void_p),
                 ("status", C.c_void_p), ("active", C.c_void_p),
-                ("cost_model", C.c_int32), ("_pad2", C.c_int32), ("cost_par", C.c_void_p)]
+                ("cost_model", C.c_int32), ("cost_par_sb", C.c_int32), ("cost_par", C.c_void_p)]
 
 
 class AdmmArgs(C.Structure):
@@ -107,7 +108,7 @@ class ExpandArgs(C.Structure):
                 ("xhat", C.c_void_p), ("uhat", C.c_void_p),
                 ("Cxx", C.c_void_p), ("Cuu", C.c_void_p), ("c0x", C.c_void_p), ("c0u", C.c_void_p),
                 ("cost", C.c_void_p), ("active", C.c_void_p),
-                ("cost_model", C.c_int32), ("_pad2", C.c_int32), ("cost_par", C.c_void_p), ("q_nonzero", C.c_void_p)]
+                ("cost_model", C.c_int32), ("cost_par_sb", C.c_int32), ("cost_par", C.c_void_p), ("q_nonzero", C.c_void_p)]
 
 
 class LinearizeArgs(C.Structure):
@@ -198,10 +199,11 @@ class AdvanceArgs(C.Structure):
 EXPORTED = [f"isls_{k}_{s}" for s in ("f64", "f32") for k in
             ("riccati_gain", "riccati_ff", "riccati_gain_ff", "riccati_ff_prepare", "rollout_ls", "admm_update", "project_rows", "sls_admm", "sls_closed_loop", "columns_rollout", "columns_admm", "dense_closed_loop", "sls_controller", "expand_quadratic", "linearize",
              "accept_step", "reduce_convergence", "reduce_convergence_table", "ilqr_admm_outer", "outer_advance", "columns_iteration",
-             "user_model_step")] + \
+             "user_model_step", "user_cost_value", "user_cost_expand")] + \
            ["isls_ff_segments", "isls_ff_record_elems", "isls_sls_controller_work_elems", "isls_version", "isls_dims_supported", "isls_dims_generic", "isls_error_string", "isls_timing_create",
             "isls_timing_destroy", "isls_timing_reset", "isls_timing_pause", "isls_timing_read_ms",
-            "isls_user_model_create", "isls_user_model_log", "isls_user_model_code", "isls_user_model_load"]
+            "isls_user_model_create", "isls_user_model_log", "isls_user_model_code", "isls_user_model_load",
+            "isls_user_cost_create", "isls_user_cost_log", "isls_user_cost_code", "isls_user_cost_load"]
 
 
 SET_BOX, SET_SOC_UNIT, SET_SQUARE, SET_LINEAR, SET_QUADRATIC, SET_SHELL, SET_MULTILINEAR = 1, 2, 3, 4, 5, 6, 7
@@ -246,6 +248,11 @@ def load_hip_library(path=None):
     lib.isls_user_model_log.argtypes = [C.c_int32, C.c_char_p, C.c_int64]
     lib.isls_user_model_code.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int64)]
     lib.isls_user_model_load.argtypes = [C.c_int32, C.c_int32]
+    lib.isls_user_cost_create.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
+    lib.isls_user_cost_log.restype = C.c_int64
+    lib.isls_user_cost_log.argtypes = [C.c_int32, C.c_char_p, C.c_int64]
+    lib.isls_user_cost_code.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int64)]
+    lib.isls_user_cost_load.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     return lib
 
 
@@ -326,6 +333,64 @@ def user_model_load(model_id, dtype=np.float64):
     rc = library().isls_user_model_load(C.c_int32(model_id), _dtype_code(dtype))
     if rc != OK:
         raise IslsError(f"isls_user_model_load -> {rc}\n{user_model_log(model_id)}")
+
+
+# ------------------------------------------------------------------------------------------------
+# user costs: run-time compiled cost functions (isls_user_cost_*)
+# ------------------------------------------------------------------------------------------------
+_USER_COSTS = {}             # (source, n, m, P) -> id: one registration per process
+
+
+def user_cost_log(cost_id):
+    lib = library()
+    size = lib.isls_user_cost_log(C.c_int32(cost_id), None, 0)
+    buf = C.create_string_buffer(int(max(size, 0)) + 1)
+    lib.isls_user_cost_log(C.c_int32(cost_id), buf, len(buf))
+    return buf.value.decode(errors="replace")
+
+
+def user_cost_create(source, n, m, n_par):
+    """Register a user cost and compile its expansion and value for gfx950 (fp64; the line-search kernels are compiled per model
+    it is used with); the same (source, n, m, n_par) is registered once per process.  IslsError carries the compile log."""
+    key = (str(source), int(n), int(m), int(n_par))
+    if key in _USER_COSTS:
+        return _USER_COSTS[key]
+    lib, cid = library(), C.c_int32(-1)
+    rc = lib.isls_user_cost_create(key[0].encode(), key[1], key[2], key[3], C.byref(cid))
+    if rc == ERR_COMPILE:
+        raise IslsError(f"user cost: compile failed\n{user_cost_log(cid.value) if cid.value >= COST_USER_BASE else ''}")
+    if rc != OK:
+        raise IslsError(f"isls_user_cost_create -> {rc}: {lib.isls_error_string(rc).decode()}")
+    _USER_COSTS[key] = cid.value
+    return cid.value
+
+
+def user_cost_code(cost_id, model=-1, dtype=np.float64):
+    """The gfx950 code object (a bare ELF) of the cost with `model` (a model id; -1: expansion and value only) for dtype."""
+    lib, size = library(), C.c_int64(0)
+    rc = lib.isls_user_cost_code(C.c_int32(cost_id), C.c_int32(model), _dtype_code(dtype), None, C.byref(size))
+    if rc == OK:
+        buf = C.create_string_buffer(size.value)
+        rc = lib.isls_user_cost_code(C.c_int32(cost_id), C.c_int32(model), _dtype_code(dtype), buf, C.byref(size))
+    if rc != OK:
+        raise IslsError(f"isls_user_cost_code -> {rc}: {lib.isls_error_string(rc).decode()}\n{user_cost_log(cost_id)}")
+    return buf.raw
+
+
+def user_cost_load(cost_id, model=-1, dtype=np.float64):
+    """Compile (if need be) and load the module of the cost with `model` onto the current device (outside any stream capture)."""
+    rc = library().isls_user_cost_load(C.c_int32(cost_id), C.c_int32(model), _dtype_code(dtype))
+    if rc != OK:
+        raise IslsError(f"isls_user_cost_load -> {rc}: {library().isls_error_string(rc).decode()}\n{user_cost_log(cost_id)}")
+
+
+def _cost_par(cost_model, cost_par, B):
+    """(ptr, batch stride) of the cost parameters: a user cost's are [P] or [B, P], a built-in cost's one shared vector"""
+    if int(cost_model) >= COST_USER_BASE:
+        if cost_par is None:
+            raise ValueError("a user cost needs its parameters (cost_par)")
+        return _par(cost_par, B, "cost_par")
+    return _ptr(cost_par), 0
 
 
 # ------------------------------------------------------------------------------------------------
@@ -585,7 +650,8 @@ class Kernels:
         a.best, a.cost_new = _ptr(best), _ptr(_dense(cost_new, (B,), "cost_new"))
         a.x_out, a.u_out = _ptr(_dense(x_out, (B, N, n), "x_out")), _ptr(_dense(u_out, (B, N, m), "u_out"))
         a.status, a.active = _ptr(status), _ptr(active)
-        a.cost_model, a.cost_par = int(cost_model), _ptr(cost_par)
+        a.cost_model = int(cost_model)
+        a.cost_par, a.cost_par_sb = _cost_par(cost_model, cost_par, B)
         return a
 
     @staticmethod
@@ -839,7 +905,8 @@ class Kernels:
         a.Cxx, a.Cuu = _ptr(_dense(Cxx, (B, N, n, n), "Cxx")), _ptr(_dense(Cuu, (B, N, m, m), "Cuu"))
         a.c0x, a.c0u = _ptr(_dense(c0x, (B, N, n), "c0x")), _ptr(_dense(c0u, (B, N, m), "c0u"))
         a.cost, a.active = _ptr(_dense(cost, (B,), "cost")), _ptr(active)
-        a.cost_model, a.cost_par, a.q_nonzero = int(cost_model), _ptr(cost_par), _ptr(q_nonzero)
+        a.cost_model, a.q_nonzero = int(cost_model), _ptr(q_nonzero)
+        a.cost_par, a.cost_par_sb = _cost_par(cost_model, cost_par, B)
         return a
 
     def linearize(self, *args, stream=None, **kw):
@@ -892,6 +959,20 @@ class Kernels:
         ptr, sb = _par(par, R, "par")
         return self._invoke("user_model_step", _sfx(xn), C.c_int32(model_id), C.c_int32(R), C.c_void_p(ptr), C.c_int64(sb),
                             C.c_void_p(_ptr(x)), C.c_void_p(_ptr(u)), C.c_void_p(_ptr(xn)), stream=stream)
+
+    def user_cost_value(self, cost_id, par, x, u, cost, stream=None):
+        """isls_user_cost_value: cost [R] = sum_t stage(x [R,N,n], u [R,N,m]) with par [P] (shared) or [R,P]."""
+        R, N, n = x.shape
+        _dense(u, (R, N, u.shape[2]), "u"), _dense(cost, (R,), "cost")
+        ptr, sb = _par(par, R, "par")
+        return self._invoke("user_cost_value", _sfx(cost), C.c_int32(cost_id), C.c_int32(R), C.c_int32(N), C.c_void_p(ptr), C.c_int64(sb),
+                            C.c_void_p(_ptr(x)), C.c_void_p(_ptr(u)), C.c_void_p(_ptr(cost)), stream=stream)
+
+    def user_cost_expand(self, exp, Cux, sfx, stream=None):
+        """isls_user_cost_expand: `exp` an expand_args block whose cost_model is the cost's id; Cux [B,N,m,n] or None."""
+        if Cux is not None:
+            _dense(Cux, (exp.B, exp.N, exp.m, exp.n), "Cux")
+        return self._invoke("user_cost_expand", sfx, C.byref(exp), C.c_void_p(_ptr(Cux)), stream=stream)
 
     def outer_advance(self, adv, sfx, stream=None):
         return self._call("outer_advance", sfx, adv, stream)

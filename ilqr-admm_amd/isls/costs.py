@@ -2,10 +2,14 @@
 
 The reference takes arbitrary `cost_function(x, u)` / `get_Cs(x, u)` callbacks (isls/isls.py:102,360); a HIP kernel
 cannot call back into Python, so a cost that the line search evaluates for every candidate has to be one the kernels
-know.  `PseudoHuber` is the car-parking cost of notebooks/Tutorial.ipynb cell 14 (Tassa et al.): assigning an instance to
+know.  `Custom` is a cost of the user's own, written once as a short HIP C++ function and compiled at run time for gfx950 into the
+line search of whichever model it is used with, plus an expansion on second-order forward-mode numbers (no get_Cs to write).
+`PseudoHuber` is the car-parking cost of notebooks/Tutorial.ipynb cell 14 (Tassa et al.): assigning an instance to
 `iSLS.cost_function` selects ISLS_COST_PHUBER on the device; the object itself is the numpy version of the same cost
 (and of its derivatives, which the notebook gets from autograd) for use on the host and in tests.
 """
+import re
+
 import numpy as np
 
 from . import _capi as capi
@@ -50,3 +54,86 @@ class PseudoHuber:
         idx = np.arange(n + m)
         Cs[:, idx, idx] = np.concatenate([h, np.broadcast_to(2 * self.cu, (N, m))], axis=1)
         return cs, Cs
+
+
+class Custom:
+    """A cost of the user's own: `source` defines
+
+        template <typename S, typename P>
+        __device__ S stage(const S *x, const S *u, const P *par, int t, int N);
+
+    the cost of step t in plain arithmetic on S (the contract of csrc/user_model_ad.hpp); the total cost is the sum over
+    t = 0 .. N-1 (a terminal term: `if (t == N - 1)`; u_{N-1} is costed, as the reference does).  Assigned to
+    `iSLS.cost_function` it puts the line search, the nominal cost and the expansion on the device, with any built-in model or a
+    `models.Custom`: the library compiles it at run time for gfx950 (hiprtc) into the rollout kernel of that model and into an
+    expansion on hyper-dual numbers -- gradient and full Hessian, x-u cross terms included, come from `stage` itself, so
+    `get_Cs=None` is all `solve` / `ilqr_admm` need.  `params` is [P] (shared) or [B, P] (one row per trajectory), P <= 16.
+    Only the (x_dim, u_dim) pairs with the row-per-lane kernels are served (`isls._capi.supported_dims()`)."""
+
+    def __init__(self, x_dim, u_dim, params, source):
+        self.x_dim, self.u_dim = int(x_dim), int(u_dim)
+        self._params = np.atleast_1d(np.asarray(params, dtype=np.float64))
+        if self._params.ndim > 2:
+            raise ValueError("params: [P] or [B, P]")
+        P = self._params.shape[-1]
+        if P > capi.USER_MAX_PAR:
+            raise capi.IslsError(f"a user cost takes at most {capi.USER_MAX_PAR} parameters, got {P}")
+        if not capi.dims_supported(self.x_dim, self.u_dim):
+            raise capi.IslsError(f"user costs need one of the (x_dim, u_dim) pairs with the row-per-lane kernels "
+                                 f"{capi.supported_dims()}, got ({self.x_dim}, {self.u_dim})")
+        if re.search(r"\b(asm|__asm|__asm__)\b", source) or "__builtin_amdgcn" in source:
+            raise capi.IslsError("a user cost is plain arithmetic: `asm` and `__builtin_amdgcn_*` are not accepted")
+        self.source = source
+        self.cost_model = capi.user_cost_create(source, self.x_dim, self.u_dim, P)
+
+    def params(self):
+        return self._params
+
+    def code(self, model=None, dtype=np.float64):
+        """The gfx950 code object of the cost for dtype: with `model` (an isls.models object or a model id) every kernel of the
+        pair -- line search, expansion, value --, without one the expansion and the value."""
+        mid = -1 if model is None else int(getattr(model, "model_id", model))
+        return capi.user_cost_code(self.cost_model, mid, dtype)
+
+    def _batch(self, x, u):
+        import torch
+        from .engine import kernels
+        x, u = np.asarray(x, dtype=np.float64), np.asarray(u, dtype=np.float64)
+        lead = np.broadcast_shapes(x.shape[:-2], u.shape[:-2])
+        N = x.shape[-2]
+        R = int(np.prod(lead)) if lead else 1
+        par = self._params
+        if par.ndim == 2 and par.shape[0] != R:
+            raise ValueError(f"per-trajectory params [{par.shape[0]}, P] need {par.shape[0]} trajectories x, u, got {R}")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        t = lambda a: torch.as_tensor(np.array(a, dtype=np.float64, order="C"), device=dev)   # noqa: E731
+        xs = t(np.broadcast_to(x, lead + (N, self.x_dim)).reshape(R, N, self.x_dim))
+        us = t(np.broadcast_to(u, lead + (N, self.u_dim)).reshape(R, N, self.u_dim))
+        capi.user_cost_load(self.cost_model, -1, np.float64)
+        return torch, kernels(), lead, R, N, xs, us, t(par), dev
+
+    def __call__(self, x, u):
+        """x [..., N, n], u [..., N, m] -> cost [...] (numpy, fp64), evaluated on the device."""
+        torch, kern, lead, R, N, xs, us, par, dev = self._batch(x, u)
+        cost = torch.empty(R, dtype=torch.float64, device=dev)
+        kern.user_cost_value(self.cost_model, par, xs, us, cost, stream=torch.cuda.current_stream().cuda_stream)
+        c = cost.cpu().numpy().reshape(lead)
+        return float(c) if lead == () else c
+
+    def get_Cs(self, x, u):
+        """(cs [N, n+m], Cs [N, n+m, n+m]) along x [N,n], u [N,m] in the reference's convention (or with a leading batch axis), on
+        the device by the same hyper-dual kernel the solver expands with."""
+        single = np.ndim(x) == 2
+        torch, kern, lead, R, N, xs, us, par, dev = self._batch(x, u)
+        n, m = self.x_dim, self.u_dim
+        z = lambda *sh: torch.zeros(*sh, dtype=torch.float64, device=dev)   # noqa: E731
+        Cxx, Cuu, Cux, c0x, c0u = z(R, N, n, n), z(R, N, m, m), z(R, N, m, n), z(R, N, n), z(R, N, m)
+        zero = z(1, n, n)
+        exp = capi.Kernels.expand_args(zero, zero[0, :1], torch.zeros(N, dtype=torch.int32, device=dev), 0.0, c0x, c0u, xhat=xs, uhat=us,
+                                       Cxx=Cxx, Cuu=Cuu, cost_model=self.cost_model, cost_par=par)
+        kern.user_cost_expand(exp, Cux, "f64", stream=torch.cuda.current_stream().cuda_stream)
+        cs = torch.cat([c0x, c0u], dim=-1).cpu().numpy()
+        Cs = torch.cat([torch.cat([Cxx, Cux.transpose(-1, -2)], dim=-1), torch.cat([Cux, Cuu], dim=-1)], dim=-2).cpu().numpy()
+        if single:
+            return cs[0], Cs[0]
+        return cs.reshape(lead + cs.shape[1:]), Cs.reshape(lead + Cs.shape[1:])

@@ -179,7 +179,22 @@ class Engine:
         if self.model >= capi.MODEL_USER_BASE:                # a user model: its module goes onto the device now, outside any capture
             with torch.cuda.device(self.device):
                 capi.user_model_load(self.model, self.dtype)
+        self._load_user_cost()
         self._ab_stale()
+
+    @property
+    def user_cost(self):
+        """True when the cost is a user cost (costs.Custom): its own expansion (with Cux), per-trajectory Hessians, no model hint"""
+        return self.cost_model >= capi.COST_USER_BASE
+
+    def _load_user_cost(self):
+        """A user cost with a model to run it with: the module of the pair goes onto the device now, outside any capture."""
+        if self.user_cost:
+            if not self.fast_dims:
+                raise capi.IslsError("a user cost needs one of the (x_dim, u_dim) pairs with the row-per-lane kernels")
+            with torch.cuda.device(self.device):
+                # with a model: the pair's module (line search, expansion, nominal cost); without one yet: expansion and cost
+                capi.user_cost_load(self.cost_model, -1 if self.model is None else self.model, self.dtype)
 
     def set_quadratic_cost(self, zs, Qs, seq, u_std):
         """Via-point quadratic cost (Base.set_quadratic_cost, isls/base.py:81-89); zs [nvia,n] or [B,nvia,n]."""
@@ -194,14 +209,19 @@ class Engine:
         self._hess_dirty = True
 
     def set_cost_model(self, cost_model, par):
-        """Built-in non-quadratic cost of the line search and of the expansion (ISLS_COST_PHUBER: [cu, cx, px, cf, pf])."""
+        """Non-quadratic cost of the line search and of the expansion: built in (ISLS_COST_PHUBER: [cu, cx, px, cf, pf]) or a
+        user cost (costs.Custom.cost_model; par [P] shared or [B, P] per trajectory)."""
         self.cost_model, self.cost_par = int(cost_model), self._t(np.ascontiguousarray(par))
+        if self.user_cost:
+            if self.Cux is None:
+                self.Cux = torch.zeros(self.B, self.N, self.m, self.n, dtype=self.dtype, device=self.device)
+            self._load_user_cost()
         # the via-point tables are ignored by this cost model; one all-zero entry keeps every argument block well formed
         self.Qtab, self.ztab = torch.zeros(1, self.n, self.n, dtype=self.dtype, device=self.device), torch.zeros(1, self.n, dtype=self.dtype, device=self.device)
         self.seq = torch.zeros(self.N, dtype=torch.int32, device=self.device)
         self.q_nonzero = torch.zeros(self.N, dtype=torch.int32, device=self.device)
         self.u_std = 0.0
-        self._outer_args = None
+        self._outer_args = self._advance_args = None
 
     def set_nominal(self, x_nom, u_nom):
         """nominal_values setter (isls/isls_base.py:80-85): stores the nominal and evaluates its cost."""
@@ -300,6 +320,10 @@ class Engine:
     # ---- single kernels -----------------------------------------------------------------------------------
     def evaluate_cost(self, out=None):
         """cost of the nominal into `out` (default: self.cost); also refreshes c0x, c0u about it"""
+        if self.user_cost:
+            self.kern.user_cost_expand(self._expand_block(False, None, cost=self.cost if out is None else out), None, self.sfx,
+                                       stream=_stream_ptr())
+            return
         self.kern.expand_quadratic(self.Qtab, self.ztab, self.seq, self.u_std, self.c0x, self.c0u,
                                    xhat=self.xhat, uhat=self.uhat, cost=self.cost if out is None else out, cost_model=self.cost_model,
                                    cost_par=self.cost_par, q_nonzero=self.q_nonzero, stream=_stream_ptr())
@@ -316,8 +340,9 @@ class Engine:
         """What every model-structured pass needs of the engine: the row-per-lane kernels for these dimensions, the forms not
         switched off (use_model_structure), a model whose structure the passes know, and ADMM weights that are the same at
         every step (Qr: or all but the last, which the passes take as the terminal block Qr_term)."""
+        # (a user cost has a full stage Hessian, Cux included, which the structured passes do not take: refused, not guessed)
         return (self.fast_dims and self.use_model_structure and self.model in (capi.MODEL_DI, capi.MODEL_ARM3R, capi.MODEL_CAR)
-                and (self._w_invariant or self._w_terminal))
+                and (self._w_invariant or self._w_terminal) and not self.user_cost)
 
     def _structure_expected(self):
         """Will the passes of this engine get the model hint, as far as can be told before A, B are linearised: the structured
@@ -354,7 +379,20 @@ class Engine:
             self._c0_sh = (z(1, self.N, self.n), z(1, self.N, self.m))
         return self._Cxx_sh, self._Cuu_sh
 
+    def _expand_block(self, with_hessian, active, cost=None):
+        return capi.Kernels.expand_args(self.Qtab, self.ztab, self.seq, self.u_std, self.c0x, self.c0u, xhat=self.xhat, uhat=self.uhat,
+                                        Cxx=self.Cxx if with_hessian else None, Cuu=self.Cuu if with_hessian else None,
+                                        Qr=self.Qr, Rr=self.Rr, cost=cost, active=active, cost_model=self.cost_model,
+                                        cost_par=self.cost_par, q_nonzero=self.q_nonzero)
+
     def expand(self, with_hessian=True):
+        if self.user_cost:                                     # user_expand_kernel: gradient and full Hessian, Cux included
+            if self.Cux is None or self.Cux.shape != (self.B, self.N, self.m, self.n):
+                self.Cux = torch.zeros(self.B, self.N, self.m, self.n, dtype=self.dtype, device=self.device)
+                self._outer_args = None
+            self.kern.user_cost_expand(self._expand_block(with_hessian, self.outer_active), self.Cux if with_hessian else None,
+                                       self.sfx, stream=_stream_ptr())
+            return
         shared = with_hessian and self._shared_hessian()
         self.kern.expand_quadratic(self.Qtab, self.ztab, self.seq, self.u_std, self.c0x, self.c0u,
                                    xhat=self.xhat, uhat=self.uhat,
@@ -525,6 +563,21 @@ class Engine:
         if linearize and self.use_model_structure and self._ab_src == STATIC:
             linearize = False                                  # the model's one linearisation is in place: nothing to rewrite
         key = (float(tol_cost), float(tol_osc), bool(linearize))
+        if self.user_cost:
+            # the advance launch without its fused expansion; the user expansion follows on the same stream for the trajectories
+            # still iterating (outer_active after the stop rules), about the nominal just written
+            if self._advance_args is None or self._advance_args[0] != key:
+                acc = K.accept_args(self.xx, self.xu, self.cost_new, self.xhat, self.uhat, self.cost, cost_hist=self.cost_hist,
+                                    hist_len=self.hist_len, tol_cost=tol_cost, tol_osc=tol_osc, outer_active=self.outer_active)
+                lin = K.linearize_args(self.model, self.model_par, self.xhat, self.uhat, self.A, self.Bm) if linearize else None
+                self._advance_args = (key, K.advance_args(acc, lin, None, admm_active=self.admm_active, iters=self.admm_iters,
+                                                          lx=self.lx, lu=self.lu, res_prev=self.res_prev),
+                                      self._expand_block(True, self.outer_active))
+            self.kern.outer_advance(self._advance_args[1], self.sfx, stream=_stream_ptr())
+            self.kern.user_cost_expand(self._advance_args[2], self.Cux, self.sfx, stream=_stream_ptr())
+            if linearize and self._ab_src != STATIC:
+                self._ab_src = LINEARIZED
+            return
         if self._advance_args is None or self._advance_args[0] != key:
             if not self._shared_hessian():
                 raise capi.IslsError("Engine.advance() serves the batch-shared cost Hessians; use accept_x_step / linearize / expand")

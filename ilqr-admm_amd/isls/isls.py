@@ -73,11 +73,13 @@ class iSLS(Base):
 
     @cost_function.setter
     def cost_function(self, function):
-        """None -> the via-point quadratic cost of set_cost_variables; an `isls.costs` object (PseudoHuber) -> that cost
-        on the device, for the line search and for the expansion (the reference's cost_function / get_Cs pair)."""
+        """None -> the via-point quadratic cost of set_cost_variables; an `isls.costs` object (PseudoHuber, or a Custom cost of
+        the user's own) -> that cost on the device, for the line search and for the expansion (the reference's cost_function / get_Cs pair)."""
         if function is None:
             self._cost_function, self._host_cost = None, False
             return
+        if hasattr(function, "cost_model") and hasattr(function, "x_dim") and (function.x_dim, function.u_dim) != (self.x_dim, self.u_dim):
+            raise ValueError("cost dimensions do not match x_dim/u_dim")
         self._cost_function = function
         if hasattr(function, "cost_model"):
             self._host_cost = False
@@ -210,7 +212,8 @@ class iSLS(Base):
     def _expand(self, Cts=None, cts=None):
         e = self.engine
         if Cts is None:
-            e.Cux = None
+            if not e.user_cost:                                 # (a user cost's expansion writes Cux)
+                e.Cux = None
             e.expand()
             return
         n = self.x_dim
@@ -409,7 +412,8 @@ class iSLS(Base):
         from the caller's get_Cs otherwise (gradients of the regulariser are added by the feed-forward pass either way)."""
         e = self.engine
         if self._device_expansion(get_Cs):
-            e.Cux = None
+            if not e.user_cost:                                 # (a user cost's expansion writes Cux)
+                e.Cux = None
             e.expand()
             return
         Cts, cts = hostpath.expansion(self, get_Cs)
@@ -554,6 +558,10 @@ class iSLS(Base):
         about the nominal, i.e. the Riccati solution rolled through the linearised dynamics, plus the dense form's last
         control (column 0 of isls_columns_rollout; SURVEY 8a quirk i)."""
         e = self.engine
+        if e.user_cost:
+            # the column roll-out (isls_columns_rollout) takes Cuu alone: a user cost's x-u cross terms would be dropped
+            raise capi.IslsError("the batch-form iLQR (backward_pass_batch, iterate_once_batch, solve(method='batch')) does not serve a "
+                                 "user cost (costs.Custom): its column roll-out has no Cux term; use method='dp'")
         if not self._user_AB:
             self._linearize(None)
         self._expand(Cts, cts)

@@ -272,6 +272,10 @@ def isls_admm(self, dim, get_AB=None, get_Cs=None, project_x=False, project_u=Fa
     the last outer iteration per problem, `self.admm_logs` their (prim, dual) residuals [J, B, 2]."""
     self._check_get_Cs(get_Cs)                                                  # a callable cost needs its get_Cs
     e = self.engine
+    if e.user_cost:
+        # the column passes (isls_columns_*) take Cuu alone: a user cost's x-u cross terms would be dropped without a word
+        raise capi.IslsError("isls_admm does not serve a user cost (costs.Custom): its column passes have no Cux term; use solve / "
+                             "ilqr_admm, or hand the cost over as a callable with get_Cs")
     B, N, n, m, C = self.batch, self.N, self.x_dim, self.u_dim, int(dim) + 1
     if not 1 <= dim <= n or C > capi.MAX_ROW_DIM:
         raise ValueError(f"dim must be in [1, {min(n, capi.MAX_ROW_DIM - 1)}]")

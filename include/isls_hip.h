@@ -84,6 +84,15 @@ extern "C" {
                                ph(x,p) = sqrt(x^2 + p^2) - p ; cost_par = [cu(m), cx(n), px(n), cf(n), pf(n)]
                                (built into the kernels of ISLS_MODEL_TASSA; Qtab/ztab/seq/u_std are then ignored)         */
 
+/* User-written costs (isls_user_cost_create): ids >= ISLS_COST_USER_BASE name a registered user cost.  The `cost_model` fields of
+ * isls_rollout_args and isls_expand_args (and of the blocks that embed isls_rollout_args) take such an id like a built-in one, with
+ * any built-in model of a fast (n, m) pair or a user model; cost_par = the cost's n_par parameters ([n_par] shared, or per
+ * trajectory with cost_par_sb = n_par); Qtab / ztab / seq / u_std are then ignored.  isls_expand_quadratic_* serves such an id
+ * for the gradients and the nominal cost only (Cxx == Cuu == NULL); the full expansion, with Cux, is isls_user_cost_expand_*.
+ * isls_outer_advance_* refuses such an id in `exp` (ISLS_ERR_UNSUPPORTED): run it with exp.c0x == NULL and the user expansion
+ * behind it on the same stream, with active = accept.outer_active.  No generic (n, m), no model hint (lin_on). */
+#define ISLS_COST_USER_BASE 1024
+
 /* rollout flags */
 #define ISLS_RO_NAN_TO_1E5 1   /* costs[isnan] = 1e5            (iterate_once_dp only, isls/isls.py:362)          */
 #define ISLS_RO_ACCEPT_TEST 2  /* accept iff cost_best < cost_cur (isls/isls.py:365-369); else nominal is kept    */
@@ -289,9 +298,9 @@ typedef struct isls_rollout_args {
     void *x_out, *u_out;
     int32_t *status;
     const int32_t *active;
-    int32_t cost_model;             /* ISLS_COST_* */
-    int32_t _pad2;
-    const void *cost_par;           /* ISLS_COST_PHUBER: [m + 4n] shared by the batch */
+    int32_t cost_model;             /* ISLS_COST_*, or the id of a user cost (>= ISLS_COST_USER_BASE) */
+    int32_t cost_par_sb;            /* a user cost's parameters: 0 = shared, else n_par = one row per trajectory (built-in costs: 0) */
+    const void *cost_par;           /* ISLS_COST_PHUBER: [m + 4n] shared by the batch; a user cost: [n_par] or [B, n_par] */
 } isls_rollout_args;
 
 int isls_rollout_ls_f64(const isls_rollout_args *a, void *stream);
@@ -601,7 +610,7 @@ typedef struct isls_expand_args {
     const int32_t *active;
     int32_t cost_model;             /* ISLS_COST_VIA: as above; ISLS_COST_PHUBER: gradient / (diagonal) Hessian of the
                                        pseudo-Huber cost about the nominal, the get_Cs callback of Tutorial.ipynb cell 16 */
-    int32_t _pad2;
+    int32_t cost_par_sb;            /* as in isls_rollout_args */
     const void *cost_par;
     const int32_t *q_nonzero;       /* [N] nullable hint as in isls_rollout_args: 0 where Q_t == 0 for every trajectory */
 } isls_expand_args;
@@ -741,6 +750,38 @@ int isls_user_model_step_f64(int32_t id, int32_t R, const void *par, int64_t par
                              void *stream);
 int isls_user_model_step_f32(int32_t id, int32_t R, const void *par, int64_t par_sb, const void *x, const void *u, void *xn,
                              void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * User-written cost functions, compiled at run time for gfx950 like the user models.  `source` defines
+ *     template <typename S, typename P> __device__ S stage(const S *x, const S *u, const P *par, int t, int N);
+ * the cost of step t; the total cost is sum_{t=0}^{N-1} stage(x_t, u_t, par, t, N) (a terminal term: `if (t == N - 1)`; u_{N-1}
+ * is costed).  Plain arithmetic on S (the contract: csrc/user_model_ad.hpp); no inline assembly, no __builtin_amdgcn_*.  It is
+ * compiled with S = T into the rollout kernel of the built-in models (the line search; one program per model it is used with)
+ * and the row-wise value, and with S = a hyper-dual number (csrc/user_cost_ad.hpp) for the expansion: gradient and full
+ * Hessian, Cux included, without a get_Cs.  The registry of user costs is process-wide, for the life of the process.
+ * ------------------------------------------------------------------------------------------- */
+/* Compiles `source` (fp64: the expansion and the value) and registers it: *id >= ISLS_COST_USER_BASE, also when the compile fails
+ * (ISLS_ERR_COMPILE; its log stays readable).  ISLS_ERR_UNSUPPORTED: (n, m) not a fast pair, n_par outside
+ * [0, ISLS_USER_MAX_PAR]; ISLS_ERR_ARG: a source with `asm` or `__builtin_amdgcn`.  Needs no GPU. */
+int isls_user_cost_create(const char *source, int32_t n, int32_t m, int32_t n_par, int32_t *id);
+/* The compile log of the cost's programs (as isls_user_model_log). */
+int64_t isls_user_cost_log(int32_t id, char *buf, int64_t len);
+/* The gfx950 code object of the cost with `model` (a built-in model of the cost's (n, m), a user model of them, or -1: the
+ * expansion and the value only) for dtype, as isls_user_model_code.  Compiles the (cost, model, dtype) program if need be. */
+int isls_user_cost_code(int32_t id, int32_t model, int32_t dtype, void *buf, int64_t *len);
+/* Compiles the (cost, model, dtype) program if need be and loads its module onto the current device (once; outside any stream
+ * capture).  A launch with a pair that has not been loaded compiles and loads it then, and fails inside a stream capture. */
+int isls_user_cost_load(int32_t id, int32_t model, int32_t dtype);
+/* cost[r] = sum_t stage(x[r,t], u[r,t], par, t, N): x [R,N,n], u [R,N,m], par [n_par] (par_sb = 0) or [R,n_par] -> cost [R]. */
+int isls_user_cost_value_f64(int32_t id, int32_t R, int32_t N, const void *par, int64_t par_sb, const void *x, const void *u,
+                             void *cost, void *stream);
+int isls_user_cost_value_f32(int32_t id, int32_t R, int32_t N, const void *par, int64_t par_sb, const void *x, const void *u,
+                             void *cost, void *stream);
+/* The expansion of a user cost about the nominal, in the layouts and with the `active` semantics of isls_expand_quadratic_*:
+ *   c0x, c0u = gradient ; Cxx = H_xx + 2 Qr ; Cuu = H_uu + 2 Rr ; Cux [B,N,m,n] = H_ux ; cost[b] (nullable) = the nominal's cost.
+ * Cxx, Cuu, Cux nullable (skipped).  a->cost_model is the cost's id; Qtab, ztab, seq, u_std, q_nonzero are ignored. */
+int isls_user_cost_expand_f64(const isls_expand_args *a, void *Cux, void *stream);
+int isls_user_cost_expand_f32(const isls_expand_args *a, void *Cux, void *stream);
 
 int isls_version(void);
 /* 1 when the kernels are instantiated for state dimension n and control dimension m (the pairs are compile-time template
