@@ -16,7 +16,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #else
-typedef struct ihipStream_t *hipStream_t;   // run-time compilation of a user model (user_model.hip): device code only
+typedef struct ihipStream_t *hipStream_t;   // run-time compilation of a user model or cost (user_rtc.hip): device code only
 #endif
 
 #include <type_traits>
@@ -299,7 +299,7 @@ constexpr int ISLS_MODEL_USER = 99;
 // model, compiled at run time, with the launch plans of the built-ins
 inline bool is_user_model(int model) { return model >= ISLS_MODEL_USER_BASE; }
 template <typename T> int launch_linearize_user(const isls_linearize_args &a, hipStream_t s);
-// user costs (isls_user_cost_create: ids >= ISLS_COST_USER_BASE): user_cost.hip launches the kernels of the (cost, model) module
+// user costs (isls_user_cost_create: ids >= ISLS_COST_USER_BASE): user_cost.hip launches their expansion and value kernels
 inline bool is_user_cost(int cost_model) { return cost_model >= ISLS_COST_USER_BASE; }
 template <typename T> int launch_expand_user_cost(const isls_expand_args &a, void *Cux, hipStream_t s);
 #endif

@@ -1,7 +1,7 @@
 // rollout.hip -- dispatcher of the line-search rollout (kernel template: rollout_kernel.hpp; one translation unit per
 // (n, m, model) family of families.def: rollout_family.hip compiled with -DISLS_FAM_*), plus the Monte-Carlo closed loop of a dense controller
-// (kernel: rollout_kernel.hpp).  User models (ids >= ISLS_MODEL_USER_BASE) go to user_model.hip, user costs (ids >=
-// ISLS_COST_USER_BASE) to user_cost.hip.
+// (kernel: rollout_kernel.hpp).  A line search with a user model (ids >= ISLS_MODEL_USER_BASE) or a user cost (ids >=
+// ISLS_COST_USER_BASE) goes to user_rtc.hip.
 #include "rollout_kernel.hpp"
 
 namespace isls {
@@ -74,12 +74,7 @@ int launch_rollout(const isls_rollout_args &a, hipStream_t s, const isls_admm_ar
         p.fa_res = (T *)f.res; p.fa_res_prev = (T *)f.res_prev; p.fa_active = f.active; p.fa_iters = f.iters;
     }
     int rc = ISLS_ERR_UNSUPPORTED;
-    if (is_user_cost(a.cost_model)) {                          // user_cost.hip: the same plan, the module of the (cost, model) pair
-        rc = launch_rollout_user_cost<T>(p, a, s, fused != nullptr);
-        if (did_fuse) *did_fuse = rc == ISLS_OK && p.fa_on != 0;
-        return rc;
-    }
-    if (is_user_model(a.model)) {                              // user_model.hip: the same plan, the model's own module
+    if (is_user_model(a.model) || is_user_cost(a.cost_model)) {   // user_rtc.hip: the same plan, the module of the (model, cost) pair
         rc = launch_rollout_user<T>(p, a, s, fused != nullptr);
         if (did_fuse) *did_fuse = rc == ISLS_OK && p.fa_on != 0;
         return rc;

@@ -1185,14 +1185,13 @@ struct UserExpP {
 };
 
 #ifndef __HIPCC_RTC__
-// the kernels of a user model (user_model.hip): the same plan, launched from the model's run-time compiled module
+// the line search with a user model, a user cost or both (user_rtc.hip): the same plan, launched from the run-time compiled
+// module of the (model, cost) pair
 template <typename T>
 int launch_rollout_user(RoP<T> &p, const isls_rollout_args &a, hipStream_t s, bool want_fused);
+// the dense closed loop of a user model (user_model.hip), from the model's own module
 template <typename T>
 int launch_dense_closed_loop_user(const DenseLoopP<T> &p, const isls_dense_loop_args &a, hipStream_t s);
-// the line search with a user cost (user_cost.hip): the module of the (cost, model) pair, built-in model or user model
-template <typename T>
-int launch_rollout_user_cost(RoP<T> &p, const isls_rollout_args &a, hipStream_t s, bool want_fused);
 #endif
 
 }  // namespace isls

@@ -1,0 +1,408 @@
+// user_rtc.hip -- run-time compilation (hiprtc, gfx950) for user-written models and costs: the hiprtc loader, the registry of
+// sources, the cache of compiled programs, module loading and the line-search launch (user_rtc.hpp; the device side is
+// user_model.hpp / user_cost.hpp, the launches of a model's and a cost's own kernels are user_model.hip / user_cost.hip).
+//
+// One hiprtc program per (model, cost, dtype).  (user model, none) holds the model's linearisation, dense closed loop and row-wise
+// step, (none, cost) the cost's expansion and value, (model, cost) -- the model a built-in id or a user model, whose source goes
+// into the same program -- the cost's two kernels again; and every key with a model holds each rollout_kernel variant the launch
+// plan can pick for its (n, m).  The rollout launch takes its plan from plan_rollout -- the very function the built-in families
+// launch with -- and differs only in how it starts the kernel (hipModuleLaunchKernel of the matching instantiation in the key's
+// module instead of hipLaunchKernelGGL).
+#ifndef _GNU_SOURCE
+#define _GNU_SOURCE                                          // dlmopen
+#endif
+#include <dlfcn.h>
+#include <hip/hiprtc.h>
+
+#include <cstring>
+#include <memory>
+#include <mutex>
+#include <tuple>
+
+#include "user_rtc.hpp"
+
+#ifndef ISLS_ROCM_PATH
+#define ISLS_ROCM_PATH "/opt/rocm"                           // the Makefile passes the ROCm of its hipcc
+#endif
+
+namespace isls {
+namespace urtc {
+
+namespace {
+
+// ---- hiprtc, dlopen-ed on the first create -------------------------------------------------------------------------------
+struct Rtc {
+    bool ok = false;
+    hiprtcResult (*create)(hiprtcProgram *, const char *, const char *, int, const char *const *, const char *const *);
+    hiprtcResult (*add_name)(hiprtcProgram, const char *);
+    hiprtcResult (*compile)(hiprtcProgram, int, const char *const *);
+    hiprtcResult (*log_size)(hiprtcProgram, size_t *);
+    hiprtcResult (*log)(hiprtcProgram, char *);
+    hiprtcResult (*code_size)(hiprtcProgram, size_t *);
+    hiprtcResult (*code)(hiprtcProgram, char *);
+    hiprtcResult (*lowered)(hiprtcProgram, const char *, const char **);
+    hiprtcResult (*destroy)(hiprtcProgram *);
+};
+
+std::string dir_of(const void *addr)
+{
+    Dl_info info;
+    if (!dladdr(addr, &info) || !info.dli_fname) return std::string();
+    std::string f = info.dli_fname;
+    const size_t k = f.rfind('/');
+    return k == std::string::npos ? std::string(".") : f.substr(0, k);
+}
+
+const Rtc &rtc()
+{
+    static Rtc r;
+    static std::once_flag once;
+    std::call_once(once, [] {
+        // The hiprtc of the ROCm whose hipcc built this library comes first, in a link namespace of its own: a process may hold
+        // another hiprtc and comgr already (PyTorch ships its own, built on another LLVM), and the code of a user model must
+        // come from the compiler that built the built-in kernels -- same instructions for the same template, same register
+        // allocation.  Then the ROCm of $ROCM_PATH, then whatever the loader finds.
+        void *h = nullptr;
+        std::vector<std::string> own = {ISLS_ROCM_PATH "/lib/libhiprtc.so"};
+        if (const char *rp = getenv("ROCM_PATH")) own.push_back(std::string(rp) + "/lib/libhiprtc.so");
+        for (const auto &n : own)
+            if ((h = dlmopen(LM_ID_NEWLM, n.c_str(), RTLD_NOW | RTLD_LOCAL)) != nullptr) break;
+        const std::string hipdir = dir_of(reinterpret_cast<const void *>(&hipModuleLoadData));   // next to the HIP runtime
+        for (const std::string &n : {std::string("libhiprtc.so"), std::string("libhiprtc.so.7"), hipdir + "/libhiprtc.so"}) {
+            if (h) break;
+            h = dlopen(n.c_str(), RTLD_NOW | RTLD_LOCAL);
+        }
+        if (!h) return;
+        bool all = true;
+        auto sym = [&](auto &fp, const char *name) {
+            fp = reinterpret_cast<std::remove_reference_t<decltype(fp)>>(dlsym(h, name));
+            all = all && fp != nullptr;
+        };
+        sym(r.create, "hiprtcCreateProgram");
+        sym(r.add_name, "hiprtcAddNameExpression");
+        sym(r.compile, "hiprtcCompileProgram");
+        sym(r.log_size, "hiprtcGetProgramLogSize");
+        sym(r.log, "hiprtcGetProgramLog");
+        sym(r.code_size, "hiprtcGetCodeSize");
+        sym(r.code, "hiprtcGetCode");
+        sym(r.lowered, "hiprtcGetLoweredName");
+        sym(r.destroy, "hiprtcDestroyProgram");
+        r.ok = all;
+    });
+    return r;
+}
+
+// ---- sources and their compilation -------------------------------------------------------------------------------------------
+bool contains_word(const std::string &s, const char *w)
+{
+    const size_t lw = strlen(w);
+    for (size_t k = s.find(w); k != std::string::npos; k = s.find(w, k + 1)) {
+        const bool l = k == 0 || !(isalnum((unsigned char)s[k - 1]) || s[k - 1] == '_');
+        const bool r = k + lw >= s.size() || !(isalnum((unsigned char)s[k + lw]) || s[k + lw] == '_');
+        if (l && r) return true;
+    }
+    return false;
+}
+
+// a user source is plain arithmetic: true when it holds `asm` (any spelling) or `__builtin_amdgcn`
+bool refused_source(const std::string &src)
+{
+    return contains_word(src, "asm") || contains_word(src, "__asm") || contains_word(src, "__asm__") ||
+           src.find("__builtin_amdgcn") != std::string::npos;
+}
+
+// `body` inside `namespace ns`, every function of it always_inline (a call that is not inlined would take its arrays through
+// scratch memory), compiler messages pointing at `label`:<line of the user's text>
+std::string wrap_source(const std::string &ns, const std::string &label, const std::string &body)
+{
+    return "namespace " + ns + " {\n#pragma clang attribute push(__attribute__((always_inline)), apply_to = function)\n#line 1 \"" +
+           label + "\"\n" + body + "\n#pragma clang attribute pop\n}  // namespace " + ns + "\n";
+}
+
+// Compile `src` (file name `file` in the messages) for gfx950 with pg.names as name expressions; fills pg.code / pg.lowered,
+// appends the compiler's log to `log`.  Once per Program (pg.tried).
+int compile_program(const std::string &src, const char *file, Program &pg, std::string &log)
+{
+    if (pg.tried) return pg.ok ? ISLS_OK : ISLS_ERR_COMPILE;
+    pg.tried = true;
+    const Rtc &r = rtc();
+    if (!r.ok) {
+        log += "libhiprtc.so could not be loaded: user models and costs need hiprtc (ROCm)\n";
+        return ISLS_ERR_COMPILE;
+    }
+    const std::string csrc = dir_of(reinterpret_cast<const void *>(&rtc));   // the device headers lie next to the library
+    hiprtcProgram prog;
+    if (r.create(&prog, src.c_str(), file, 0, nullptr, nullptr) != HIPRTC_SUCCESS) {
+        log += "hiprtcCreateProgram failed\n";
+        return ISLS_ERR_COMPILE;
+    }
+    for (const auto &nm : pg.names) r.add_name(prog, nm.c_str());
+    // the flags of the Makefile's build of the built-in kernels (-O3 -std=c++17, clang's HIP default contraction): the same
+    // template gives the same instructions, so a user model that restates a built-in one gets its bits
+    const std::string inc = "-I" + csrc;
+    const char *opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=fast-honor-pragmas", inc.c_str()};
+    const hiprtcResult cr = r.compile(prog, (int)(sizeof(opts) / sizeof(opts[0])), opts);
+    size_t ls = 0;
+    if (r.log_size(prog, &ls) == HIPRTC_SUCCESS && ls > 1) {
+        std::string lg(ls, '\0');
+        if (r.log(prog, &lg[0]) == HIPRTC_SUCCESS) log += lg.c_str();
+    }
+    bool ok = cr == HIPRTC_SUCCESS;
+    size_t cs = 0;
+    if (ok && r.code_size(prog, &cs) == HIPRTC_SUCCESS && cs > 0) {
+        pg.code.resize(cs);
+        ok = r.code(prog, pg.code.data()) == HIPRTC_SUCCESS;
+    } else {
+        ok = false;
+    }
+    pg.lowered.clear();
+    for (const auto &nm : pg.names) {
+        const char *low = nullptr;
+        if (!ok || r.lowered(prog, nm.c_str(), &low) != HIPRTC_SUCCESS || !low) {
+            ok = false;
+            break;
+        }
+        pg.lowered.push_back(low);
+    }
+    r.destroy(&prog);
+    pg.ok = ok;
+    if (!ok) pg.code.clear();
+    return ok ? ISLS_OK : ISLS_ERR_COMPILE;
+}
+
+// the program's functions (index: pg.names) on the current device, loaded on first use -- never inside a stream capture
+// (capture_check: the stream to test, or nullptr)
+int load_program(Program &pg, const std::vector<hipFunction_t> **out, hipStream_t capture_check)
+{
+    if (!pg.ok) return ISLS_ERR_COMPILE;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return ISLS_ERR_LAUNCH;
+    auto it = pg.dev.find(dev);
+    if (it == pg.dev.end()) {
+        if (capture_check) {                                 // no module load inside a stream capture: load first
+            hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+            if (hipStreamIsCapturing(capture_check, &st) != hipSuccess || st != hipStreamCaptureStatusNone) return ISLS_ERR_LAUNCH;
+        }
+        hipModule_t mod;
+        if (hipModuleLoadData(&mod, pg.code.data()) != hipSuccess) return ISLS_ERR_LAUNCH;
+        std::vector<hipFunction_t> fns(pg.lowered.size());
+        for (size_t i = 0; i < fns.size(); ++i)
+            if (hipModuleGetFunction(&fns[i], mod, pg.lowered[i].c_str()) != hipSuccess) {
+                hipModuleUnload(mod);
+                return ISLS_ERR_LAUNCH;
+            }
+        it = pg.dev.emplace(dev, std::make_pair(mod, std::move(fns))).first;
+    }
+    if (out) *out = &it->second.second;
+    return ISLS_OK;
+}
+
+// ---- the registry and the program cache (both under g_mu) --------------------------------------------------------------------
+struct Source {
+    std::string source;
+    int n, m, npar;
+    std::string log;
+};
+
+std::mutex g_mu;
+std::vector<std::unique_ptr<Source>> g_src[2];               // [Kind]: id - ISLS_{MODEL,COST}_USER_BASE -> source
+std::map<std::tuple<int, int, int>, Program> g_prog;         // (cost, dtype, model) -> program: the programs of a cost lie together
+
+Source *find(Kind kind, int id)
+{
+    const int k = id - (kind == KIND_MODEL ? ISLS_MODEL_USER_BASE : ISLS_COST_USER_BASE);
+    return (k >= 0 && k < (int)g_src[kind].size()) ? g_src[kind][k].get() : nullptr;
+}
+
+// the (JM, OCC) variants the launch plan of these dimensions can pick
+template <int NX, int NU>
+void ro_variants(std::vector<std::pair<int, int>> &v)
+{
+    for (int occ = 2; occ >= 1; --occ)
+        for (int i = 0; i < (occ == 2 ? 3 : 4); ++i) {
+            const std::pair<int, int> jo(ro_jm_variant<NX, NU>(occ, i), occ);
+            bool seen = false;
+            for (const auto &e : v) seen = seen || e == jo;
+            if (!seen) v.push_back(jo);
+        }
+}
+
+// the built-in family (n, m, model) and its LDS words
+bool builtin_family(int n, int m, int model, int *mdlw)
+{
+#define ISLS_URTC_FAMILY_(NX_, NU_, MODEL_) \
+    if (n == NX_ && m == NU_ && model == MODEL_) { *mdlw = Model<double, NX_, NU_, MODEL_>::LDS_WORDS; return true; }
+    ISLS_FOR_EACH_FAMILY(ISLS_URTC_FAMILY_)
+#undef ISLS_URTC_FAMILY_
+    return false;
+}
+
+// The program of (model, cost, dtype), compiled on first use: its text, its file name and its name expressions in order --
+// lin, loop, step, rollouts for a model alone; exp, val, rollouts (none without a model) for a cost.  The compiler's messages go
+// to the cost's log, to the model's when there is no cost.  ISLS_ERR_ARG: no such source, or a model and a cost of different
+// dimensions; ISLS_ERR_UNSUPPORTED: a built-in model with no family for the cost's dimensions.
+int program(int model, int cost, int dtype, Program **out)
+{
+    Source *um = is_user_model(model) ? find(KIND_MODEL, model) : nullptr, *uc = cost != kNone ? find(KIND_COST, cost) : nullptr;
+    if ((is_user_model(model) && !um) || (cost != kNone && !uc) || (!um && !uc)) return ISLS_ERR_ARG;
+    if (um && uc && (um->n != uc->n || um->m != uc->m)) return ISLS_ERR_ARG;
+    const int n = uc ? uc->n : um->n, m = uc ? uc->m : um->m;
+    int mdlw = 0;
+    if (!um && model != kNone && !builtin_family(n, m, model, &mdlw)) return ISLS_ERR_UNSUPPORTED;
+    Program &pg = g_prog[std::make_tuple(cost, dtype, model)];
+    *out = &pg;
+    if (pg.tried) return pg.ok ? ISLS_OK : ISLS_ERR_COMPILE;
+    const std::string T = dtype == ISLS_DTYPE_F64 ? "double" : "float", dims = std::to_string(n) + ", " + std::to_string(m);
+    const std::string tmodel = std::to_string(um ? ISLS_MODEL_USER : model);   // the MODEL template argument
+    if (uc)
+        pg.names = {"isls::user_expand_kernel<" + T + ", " + dims + ">", "isls::user_cost_value_kernel<" + T + ", " + dims + ">"};
+    else
+        pg.names = {"isls::user_linearize_kernel<" + T + ", " + dims + ">",
+                    "isls::dense_closed_loop_kernel<" + T + ", " + dims + ", " + tmodel + ">",
+                    "isls::user_step_kernel<" + T + ", " + dims + ">"};
+    pg.ro0 = (int)pg.names.size();
+    pg.mdlw = mdlw;
+    pg.ro.clear();
+    if (model != kNone) {
+#define ISLS_URTC_VARIANTS_(NX_, NU_) if (n == NX_ && m == NU_) ro_variants<NX_, NU_>(pg.ro);
+        ISLS_FOR_EACH_DIMS(ISLS_URTC_VARIANTS_)
+#undef ISLS_URTC_VARIANTS_
+    }
+    for (const auto &jo : pg.ro)
+        pg.names.push_back("isls::rollout_kernel<" + T + ", " + dims + ", " + tmodel + ", " + std::to_string(jo.first) + ", " +
+                           std::to_string(jo.second) + ">");
+    std::string src = uc ? "#include \"user_cost_ad.hpp\"\n" : "#include \"user_model_ad.hpp\"\n";
+    if (um) src += wrap_source("isls_user", "user_model", um->source) + "#define ISLS_USER_NPAR " + std::to_string(um->npar) + "\n";
+    if (uc) src += wrap_source("isls_user_cost", "user_cost", uc->source) + "#define ISLS_USER_COST_NPAR " + std::to_string(uc->npar) + "\n";
+    src += uc ? "#include \"user_cost.hpp\"\n" : "#include \"user_model.hpp\"\n";
+    return compile_program(src, uc ? "user_cost.hip" : "user_model.hip", pg, (uc ? uc : um)->log);
+}
+
+bool dtype_ok(int dtype) { return dtype == ISLS_DTYPE_F64 || dtype == ISLS_DTYPE_F32; }
+
+}  // namespace
+
+// ---- what user_model.hip and user_cost.hip build their entry points and launches from ------------------------------------------
+int create(Kind kind, const char *source, int n, int m, int n_par, int32_t *id)
+{
+    if (!source || !id) return ISLS_ERR_ARG;
+    if (!dims_supported(n, m) || n_par < 0 || n_par > ISLS_USER_MAX_PAR) return ISLS_ERR_UNSUPPORTED;
+    auto src = std::make_unique<Source>();
+    src->source = source; src->n = n; src->m = m; src->npar = n_par;
+    if (refused_source(src->source)) return ISLS_ERR_ARG;     // plain arithmetic: no hand-written ISA through this door
+    std::lock_guard<std::mutex> lk(g_mu);
+    *id = (kind == KIND_MODEL ? ISLS_MODEL_USER_BASE : ISLS_COST_USER_BASE) + (int32_t)g_src[kind].size();
+    g_src[kind].push_back(std::move(src));
+    Program *pg;                                             // fp64 at once: every operation of the source meets the compiler
+    return kind == KIND_MODEL ? program(*id, kNone, ISLS_DTYPE_F64, &pg) : program(kNone, *id, ISLS_DTYPE_F64, &pg);
+}
+
+int64_t copy_log(Kind kind, int id, char *buf, int64_t len)
+{
+    std::lock_guard<std::mutex> lk(g_mu);
+    const Source *src = find(kind, id);
+    if (!src) return ISLS_ERR_ARG;
+    if (buf && len > 0) {
+        const size_t k = src->log.size() < (size_t)(len - 1) ? src->log.size() : (size_t)(len - 1);
+        memcpy(buf, src->log.data(), k);
+        buf[k] = '\0';
+    }
+    return (int64_t)src->log.size();
+}
+
+int copy_code(int model, int cost, int dtype, void *buf, int64_t *len)
+{
+    if (!len || !dtype_ok(dtype)) return ISLS_ERR_ARG;
+    std::lock_guard<std::mutex> lk(g_mu);
+    Program *pg;
+    const int rc = program(model, cost, dtype, &pg);
+    if (rc != ISLS_OK) return rc;
+    const int64_t cap = *len;
+    *len = (int64_t)pg->code.size();
+    if (buf) {
+        if (cap < *len) return ISLS_ERR_ARG;
+        memcpy(buf, pg->code.data(), pg->code.size());
+    }
+    return ISLS_OK;
+}
+
+int load(int model, int cost, int dtype)
+{
+    if (!dtype_ok(dtype)) return ISLS_ERR_ARG;
+    std::lock_guard<std::mutex> lk(g_mu);
+    Program *pg;
+    const int rc = program(model, cost, dtype, &pg);
+    return rc != ISLS_OK ? rc : load_program(*pg, nullptr, nullptr);
+}
+
+int dims(Kind kind, int id, int *n, int *m)
+{
+    std::lock_guard<std::mutex> lk(g_mu);
+    const Source *src = find(kind, id);
+    if (!src) return ISLS_ERR_ARG;
+    *n = src->n; *m = src->m;
+    return ISLS_OK;
+}
+
+int prepare(int model, int cost, int dtype, int n, int m, hipStream_t s, const std::vector<hipFunction_t> **fns, const Program **out)
+{
+    std::lock_guard<std::mutex> lk(g_mu);
+    const Source *src = cost != kNone ? find(KIND_COST, cost) : find(KIND_MODEL, model);
+    if (!src || src->n != n || src->m != m) return ISLS_ERR_ARG;
+    if (model == kNone) {
+        // expansion / value: every program of the cost holds them.  One that is on this device already serves (the pair the
+        // engine loaded); the cost's own program is compiled only when there is no such pair
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess) return ISLS_ERR_LAUNCH;
+        for (auto it = g_prog.lower_bound(std::make_tuple(cost, dtype, kNone)); it != g_prog.end(); ++it) {
+            if (std::get<0>(it->first) != cost || std::get<1>(it->first) != dtype) break;
+            if (it->second.ok && it->second.dev.count(dev)) { model = std::get<2>(it->first); break; }
+        }
+    }
+    Program *pg;
+    const int rc = program(model, cost, dtype, &pg);
+    if (rc != ISLS_OK) return rc;
+    if (out) *out = pg;
+    return load_program(*pg, fns, s);
+}
+
+int launch(hipFunction_t f, int grid, size_t smem, hipStream_t s, void **args)
+{
+    if (grid <= 0) return ISLS_OK;
+    return hipModuleLaunchKernel(f, grid, 1, 1, 64, 1, 1, (unsigned)smem, s, args, nullptr) == hipSuccess ? ISLS_OK : ISLS_ERR_LAUNCH;
+}
+
+}  // namespace urtc
+
+// ---- the line search of every key (dispatched from rollout.hip on a user model or a user cost) ---------------------------------
+template <typename T>
+int launch_rollout_user(RoP<T> &p, const isls_rollout_args &a, hipStream_t s, bool want_fused)
+{
+    const bool ucost = is_user_cost(a.cost_model);
+    if (ucost && (!a.cost_par || a.cost_par_sb < 0)) return ISLS_ERR_ARG;
+    const urtc::Program *pg;
+    const std::vector<hipFunction_t> *fns;
+    int rc = urtc::prepare(a.model, ucost ? a.cost_model : urtc::kNone, urtc::dtype_of<T>(), a.n, a.m, s, &fns, &pg);
+    if (rc != ISLS_OK) return rc;
+    if (ucost) p.cpar_sb = a.cost_par_sb;
+    RoLaunch pl;
+    rc = ISLS_ERR_UNSUPPORTED;
+    // the model enters the plan through its LDS words only (a dense LTI model's [A B]; none for the others and for user models)
+#define ISLS_URTC_PLAN_(NX_, NU_)                                                                              \
+    if (a.n == NX_ && a.m == NU_)                                                                              \
+        rc = pg->mdlw ? plan_rollout<T, NX_, NU_, NX_ * (NX_ + NU_)>(p, a, want_fused, nullptr, pl)            \
+                      : plan_rollout<T, NX_, NU_, 0>(p, a, want_fused, nullptr, pl);
+    ISLS_FOR_EACH_DIMS(ISLS_URTC_PLAN_)
+#undef ISLS_URTC_PLAN_
+    if (rc != ISLS_OK) return rc;
+    for (size_t i = 0; i < pg->ro.size(); ++i)
+        if (pg->ro[i].first == pl.jm && pg->ro[i].second == pl.occ) {
+            void *args[] = {&p};
+            return urtc::launch((*fns)[pg->ro0 + i], pl.grid, pl.smem, s, args);
+        }
+    return ISLS_ERR_UNSUPPORTED;
+}
+template int launch_rollout_user<double>(RoP<double> &, const isls_rollout_args &, hipStream_t, bool);
+template int launch_rollout_user<float>(RoP<float> &, const isls_rollout_args &, hipStream_t, bool);
+
+}  // namespace isls

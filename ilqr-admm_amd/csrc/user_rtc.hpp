@@ -1,5 +1,8 @@
-// user_rtc.hpp -- what the run-time compiled pieces share (user_model.hip implements it; user_cost.hip uses it too): one hiprtc
-// program per dtype with its name expressions, its code object and its module per device, and the module launcher.
+// user_rtc.hpp -- the host of the run-time compiled pieces (user_rtc.hip): the registry of user sources (models and costs), the
+// cache of their hiprtc programs and the module launcher.  A program is keyed by (model, cost, dtype): the model slot is a
+// built-in id, a user model or kNone, the cost slot a user cost or kNone.  (user model, kNone) is the model's own program
+// (user_model.hip launches its kernels), (kNone, cost) the cost's expansion and value (user_cost.hip), and a key with both slots
+// filled is the line search of that pair, which launch_rollout_user (rollout_kernel.hpp) serves for every key.
 #pragma once
 
 #include <map>
@@ -12,48 +15,33 @@
 namespace isls {
 namespace urtc {
 
-struct Program {                                             // one dtype of a model, or of a (cost, model) pair
+enum Kind { KIND_MODEL = 0, KIND_COST = 1 };                 // ids count from ISLS_{MODEL,COST}_USER_BASE per kind: every lookup takes it
+constexpr int kNone = -1;                                    // the empty slot of a key
+
+struct Program {                                             // one key: a model, a cost, or a (model, cost) pair in one dtype
     bool tried = false, ok = false;
     std::vector<char> code;
     std::vector<std::string> names, lowered;                 // name expressions and their mangled names
-    std::vector<std::pair<int, int>> ro;                     // (JM, OCC) of the rollout variants among the names
+    int ro0 = 0, mdlw = 0;                                   // index of the first rollout variant; LDS words of the model (plan_rollout)
+    std::vector<std::pair<int, int>> ro;                     // (JM, OCC) of the rollout variants: names[ro0 + i]
     std::map<int, std::pair<hipModule_t, std::vector<hipFunction_t>>> dev;   // device -> module, functions
 };
 
-// the (JM, OCC) variants the launch plan of these dimensions can pick
-template <int NX, int NU>
-void ro_variants(std::vector<std::pair<int, int>> &v)
-{
-    for (int occ = 2; occ >= 1; --occ)
-        for (int i = 0; i < (occ == 2 ? 3 : 4); ++i) {
-            const std::pair<int, int> jo(ro_jm_variant<NX, NU>(occ, i), occ);
-            bool seen = false;
-            for (const auto &e : v) seen = seen || e == jo;
-            if (!seen) v.push_back(jo);
-        }
-}
-inline void ro_variants_of(int n, int m, std::vector<std::pair<int, int>> &v)
-{
-    v.clear();
-#define ISLS_URTC_VARIANTS_(NX_, NU_) if (n == NX_ && m == NU_) ro_variants<NX_, NU_>(v);
-    ISLS_FOR_EACH_DIMS(ISLS_URTC_VARIANTS_)
-#undef ISLS_URTC_VARIANTS_
-}
-
-// a user source is plain arithmetic: true when it holds `asm` (any spelling) or `__builtin_amdgcn`
-bool refused_source(const std::string &src);
-// `body` inside `namespace ns`, every function of it always_inline (a call that is not inlined would take its arrays through
-// scratch memory), compiler messages pointing at `label`:<line of the user's text>
-std::string wrap_source(const std::string &ns, const std::string &label, const std::string &body);
-// Compile `src` (file name `file` in the messages) for gfx950 with pg.names as name expressions, with the flags of the library's
-// own kernels; fills pg.code / pg.lowered, appends the compiler's log to `log`.  Once per Program (pg.tried).
-int compile_program(const std::string &src, const char *file, Program &pg, std::string &log);
-// the program's functions (index: pg.names) on the current device, loaded on first use -- never inside a stream capture
-// (capture_check: the stream to test, or nullptr)
-int load_program(Program &pg, const std::vector<hipFunction_t> **out, hipStream_t capture_check);
+// isls_user_{model,cost}_create: register `source` (an id is assigned even when the compile fails) and compile its own program
+// (the model's, or the cost's expansion and value) for fp64
+int create(Kind kind, const char *source, int n, int m, int n_par, int32_t *id);
+// isls_user_*_log / _code / _load: the compiler's messages for a source so far; the code object of a key, compiled on first use;
+// the same loaded onto the current device
+int64_t copy_log(Kind kind, int id, char *buf, int64_t len);
+int copy_code(int model, int cost, int dtype, void *buf, int64_t *len);
+int load(int model, int cost, int dtype);
+int dims(Kind kind, int id, int *n, int *m);                 // ISLS_ERR_ARG: no such id
+// The functions (index: pg.names) of the key's program for a launch of dims (n, m) on the current device: compiled and loaded on
+// first use -- never inside a capture of stream `s`.  (kNone, cost) asks for the expansion and the value, which every program
+// of the cost holds: one that is on this device already serves, the cost's own program is compiled only when there is none.
+int prepare(int model, int cost, int dtype, int n, int m, hipStream_t s, const std::vector<hipFunction_t> **fns,
+            const Program **pg = nullptr);
 int launch(hipFunction_t f, int grid, size_t smem, hipStream_t s, void **args);
-// a registered user model (ISLS_ERR_ARG: no such id)
-int user_model_info(int id, std::string *source, int *n, int *m, int *npar);
 
 template <typename T>
 constexpr int dtype_of() { return sizeof(T) == 8 ? ISLS_DTYPE_F64 : ISLS_DTYPE_F32; }

@@ -283,105 +283,94 @@ def supported_dims(n_max=16, m_max=8):
 
 
 # ------------------------------------------------------------------------------------------------
-# user models: run-time compiled forward models (isls_user_model_*)
+# user models and user costs: run-time compiled sources (isls_user_model_*, isls_user_cost_*)
 # ------------------------------------------------------------------------------------------------
-_USER_MODELS = {}            # (source, n, m, P) -> id: one compile per process
+def _dtype_code(dtype):
+    return DTYPE_F32 if dtype in (np.float32, "f32") or (torch is not None and dtype == torch.float32) else DTYPE_F64
 
 
-def user_model_log(model_id):
-    lib = library()
-    size = lib.isls_user_model_log(C.c_int32(model_id), None, 0)
-    buf = C.create_string_buffer(int(max(size, 0)) + 1)
-    lib.isls_user_model_log(C.c_int32(model_id), buf, len(buf))
-    return buf.value.decode(errors="replace")
+class _UserKind:
+    """The four entry points of one kind of source (`noun`: model | cost).  A cost's code and load also take the model it is
+    paired with (-1: expansion and value only); ids of the two kinds count independently from `base`."""
+
+    def __init__(self, noun, base):
+        self.noun, self.base, self.ids = noun, base, {}      # ids: (source, n, m, P) -> id, one registration per process
+
+    def _fn(self, what):
+        return getattr(library(), f"isls_user_{self.noun}_{what}")
+
+    def _fail(self, what, rc, uid):
+        return IslsError(f"isls_user_{self.noun}_{what} -> {rc}: {library().isls_error_string(rc).decode()}\n{self.log(uid)}")
+
+    def log(self, uid):
+        size = self._fn("log")(C.c_int32(uid), None, 0)
+        buf = C.create_string_buffer(int(max(size, 0)) + 1)
+        self._fn("log")(C.c_int32(uid), buf, len(buf))
+        return buf.value.decode(errors="replace")
+
+    def create(self, source, n, m, n_par):
+        key = (str(source), int(n), int(m), int(n_par))
+        if key in self.ids:
+            return self.ids[key]
+        uid = C.c_int32(-1)
+        rc = self._fn("create")(key[0].encode(), key[1], key[2], key[3], C.byref(uid))
+        if rc == ERR_COMPILE:
+            raise IslsError(f"user {self.noun}: compile failed\n{self.log(uid.value) if uid.value >= self.base else ''}")
+        if rc != OK:
+            raise IslsError(f"isls_user_{self.noun}_create -> {rc}: {library().isls_error_string(rc).decode()}")
+        self.ids[key] = uid.value
+        return uid.value
+
+    def code(self, uid, *model, dtype):
+        args, size = [C.c_int32(v) for v in (uid,) + model] + [_dtype_code(dtype)], C.c_int64(0)
+        rc = self._fn("code")(*args, None, C.byref(size))
+        if rc == OK:
+            buf = C.create_string_buffer(size.value)
+            rc = self._fn("code")(*args, buf, C.byref(size))
+        if rc != OK:
+            raise self._fail("code", rc, uid)
+        return buf.raw
+
+    def load(self, uid, *model, dtype):
+        rc = self._fn("load")(*[C.c_int32(v) for v in (uid,) + model], _dtype_code(dtype))
+        if rc != OK:
+            raise self._fail("load", rc, uid)
+
+
+_USER_MODEL, _USER_COST = _UserKind("model", MODEL_USER_BASE), _UserKind("cost", COST_USER_BASE)
+user_model_log, user_cost_log = _USER_MODEL.log, _USER_COST.log
 
 
 def user_model_create(source, n, m, n_par):
     """Compile a user model for gfx950 (fp64 at once, fp32 on first use) and return its id; the same (source, n, m, n_par)
     is compiled once per process.  IslsError carries the compile log."""
-    key = (str(source), int(n), int(m), int(n_par))
-    if key in _USER_MODELS:
-        return _USER_MODELS[key]
-    lib, mid = library(), C.c_int32(-1)
-    rc = lib.isls_user_model_create(key[0].encode(), key[1], key[2], key[3], C.byref(mid))
-    if rc == ERR_COMPILE:
-        raise IslsError(f"user model: compile failed\n{user_model_log(mid.value) if mid.value >= MODEL_USER_BASE else ''}")
-    if rc != OK:
-        raise IslsError(f"isls_user_model_create -> {rc}: {lib.isls_error_string(rc).decode()}")
-    _USER_MODELS[key] = mid.value
-    return mid.value
-
-
-def _dtype_code(dtype):
-    return DTYPE_F32 if dtype in (np.float32, "f32") or (torch is not None and dtype == torch.float32) else DTYPE_F64
+    return _USER_MODEL.create(source, n, m, n_par)
 
 
 def user_model_code(model_id, dtype=np.float64):
     """The model's gfx950 code object (a bare ELF) for dtype."""
-    lib, size = library(), C.c_int64(0)
-    rc = lib.isls_user_model_code(C.c_int32(model_id), _dtype_code(dtype), None, C.byref(size))
-    if rc == OK:
-        buf = C.create_string_buffer(size.value)
-        rc = lib.isls_user_model_code(C.c_int32(model_id), _dtype_code(dtype), buf, C.byref(size))
-    if rc != OK:
-        raise IslsError(f"isls_user_model_code -> {rc}\n{user_model_log(model_id)}")
-    return buf.raw
+    return _USER_MODEL.code(model_id, dtype=dtype)
 
 
 def user_model_load(model_id, dtype=np.float64):
     """Load the model's module onto the current device (outside any stream capture)."""
-    rc = library().isls_user_model_load(C.c_int32(model_id), _dtype_code(dtype))
-    if rc != OK:
-        raise IslsError(f"isls_user_model_load -> {rc}\n{user_model_log(model_id)}")
-
-
-# ------------------------------------------------------------------------------------------------
-# user costs: run-time compiled cost functions (isls_user_cost_*)
-# ------------------------------------------------------------------------------------------------
-_USER_COSTS = {}             # (source, n, m, P) -> id: one registration per process
-
-
-def user_cost_log(cost_id):
-    lib = library()
-    size = lib.isls_user_cost_log(C.c_int32(cost_id), None, 0)
-    buf = C.create_string_buffer(int(max(size, 0)) + 1)
-    lib.isls_user_cost_log(C.c_int32(cost_id), buf, len(buf))
-    return buf.value.decode(errors="replace")
+    _USER_MODEL.load(model_id, dtype=dtype)
 
 
 def user_cost_create(source, n, m, n_par):
     """Register a user cost and compile its expansion and value for gfx950 (fp64; the line-search kernels are compiled per model
     it is used with); the same (source, n, m, n_par) is registered once per process.  IslsError carries the compile log."""
-    key = (str(source), int(n), int(m), int(n_par))
-    if key in _USER_COSTS:
-        return _USER_COSTS[key]
-    lib, cid = library(), C.c_int32(-1)
-    rc = lib.isls_user_cost_create(key[0].encode(), key[1], key[2], key[3], C.byref(cid))
-    if rc == ERR_COMPILE:
-        raise IslsError(f"user cost: compile failed\n{user_cost_log(cid.value) if cid.value >= COST_USER_BASE else ''}")
-    if rc != OK:
-        raise IslsError(f"isls_user_cost_create -> {rc}: {lib.isls_error_string(rc).decode()}")
-    _USER_COSTS[key] = cid.value
-    return cid.value
+    return _USER_COST.create(source, n, m, n_par)
 
 
 def user_cost_code(cost_id, model=-1, dtype=np.float64):
     """The gfx950 code object (a bare ELF) of the cost with `model` (a model id; -1: expansion and value only) for dtype."""
-    lib, size = library(), C.c_int64(0)
-    rc = lib.isls_user_cost_code(C.c_int32(cost_id), C.c_int32(model), _dtype_code(dtype), None, C.byref(size))
-    if rc == OK:
-        buf = C.create_string_buffer(size.value)
-        rc = lib.isls_user_cost_code(C.c_int32(cost_id), C.c_int32(model), _dtype_code(dtype), buf, C.byref(size))
-    if rc != OK:
-        raise IslsError(f"isls_user_cost_code -> {rc}: {lib.isls_error_string(rc).decode()}\n{user_cost_log(cost_id)}")
-    return buf.raw
+    return _USER_COST.code(cost_id, model, dtype=dtype)
 
 
 def user_cost_load(cost_id, model=-1, dtype=np.float64):
     """Compile (if need be) and load the module of the cost with `model` onto the current device (outside any stream capture)."""
-    rc = library().isls_user_cost_load(C.c_int32(cost_id), C.c_int32(model), _dtype_code(dtype))
-    if rc != OK:
-        raise IslsError(f"isls_user_cost_load -> {rc}: {library().isls_error_string(rc).decode()}\n{user_cost_log(cost_id)}")
+    _USER_COST.load(cost_id, model, dtype=dtype)
 
 
 def _cost_par(cost_model, cost_par, B):

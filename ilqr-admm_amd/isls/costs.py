@@ -8,11 +8,10 @@ line search of whichever model it is used with, plus an expansion on second-orde
 `iSLS.cost_function` selects ISLS_COST_PHUBER on the device; the object itself is the numpy version of the same cost
 (and of its derivatives, which the notebook gets from autograd) for use on the host and in tests.
 """
-import re
-
 import numpy as np
 
 from . import _capi as capi
+from .models import UserSource
 
 
 class PseudoHuber:
@@ -56,7 +55,7 @@ class PseudoHuber:
         return cs, Cs
 
 
-class Custom:
+class Custom(UserSource):
     """A cost of the user's own: `source` defines
 
         template <typename S, typename P>
@@ -71,23 +70,7 @@ class Custom:
     Only the (x_dim, u_dim) pairs with the row-per-lane kernels are served (`isls._capi.supported_dims()`)."""
 
     def __init__(self, x_dim, u_dim, params, source):
-        self.x_dim, self.u_dim = int(x_dim), int(u_dim)
-        self._params = np.atleast_1d(np.asarray(params, dtype=np.float64))
-        if self._params.ndim > 2:
-            raise ValueError("params: [P] or [B, P]")
-        P = self._params.shape[-1]
-        if P > capi.USER_MAX_PAR:
-            raise capi.IslsError(f"a user cost takes at most {capi.USER_MAX_PAR} parameters, got {P}")
-        if not capi.dims_supported(self.x_dim, self.u_dim):
-            raise capi.IslsError(f"user costs need one of the (x_dim, u_dim) pairs with the row-per-lane kernels "
-                                 f"{capi.supported_dims()}, got ({self.x_dim}, {self.u_dim})")
-        if re.search(r"\b(asm|__asm|__asm__)\b", source) or "__builtin_amdgcn" in source:
-            raise capi.IslsError("a user cost is plain arithmetic: `asm` and `__builtin_amdgcn_*` are not accepted")
-        self.source = source
-        self.cost_model = capi.user_cost_create(source, self.x_dim, self.u_dim, P)
-
-    def params(self):
-        return self._params
+        self.cost_model = self._register("cost", capi.user_cost_create, x_dim, u_dim, params, source)
 
     def code(self, model=None, dtype=np.float64):
         """The gfx950 code object of the cost for dtype: with `model` (an isls.models object or a model id) every kernel of the
@@ -95,22 +78,18 @@ class Custom:
         mid = -1 if model is None else int(getattr(model, "model_id", model))
         return capi.user_cost_code(self.cost_model, mid, dtype)
 
+    def _load(self, dtype):
+        capi.user_cost_load(self.cost_model, -1, dtype)
+
     def _batch(self, x, u):
-        import torch
-        from .engine import kernels
         x, u = np.asarray(x, dtype=np.float64), np.asarray(u, dtype=np.float64)
         lead = np.broadcast_shapes(x.shape[:-2], u.shape[:-2])
         N = x.shape[-2]
         R = int(np.prod(lead)) if lead else 1
-        par = self._params
-        if par.ndim == 2 and par.shape[0] != R:
-            raise ValueError(f"per-trajectory params [{par.shape[0]}, P] need {par.shape[0]} trajectories x, u, got {R}")
-        dev = torch.device("cuda", torch.cuda.current_device())
-        t = lambda a: torch.as_tensor(np.array(a, dtype=np.float64, order="C"), device=dev)   # noqa: E731
-        xs = t(np.broadcast_to(x, lead + (N, self.x_dim)).reshape(R, N, self.x_dim))
-        us = t(np.broadcast_to(u, lead + (N, self.u_dim)).reshape(R, N, self.u_dim))
-        capi.user_cost_load(self.cost_model, -1, np.float64)
-        return torch, kernels(), lead, R, N, xs, us, t(par), dev
+        torch, kern, dev, (par, xs, us) = self._on_device(R, "{0} trajectories x, u, got {1}",
+                                                           np.broadcast_to(x, lead + (N, self.x_dim)).reshape(R, N, self.x_dim),
+                                                           np.broadcast_to(u, lead + (N, self.u_dim)).reshape(R, N, self.u_dim))
+        return torch, kern, lead, R, N, xs, us, par, dev
 
     def __call__(self, x, u):
         """x [..., N, n], u [..., N, m] -> cost [...] (numpy, fp64), evaluated on the device."""

@@ -563,34 +563,24 @@ class Engine:
         if linearize and self.use_model_structure and self._ab_src == STATIC:
             linearize = False                                  # the model's one linearisation is in place: nothing to rewrite
         key = (float(tol_cost), float(tol_osc), bool(linearize))
-        if self.user_cost:
-            # the advance launch without its fused expansion; the user expansion follows on the same stream for the trajectories
-            # still iterating (outer_active after the stop rules), about the nominal just written
-            if self._advance_args is None or self._advance_args[0] != key:
-                acc = K.accept_args(self.xx, self.xu, self.cost_new, self.xhat, self.uhat, self.cost, cost_hist=self.cost_hist,
-                                    hist_len=self.hist_len, tol_cost=tol_cost, tol_osc=tol_osc, outer_active=self.outer_active)
-                lin = K.linearize_args(self.model, self.model_par, self.xhat, self.uhat, self.A, self.Bm) if linearize else None
-                self._advance_args = (key, K.advance_args(acc, lin, None, admm_active=self.admm_active, iters=self.admm_iters,
-                                                          lx=self.lx, lu=self.lu, res_prev=self.res_prev),
-                                      self._expand_block(True, self.outer_active))
-            self.kern.outer_advance(self._advance_args[1], self.sfx, stream=_stream_ptr())
-            self.kern.user_cost_expand(self._advance_args[2], self.Cux, self.sfx, stream=_stream_ptr())
-            if linearize and self._ab_src != STATIC:
-                self._ab_src = LINEARIZED
-            return
         if self._advance_args is None or self._advance_args[0] != key:
-            if not self._shared_hessian():
-                raise capi.IslsError("Engine.advance() serves the batch-shared cost Hessians; use accept_x_step / linearize / expand")
-            if self._hess_dirty:
-                self.expand()                                  # writes the shared Hessian tables once
+            if not self.user_cost:
+                if not self._shared_hessian():
+                    raise capi.IslsError("Engine.advance() serves the batch-shared cost Hessians; use accept_x_step / linearize / expand")
+                if self._hess_dirty:
+                    self.expand()                              # writes the shared Hessian tables once
             acc = K.accept_args(self.xx, self.xu, self.cost_new, self.xhat, self.uhat, self.cost, cost_hist=self.cost_hist,
                                 hist_len=self.hist_len, tol_cost=tol_cost, tol_osc=tol_osc, outer_active=self.outer_active)
             lin = K.linearize_args(self.model, self.model_par, self.xhat, self.uhat, self.A, self.Bm) if linearize else None
-            exp = K.expand_args(self.Qtab, self.ztab, self.seq, self.u_std, self.c0x, self.c0u, xhat=self.xhat, uhat=self.uhat,
-                                Qr=self.Qr, Rr=self.Rr, cost_model=self.cost_model, cost_par=self.cost_par, q_nonzero=self.q_nonzero)
+            # a built-in cost's expansion (gradients: the Hessians are the shared tables) is fused into the launch; a user cost's
+            # follows it on the same stream for the trajectories still iterating (outer_active after the stop rules), about the
+            # nominal just written
+            exp, after = (None, self._expand_block(True, self.outer_active)) if self.user_cost else (self._expand_block(False, None), None)
             self._advance_args = (key, K.advance_args(acc, lin, exp, admm_active=self.admm_active, iters=self.admm_iters,
-                                                      lx=self.lx, lu=self.lu, res_prev=self.res_prev))
+                                                      lx=self.lx, lu=self.lu, res_prev=self.res_prev), after)
         self.kern.outer_advance(self._advance_args[1], self.sfx, stream=_stream_ptr())
+        if self._advance_args[2] is not None:
+            self.kern.user_cost_expand(self._advance_args[2], self.Cux, self.sfx, stream=_stream_ptr())
         if linearize and self._ab_src != STATIC:
             self._ab_src = LINEARIZED                          # the launch linearised the trajectories still iterating
 

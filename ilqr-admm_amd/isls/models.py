@@ -167,7 +167,43 @@ class TassaCar(Model):
         return A, B
 
 
-class Custom(Model):
+class UserSource:
+    """What models.Custom and costs.Custom share: the validation and registration of a run-time compiled source (`noun`: model |
+    cost) and the way their host-side evaluations put numpy arrays on the device."""
+
+    def _register(self, noun, create, x_dim, u_dim, params, source):
+        self.x_dim, self.u_dim = int(x_dim), int(u_dim)
+        self._params = np.atleast_1d(np.asarray(params, dtype=np.float64))
+        if self._params.ndim > 2:
+            raise ValueError("params: [P] or [B, P]")
+        P = self._params.shape[-1]
+        if P > capi.USER_MAX_PAR:
+            raise capi.IslsError(f"a user {noun} takes at most {capi.USER_MAX_PAR} parameters, got {P}")
+        if not capi.dims_supported(self.x_dim, self.u_dim):
+            raise capi.IslsError(f"user {noun}s need one of the (x_dim, u_dim) pairs with the row-per-lane kernels "
+                                 f"{capi.supported_dims()}, got ({self.x_dim}, {self.u_dim})")
+        if re.search(r"\b(asm|__asm|__asm__)\b", source) or "__builtin_amdgcn" in source:
+            raise capi.IslsError(f"a user {noun} is plain arithmetic: `asm` and `__builtin_amdgcn_*` are not accepted")
+        self.source = source
+        return create(source, self.x_dim, self.u_dim, P)
+
+    def params(self):
+        return self._params
+
+    def _on_device(self, rows, need, *arrays):
+        """(torch, kernels, device, [parameters, *arrays] as fp64 device tensors) for an evaluation of `rows` trajectories on the
+        current device, the module put there by _load(); per-trajectory parameters need one row each (`need`: the error's words)."""
+        import torch
+        from .engine import kernels
+        par = self._params
+        if par.ndim == 2 and par.shape[0] != rows:
+            raise ValueError(f"per-trajectory params [{par.shape[0]}, P] need " + need.format(par.shape[0], rows))
+        dev = torch.device("cuda", torch.cuda.current_device())
+        self._load(np.float64)
+        return torch, kernels(), dev, [torch.as_tensor(np.array(a, dtype=np.float64, order="C"), device=dev) for a in (par,) + arrays]
+
+
+class Custom(UserSource, Model):
     """A forward model of the user's own: `source` defines
 
         template <typename S, typename P>
@@ -180,68 +216,37 @@ class Custom(Model):
     Only the (x_dim, u_dim) pairs with the row-per-lane kernels are served (`isls._capi.supported_dims()`)."""
 
     def __init__(self, x_dim, u_dim, params, source):
-        self.x_dim, self.u_dim = int(x_dim), int(u_dim)
-        self._params = np.atleast_1d(np.asarray(params, dtype=np.float64))
-        if self._params.ndim > 2:
-            raise ValueError("params: [P] or [B, P]")
-        P = self._params.shape[-1]
-        if P > capi.USER_MAX_PAR:
-            raise capi.IslsError(f"a user model takes at most {capi.USER_MAX_PAR} parameters, got {P}")
-        if not capi.dims_supported(self.x_dim, self.u_dim):
-            raise capi.IslsError(f"user models need one of the (x_dim, u_dim) pairs with the row-per-lane kernels "
-                                 f"{capi.supported_dims()}, got ({self.x_dim}, {self.u_dim})")
-        if re.search(r"\b(asm|__asm|__asm__)\b", source) or "__builtin_amdgcn" in source:
-            raise capi.IslsError("a user model is plain arithmetic: `asm` and `__builtin_amdgcn_*` are not accepted")
-        self.source = source
-        self.model_id = capi.user_model_create(source, self.x_dim, self.u_dim, P)
-
-    def params(self):
-        return self._params
+        self.model_id = self._register("model", capi.user_model_create, x_dim, u_dim, params, source)
 
     def code(self, dtype=np.float64):
         """The gfx950 code object of the model (all its kernels) for dtype."""
         return capi.user_model_code(self.model_id, dtype)
 
-    @staticmethod
-    def _device():
-        import torch
-        from .engine import kernels
-        return torch, kernels()
+    def _load(self, dtype):
+        capi.user_model_load(self.model_id, dtype)
 
     def __call__(self, x, u):
         """x [..., n], u [..., m] -> f(x, u) [..., n] (numpy, fp64), evaluated on the device."""
-        torch, kern = self._device()
         x, u = np.asarray(x, dtype=np.float64), np.asarray(u, dtype=np.float64)
         lead = np.broadcast_shapes(x.shape[:-1], u.shape[:-1])
         R = int(np.prod(lead)) if lead else 1
-        dev = torch.device("cuda", torch.cuda.current_device())
-        t = lambda a: torch.as_tensor(np.array(a, dtype=np.float64, order="C"), device=dev)   # noqa: E731
-        xs = t(np.broadcast_to(x, lead + (self.x_dim,)).reshape(R, self.x_dim))
-        us = t(np.broadcast_to(u, lead + (self.u_dim,)).reshape(R, self.u_dim))
-        par = self._params
-        if par.ndim == 2 and par.shape[0] != R:
-            raise ValueError(f"per-trajectory params [{par.shape[0]}, P] need {par.shape[0]} rows of x, u, got {R}")
+        torch, kern, dev, (par, xs, us) = self._on_device(R, "{0} rows of x, u, got {1}",
+                                                           np.broadcast_to(x, lead + (self.x_dim,)).reshape(R, self.x_dim),
+                                                           np.broadcast_to(u, lead + (self.u_dim,)).reshape(R, self.u_dim))
         xn = torch.empty(R, self.x_dim, dtype=torch.float64, device=dev)
-        capi.user_model_load(self.model_id, np.float64)
-        kern.user_model_step(self.model_id, t(par), xs, us, xn, stream=torch.cuda.current_stream().cuda_stream)
+        kern.user_model_step(self.model_id, par, xs, us, xn, stream=torch.cuda.current_stream().cuda_stream)
         return xn.cpu().numpy().reshape(lead + (self.x_dim,))
 
     def get_AB(self, x, u):
         """A [N,n,n], B [N,n,m] along x [N,n], u [N,m] in the reference's convention (or [Bt,N,...] for a batch), on the device
         by the same dual-number kernel the solver linearises with."""
-        torch, kern = self._device()
         x, u = np.asarray(x, dtype=np.float64), np.asarray(u, dtype=np.float64)
         single = x.ndim == 2
         xb, ub = (x[None], u[None]) if single else (x, u)
         Bt, N = xb.shape[:2]
-        par = self._params
-        if par.ndim == 2 and par.shape[0] != Bt:
-            raise ValueError(f"per-trajectory params [{par.shape[0]}, P] need x, u of [{par.shape[0]}, N, .]")
-        dev = torch.device("cuda", torch.cuda.current_device())
-        t = lambda a: torch.as_tensor(np.array(a, dtype=np.float64, order="C"), device=dev)   # noqa: E731
+        torch, kern, dev, (par, xs, us) = self._on_device(Bt, "x, u of [{0}, N, .]", xb, ub)
         A = torch.zeros(Bt, N, self.x_dim, self.x_dim, dtype=torch.float64, device=dev)
         Bm = torch.zeros(Bt, N, self.x_dim, self.u_dim, dtype=torch.float64, device=dev)
-        capi.user_model_load(self.model_id, np.float64)
-        kern.linearize(self.model_id, t(par), t(xb), t(ub), A, Bm, stream=torch.cuda.current_stream().cuda_stream)
+        kern.linearize(self.model_id, par, xs, us, A, Bm, stream=torch.cuda.current_stream().cuda_stream)
         A, Bm = A.cpu().numpy(), Bm.cpu().numpy()
         return (A[0], Bm[0]) if single else (A, Bm)

@@ -224,6 +224,61 @@ def test_line_search_via_point_restatement_on_the_arm(L):
     assert not torch.equal(ec.xx[replayed], ec.xhat[replayed])  # (and it is the winner, not the nominal handed back)
 
 
+def test_line_search_with_a_model_and_a_cost_of_the_same_id_number():
+    """A Custom car and the coupled cost registered under the same id number (the two kinds count their ids independently), fp64,
+    B = 5, N = 6, L = 20: three trajectories per wavefront, the second wavefront partial.  One launcher serves the three kinds
+    of program and picks each by (model, cost): (a) the Custom car with the via-point cost gives the built-in car's bits;
+    (c) the coupled cost with the Custom car gives the bits of (b) the coupled cost with the built-in car -- the same template
+    with the same arithmetic, on the same A, B and gains ((b)'s, copied).  (Measured with the two launchers this one replaced:
+    (c) and (b) bit-identical in best, xx, xu and cost_new, so bit identity is what is asserted.)"""
+    from isls import _capi as capi
+    from isls import iSLS, models
+    import isls_problems as P
+    B, N, L = 5, 6, 20
+    cfg = P.config4(batch=B, N=N, seed=0)
+    builtin = models.CarSimple(cfg["dt"])
+    custom, coupled = uc.same_id_pair((4, 2, [cfg["dt"]], um.CAR), (4, 2, uc.COUPLED_PAR, uc.coupled_source(4, 2)))
+    assert custom.model_id == coupled.cost_model
+    xs, us = (np.stack(v) for v in zip(*[P.initial_nominal(cfg, b) for b in range(B)]))
+
+    def search(model, cost, gains_of=None):
+        s = iSLS(4, 2, N, batch=B)
+        s.forward_model = model
+        s.set_cost_variables(cfg["zs"], cfg["Qs"], cfg["seq"], cfg["u_std"])
+        if cost is not None:
+            s.cost_function = cost
+        s.reset()
+        s.nominal_values = xs, us
+        e = s.engine
+        if gains_of is None:
+            s._linearize(lambda x, u: builtin.get_AB(x, u))     # (a callable: the host route, the same A, B for every side)
+            s._expand()
+            e.gain(active=e.outer_active)
+            e.feedforward(active=e.outer_active)
+        else:
+            share(gains_of, e, ("A", "Bm", "K", "k"))
+        e.rollout(L, flags=capi.RO_NAN_TO_1E5 | capi.RO_ACCEPT_TEST, active=e.outer_active)
+        torch.cuda.synchronize()
+        return e
+
+    def same_bits(ea, eb, what):
+        for k in ("best", "xx", "xu", "cost_new"):
+            a, b = getattr(ea, k), getattr(eb, k)
+            print(f"{what}: {k} differs by at most {(a.double() - b.double()).abs().max().item():.3e}")
+        for k in ("best", "xx", "xu", "cost_new"):
+            a, b = getattr(ea, k), getattr(eb, k)
+            assert torch.equal(a.view(torch.int64) if a.dtype == torch.float64 else a,
+                               b.view(torch.int64) if b.dtype == torch.float64 else b), (what, k)
+
+    e0, ea = search(builtin, None), search(custom, None)
+    eb = search(builtin, coupled)
+    ec = search(custom, coupled, gains_of=eb)
+    same_bits(ea, e0, "(a) Custom car, via-point cost, against the built-in car")
+    same_bits(ec, eb, "(c) coupled cost on the Custom car against (b) on the built-in car")
+    assert torch.isfinite(e0.xx).all() and torch.isfinite(eb.xx).all()
+    assert not torch.equal(eb.cost_new, e0.cost_new)           # (the two costs are two costs)
+
+
 def test_second_derivatives_of_every_operation():
     """Every second-order rule of the hyper-dual type (sin cos sqrt exp log tanh asin atan2 fabs, division, isls::sin_cos,
     isls::py_mod, compound assignment, mixed operands) on the device: the Hessian of a cost that uses them all against central

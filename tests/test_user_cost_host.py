@@ -5,6 +5,7 @@ error, and the numpy derivatives the GPU tests compare against agree with centra
 import ctypes
 import os
 import sys
+import threading
 
 import numpy as np
 import pytest
@@ -94,6 +95,58 @@ def test_one_registration_per_source():
     a = costs.Custom(4, 2, uc.COUPLED_PAR, uc.coupled_source(4, 2))
     b = costs.Custom(4, 2, np.tile(uc.COUPLED_PAR, (3, 1)), uc.coupled_source(4, 2))   # per-trajectory parameters: same program
     assert a.cost_model == b.cost_model
+
+
+def test_a_model_and_a_cost_of_the_same_id_number_are_told_apart():
+    """Ids count per kind, so a model and a cost share their number as a matter of course: every lookup goes by kind."""
+    warns = uc.coupled_source(4, 2).replace("S c = S(0), d2 = S(0);", "S c = S(0), d2 = S(0);\n    int narrowed = 1.5;")
+    mdl, cst = uc.same_id_pair((4, 2, [0.1], um.CAR), (4, 2, uc.COUPLED_PAR, warns))
+    uid = mdl.model_id
+    assert uid == cst.cost_model
+    lib = capi.load_hip_library()
+    logs = []
+    for fn in (lib.isls_user_model_log, lib.isls_user_cost_log):
+        buf = ctypes.create_string_buffer(fn(uid, None, 0) + 1)
+        fn(uid, buf, len(buf))
+        logs.append(buf.value.decode())
+    assert "user_cost:" in logs[1] and "warning" in logs[1] and "warning" not in logs[0]
+    assert logs == [capi.user_model_log(uid), capi.user_cost_log(uid)]
+    of_model, of_cost, of_pair = kernels_of(mdl.code()), kernels_of(cst.code()), kernels_of(cst.code(mdl))
+    has = lambda ks, name: any(k.startswith(f"_ZN4isls{len(name)}{name}I") for k in ks)   # noqa: E731
+    assert has(of_model, "user_linearize_kernel") and not has(of_model, "user_expand_kernel")
+    assert has(of_cost, "user_expand_kernel") and not has(of_cost, "user_linearize_kernel")
+    assert set(rollout_variants(of_pair, "d", 4, 2, 99)) == set(rollout_variants(of_model, "d", 4, 2, 99)) != set()
+    assert has(of_pair, "user_expand_kernel") and not has(of_pair, "user_linearize_kernel")
+    assert not rollout_variants(of_cost, "d", 4, 2, 99)
+
+
+def test_one_compile_per_key_under_concurrency():
+    """Four threads ask for the same (model, cost) program while a fifth registers models: one compile serves them all (the
+    compiler's warning enters the cost's log once per compile), and sources and programs being under one lock, it ends."""
+    warns = body("int narrowed = 1.5; return x[0] * u[1] + narrowed;")
+    cost = costs.Custom(4, 2, [0.1], uc.fresh(warns))
+    after_create = len(capi.user_cost_log(cost.cost_model))
+    assert after_create > 0
+    car, codes, ids = models.CarSimple(0.1), [None] * 4, []
+
+    def ask(k):
+        codes[k] = cost.code(car)
+
+    def register():
+        for _ in range(3):
+            ids.append(models.Custom(2, 1, [0.1], uc.fresh(um.Z21)).model_id)
+    threads = [threading.Thread(target=ask, args=(k,)) for k in range(4)] + [threading.Thread(target=register)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    assert codes[0][:4] == b"\x7fELF" and all(c == codes[0] for c in codes)
+    assert len(set(ids)) == 3
+    once = len(capi.user_cost_log(cost.cost_model))
+    assert once > after_create                                 # the pair's compile added its warning ...
+    assert cost.code(car) == codes[0]
+    assert len(capi.user_cost_log(cost.cost_model)) == once    # ... and a fifth, later call compiles nothing
+    assert once <= 2 * after_create + 64                       # one more compile's worth of messages, not four
 
 
 def body(text):

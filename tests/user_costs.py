@@ -1,7 +1,41 @@
 """Sources of user costs (isls.costs.Custom) shared by the user-cost tests and tools/user_cost_bench.py: the pseudo-Huber cost and
 a via-point cost restated as `stage` functions, and a coupled cost (x-u cross terms, an off-diagonal state Hessian, a terminal
 term) with its numpy value, gradient and Hessian written out by hand."""
+import ctypes
+import itertools
+
 import numpy as np
+
+_FRESH = itertools.count()
+
+
+def fresh(source):
+    """`source` with a trailing comment no other source of this process has: the same code under an id of its own (the binding
+    registers one text once)"""
+    return source + f"// registration {next(_FRESH)} of this process\n"
+
+
+def same_id_pair(model_args, cost_args):
+    """(models.Custom, costs.Custom) from (x_dim, u_dim, params, source) each, registered anew so that the model's id and the
+    cost's id are the same number.  The two kinds count their ids independently, and a source gets its id even when its compile
+    fails: the kind that is behind is padded with sources that stop the compiler at their first line."""
+    from isls import _capi as capi
+    from isls import costs, models
+    lib = capi.load_hip_library()
+
+    def pad(kind):
+        uid = ctypes.c_int32(-1)
+        rc = getattr(lib, f"isls_user_{kind}_create")(b'#include "no_such_header.hpp"\n', 2, 1, 0, ctypes.byref(uid))
+        assert rc == capi.ERR_COMPILE and uid.value >= 1024
+        return uid.value
+    last = {kind: pad(kind) for kind in ("model", "cost")}
+    behind = min(last, key=last.get)
+    while last[behind] < max(last.values()):
+        last[behind] = pad(behind)
+    mdl = models.Custom(*model_args[:3], fresh(model_args[3]))
+    cst = costs.Custom(*cost_args[:3], fresh(cost_args[3]))
+    assert mdl.model_id == cst.cost_model == last[behind] + 1
+    return mdl, cst
 
 
 def _lit(v):
