@@ -55,6 +55,17 @@ static int outer_iteration(const isls_outer_args &a, hipStream_t s)
     // the gain pass writes the records in the layout its hint selects and the feed-forward passes read them in theirs
     if (a.J > 0 && a.gain.rec && a.ff.rec == a.gain.rec && (a.gain.lin_on != 0) != (a.ff.lin_on != 0)) return ISLS_ERR_ARG;
     if (a.ff.lin_on && ff_seg_enabled(a.ff.seg)) return ISLS_ERR_UNSUPPORTED;   // the segment operators need the dense records
+    // One set of records for the whole batch (isls_gain_args.rec in include/isls_hip.h): the declared strides and hints say that
+    // every trajectory has the same A, B, Cxx, Cuu, Cux, this call's gain pass writes the records its own feed-forward passes and
+    // line searches read, the recursion is sequential, and all four blocks speak of the same batch and mask.  Then K_t and fac_t
+    // are the same for every trajectory: the gain pass writes them once, and the other passes read that one table (which stays
+    // in the caches) instead of a copy per trajectory.  The K array is still written for every trajectory.
+    const bool shared = a.J > 0 && !a.skip_gain && gain_inputs_shared(a.gain) && dims_supported(a.gain.n, a.gain.m) &&
+                        a.ff.rec == a.gain.rec && a.ff.lin_on && a.ff.lin_model == a.gain.lin_model && a.ff.lin_par_sb == 0 &&
+                        !ff_seg_enabled(a.ff.seg) && a.ff.B == a.gain.B && a.ff.N == a.gain.N && a.ff.n == a.gain.n &&
+                        a.ff.m == a.gain.m && a.ff.active == a.gain.active && a.ff._pad <= 1 && a.ro.B == a.gain.B &&
+                        a.ro.N == a.gain.N && a.ro.n == a.gain.n && a.ro.m == a.gain.m && a.ro.K == a.gain.K &&
+                        a.ro.active == a.gain.active;
     if (!a.skip_gain) {
         {
             ScopedTimer tm(tmg, 0, s);
@@ -70,7 +81,7 @@ static int outer_iteration(const isls_outer_args &a, hipStream_t s)
             const int lanes = a.gain.n + a.gain.m;
             const int64_t waves = lanes > 0 && lanes <= kWave ? (a.gain.B + kWave / lanes - 1) / (kWave / lanes) : 0;
             const bool fuse_now = a.J > 0 && waves <= simds;
-            if ((rc = launch_gain<T>(a.gain, s, fuse_now ? &a.ff : nullptr, &ff_done)) != ISLS_OK) return rc;
+            if ((rc = launch_gain<T>(a.gain, s, fuse_now ? &a.ff : nullptr, &ff_done, false, shared)) != ISLS_OK) return rc;
         }
         if (ff_seg_enabled(a.ff.seg)) {                        // operators of the time-parallel feed-forward pass
             const isls_ff_args &f = a.ff;
@@ -88,11 +99,11 @@ static int outer_iteration(const isls_outer_args &a, hipStream_t s)
     for (int j = 0; j < a.J; ++j) {
         if (!(j == 0 && ff_done)) {
             ScopedTimer tm(tmg, 1, s);
-            if ((rc = launch_ff<T>(a.ff, s)) != ISLS_OK) return rc;
+            if ((rc = launch_ff<T>(a.ff, s, shared)) != ISLS_OK) return rc;
         }
         {
             ScopedTimer tm(tmg, 2, s);
-            if ((rc = launch_rollout<T>(a.ro, s, fuse ? &a.admm : nullptr, &fused, j == a.J - 1 || a.log != nullptr)) != ISLS_OK) return rc;
+            if ((rc = launch_rollout<T>(a.ro, s, fuse ? &a.admm : nullptr, &fused, j == a.J - 1 || a.log != nullptr, shared ? a.gain.rec : nullptr)) != ISLS_OK) return rc;
         }
         if (!fused) {
             ScopedTimer tm(tmg, 3, s);

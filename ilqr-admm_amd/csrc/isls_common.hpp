@@ -228,13 +228,28 @@ __host__ __device__ constexpr int rec_stride(int n, int m) { return (n * n + 2 *
 // (the same buffer: isls_ff_record_elems covers the dense layout, the lean one uses a prefix of it).
 __host__ __device__ constexpr int rec_lean_stride(int n, int m) { return (m * n + m * m + rec_model_words(n, m) + 1) & ~1; }
 
+#ifndef __HIPCC_RTC__
+// Do all trajectories of the batch share the inputs of the gain recursion (A, B, Cxx, Cuu, Cux), as far as the strides and hints
+// of the argument block DECLARE it (addresses and values are never compared)?  Then K_t and fac_t are the same for all of them
+// and the outer driver keeps one set of lean records.  The structured double-integrator form only: its A, B are functions of
+// the one parameter row.
+inline bool gain_inputs_shared(const isls_gain_args &g)
+{
+    return g.rec && g.lin_on && g.lin_model == ISLS_MODEL_DI && g.lin_par && g.lin_par_sb == 0 && g.Cxx.sb == 0 && g.Cuu.sb == 0 &&
+           (!g.Cux.p || g.Cux.sb == 0);
+}
+#endif
+
 // Launch wrappers implemented one per .hip file; each returns ISLS_OK / ISLS_ERR_*.
 // ff != nullptr: the pass may also run the first feed-forward pass (same records, time-invariant Qr / Rr); *did_ff tells
 // require_ff: launch nothing unless the feed-forward pass can ride along (*did_ff stays false)
+// shared (the outer driver, gain_inputs_shared): one set of records for the whole batch, in slot 0 of block 0 -- the gain pass
+// writes them there only, the feed-forward passes and the line search read them from there (K, k stay per trajectory)
 template <typename T>
-int launch_gain(const isls_gain_args &a, hipStream_t s, const isls_ff_args *ff = nullptr, bool *did_ff = nullptr, bool require_ff = false);
-template <typename T> int launch_ff(const isls_ff_args &a, hipStream_t s);
-template <typename T> int launch_ff_record(const isls_ff_args &a, hipStream_t s);
+int launch_gain(const isls_gain_args &a, hipStream_t s, const isls_ff_args *ff = nullptr, bool *did_ff = nullptr, bool require_ff = false,
+                bool shared = false);
+template <typename T> int launch_ff(const isls_ff_args &a, hipStream_t s, bool shared = false);
+template <typename T> int launch_ff_record(const isls_ff_args &a, hipStream_t s, bool shared = false);
 template <typename T> int launch_ff_prepare(const isls_ff_prepare_args &a, hipStream_t s);
 template <typename T> int launch_ff_stitch(const isls_ff_args &a, hipStream_t s);
 bool ff_seg_enabled(const isls_ffseg &sg);
@@ -242,7 +257,9 @@ int ff_segments(int N, int nseg_req, int *seg_len);
 template <typename T>
 // last = false (fused form only): further ADMM iterations of the same outer iteration follow, the x-step of a trajectory that
 // goes on need not be written out
-int launch_rollout(const isls_rollout_args &a, hipStream_t s, const isls_admm_args *fused = nullptr, bool *did_fuse = nullptr, bool last = true);
+// shared_rec != nullptr: K_t is read from the batch's one set of lean records (see launch_gain) instead of the K array
+int launch_rollout(const isls_rollout_args &a, hipStream_t s, const isls_admm_args *fused = nullptr, bool *did_fuse = nullptr, bool last = true,
+                   const void *shared_rec = nullptr);
 bool rollout_can_fuse_admm(const isls_rollout_args &r, const isls_admm_args &a);
 template <typename T> int launch_admm(const isls_admm_args &a, hipStream_t s);
 template <typename T> int launch_project(const isls_project_args &a, hipStream_t s);

@@ -113,11 +113,26 @@ __device__ __forceinline__ bool chol_upper_rd(const T (&A)[M][M], T (&U)[M][M], 
 // RL (isls_gain_args.lin_on): only the tail [K | fac | model words] of every record leaves for HBM, at its own dense stride
 // rec_lean_stride -- the layout the model-structured feed-forward pass reads (the [Phi | B] blocks nobody would read are 54 of
 // 81 words at n = 6, m = 3: 177 MB of stores per launch at the headline size).  The record IMAGE in LDS keeps its full form.
-template <typename T, int NX, int NU, int D, int MODE, bool FF, bool REC, bool ARR, int LIN = 0, bool RL = (LIN == 1)>
-__global__ __launch_bounds__(64, ISLS_GAIN_OCC) void riccati_gain_kernel(GainP<T> p)
+// SH (launch_gain's `shared`: the inputs of the recursion are the same for every trajectory of the batch, so every wavefront
+// computes the same K_t, fac_t): only block 0 writes records, all of its slots (identical images), and every reader takes
+// slot 0 of block 0 at every step.  The other wavefronts run the step loop without the record stores -- a second instantiation
+// of the loop picked once per wavefront (RS), not a predicate on the stores.  K, k and status stay per trajectory.  Block 0 must
+// write the records even when none of its trajectories is active: it then runs the recursion on trajectory 0's operands
+// (loads only) and aims the K / k stores at spare words of the record buffer behind its own run.
+// (words of the slots' LDS records: the kernel declares them, the body checks the count against its layout)
+template <int NX, int NU>
+__host__ __device__ constexpr int gain_lds_words(bool ff)
+{
+    constexpr int W = NX + NU;
+    return (kWave / W) * ((NX * NX + NX * W + NU * W + NU * NX + (ff ? 2 * W + NX + 2 * NU : W)) | 1);   // TPW slots, see the body
+}
+template <typename T, int NX, int NU, int D, int MODE, bool FF, bool REC, bool ARR, int LIN, bool RL, bool SH, bool RS>
+__device__ __forceinline__ void riccati_gain_body(const GainP<T> &p, T *lds, T *img)
 {
     static_assert(LIN == 0 || NX == 2 * NU, "double integrator: n = 2 d, m = d");
     static_assert(!RL || (REC && !ARR), "lean records: record form without the Quu / fac / Qux arrays");
+    static_assert(!SH || (REC && !ARR), "shared records: record form without the Quu / fac / Qux arrays");
+    static_assert(RS || SH, "only a wavefront of the shared form leaves its records unwritten");
     constexpr int G = NX + NU, W = NX + NU, TPW = kWave / G;
     constexpr int V_OFF = 0, AB_OFF = V_OFF + NX * NX, Q_OFF = AB_OFF + NX * W, K_OFF = Q_OFF + NU * W;
     constexpr int DUMP_OFF = K_OFF + NU * NX;              // W words that absorb the LDS writes of lanes with nothing to publish
@@ -126,14 +141,13 @@ __global__ __launch_bounds__(64, ISLS_GAIN_OCC) void riccati_gain_kernel(GainP<T
     constexpr int SLOT = FF ? ((QU_OFF + NU) | 1) : ((DUMP_OFF + W) | 1);   // odd stride: slots start on different banks
     constexpr int JA = (NX * NX + G - 1) / G, JB = (NX * NU + G - 1) / G, JQ = (NU * W + G - 1) / G;
     constexpr int RB = NX * NX, RK = RB + NX * NU, RFAC = RK + NU * NX, RW = rec_stride(NX, NU);   // packed record (padded stride), see riccati_ffrec.hip
-    __shared__ T lds[TPW * SLOT];
+    static_assert(TPW * SLOT == gain_lds_words<NX, NU>(FF), "slot record");
     // Image of the step's packed records, [2][TPW + 1][RW] (double buffer): the lanes drop
     // their words of a step here (this is also where the V update reads K from) and read the finished image back lane-linearly
     // while the V update computes -- the wavefront's TPW records are one contiguous run of TPW*RW words, written with
     // ceil(TPW*RW/128) fully coalesced 16-byte stores instead of W scattered 8-byte stores per lane.  The K array leaves the
     // same way.  Two buffers: a step's image is still being read when the next step starts writing.
     constexpr int IMG = (TPW + 1) * RW;
-    __shared__ __align__(16) T img[2 * IMG];
 
     const int lane = threadIdx.x;
     const int bx = blockIdx.x;                                 // trajectory block of this wavefront
@@ -142,8 +156,9 @@ __global__ __launch_bounds__(64, ISLS_GAIN_OCC) void riccati_gain_kernel(GainP<T
     const int b = bx * TPW + s;
     const bool valid = b < p.B && (p.active == nullptr || p.active[b] != 0);
     const unsigned long long vmask = __ballot(valid);
-    if (vmask == 0ull) return;                                 // nothing to do for this wavefront
-    const int vlane = __builtin_ctzll(vmask);                  // a lane of the first valid slot
+    const bool ronly = SH && RS && vmask == 0ull;              // shared form, block 0: the records are everybody's (uniform)
+    if (vmask == 0ull && !ronly) return;                       // nothing to do for this wavefront
+    const int vlane = ronly ? 0 : __builtin_ctzll(vmask);      // a lane of the first valid slot (records only: trajectory 0)
     const int bsh = __builtin_amdgcn_readlane(b, vlane), ssh = __builtin_amdgcn_readlane(s, vlane);
     const int N = p.N;
     const int bb = valid ? b : bsh;
@@ -344,27 +359,33 @@ __global__ __launch_bounds__(64, ISLS_GAIN_OCC) void riccati_gain_kernel(GainP<T
         fw[j] = (fd[j] / RSW) * RW + RSRC + fd[j] % RSW;       // (dense records: fw == fd)
     }
     T *const recg = REC ? p.rec + (int64_t)bx * N * (TPW * RSW) : nullptr;   // the wavefront's records, step 0
+    // where K and k leave for: the arrays, or (records only) N (NU NX + NU) spare words behind block 0's run of the buffer
+    static_assert(!SH || TPW * RSW + NU * NX + NU <= TPW * RW, "spare words of the record buffer behind block 0's run");
+    T *const spare = (SH && RS) ? p.rec + (int64_t)N * (TPW * RSW) : nullptr;
+    T *const Kout = ronly ? spare : p.K;
+    T *const kffout = ronly ? spare + (int64_t)N * (NU * NX) : p.kff;
+    constexpr int JPS = RS ? JP : 0;                           // record stores of a step
 
     // The image of a step is read back into fl / fk behind its sync (c) and leaves for HBM during the NEXT step, one store
     // between two blocks of that step's arithmetic: a wavefront waits while a store's data drains (the CU moves ~7-16 B per
     // clock), so stores issued back to back are paid in full, spread out they overlap with the arithmetic.
     V2 fl[JP], fk[JK];
     T fk1[JK];
-    auto send = [&](int tq, int j) {                           // j-th of the JP + JK stores of step tq's image
-        if (j < JP) {
-            if constexpr (REC) {
+    auto send = [&](int tq, int j) {                           // j-th of the JPS + JK stores of step tq's image
+        if (j < JPS) {
+            if constexpr (REC && RS) {
                 V2 *dr = reinterpret_cast<V2 *>(recg + (int64_t)tq * (TPW * RSW) + fd[j < JP ? j : 0]);
                 st_stream(dr, fl[j < JP ? j : 0]);
             }
-        } else if (j < JP + JK) {
-            const int jj = j - JP < JK ? (j - JP >= 0 ? j - JP : 0) : 0;
-            T *dk = p.K + kgo[jj] + (int64_t)tq * (NU * NX);
+        } else if (j < JPS + JK) {
+            const int jj = j - JPS < JK ? (j - JPS >= 0 ? j - JPS : 0) : 0;
+            T *dk = Kout + kgo[jj] + (int64_t)tq * (NU * NX);
             if constexpr (KPAIRS) st_stream(reinterpret_cast<V2 *>(dk), fk[jj]);
             else *dk = fk1[jj];
         }
     };
-    // the JP + JK stores take evenly spaced places among the 3 NX blocks of the step's three accumulation loops
-    constexpr int NSEND = JP + JK, NPOS = 3 * NX;
+    // the JPS + JK stores take evenly spaced places among the 3 NX blocks of the step's three accumulation loops
+    constexpr int NSEND = JPS + JK, NPOS = 3 * NX;
     static_assert(NSEND <= NPOS, "at most one store per block");
     auto send_at = [&](int tq, auto POS) {
         constexpr int pos = decltype(POS)::value;
@@ -601,7 +622,7 @@ __global__ __launch_bounds__(64, ISLS_GAIN_OCC) void riccati_gain_kernel(GainP<T
             T kv = kt[0];
 #pragma unroll
             for (int r = 1; r < NU; ++r) kv = (ff_ku == r) ? kt[r] : kv;
-            p.kff[o * NU + ff_ku] = kv;                        // every lane (x-lanes and shadows store copies)
+            kffout[o * NU + ff_ku] = kv;                       // every lane (x-lanes and shadows store copies)
             // v_i = (cx_i + (Phi'v)_i) + (K'cu)_i
             T acc = T(0), kcu = T(0);
 #pragma unroll
@@ -648,7 +669,7 @@ __global__ __launch_bounds__(64, ISLS_GAIN_OCC) void riccati_gain_kernel(GainP<T
         const T *Ks = imq + s * RW + RK;
         // the finished image goes back into registers lane-linearly (unconditional reads, issued ahead of the V update whose
         // arithmetic covers their latency) and leaves for HBM behind it
-        if constexpr (REC) {
+        if constexpr (REC && RS) {
 #pragma unroll
             for (int j = 0; j < JP; ++j) fl[j] = *reinterpret_cast<const V2 *>(imq + fw[j]);
         }
@@ -716,9 +737,22 @@ __global__ __launch_bounds__(64, ISLS_GAIN_OCC) void riccati_gain_kernel(GainP<T
     }
     if (tlast >= 0) {                                          // the last step's image
 #pragma unroll
-        for (int j = 0; j < JP + JK; ++j) send(tlast, j);
+        for (int j = 0; j < JPS + JK; ++j) send(tlast, j);
     }
     if (valid && i == 0 && !pd_ok && p.status) atomicOr(&p.status[b], ISLS_ST_NOT_PD);
+}
+
+template <typename T, int NX, int NU, int D, int MODE, bool FF, bool REC, bool ARR, int LIN = 0, bool RL = (LIN == 1), bool SH = false>
+__global__ __launch_bounds__(64, ISLS_GAIN_OCC) void riccati_gain_kernel(GainP<T> p)
+{
+    __shared__ T lds[gain_lds_words<NX, NU>(FF)];
+    __shared__ __align__(16) T img[2 * (kWave / (NX + NU) + 1) * rec_stride(NX, NU)];
+    if constexpr (SH) {
+        if (blockIdx.x == 0) riccati_gain_body<T, NX, NU, D, MODE, FF, REC, ARR, LIN, RL, true, true>(p, lds, img);
+        else riccati_gain_body<T, NX, NU, D, MODE, FF, REC, ARR, LIN, RL, true, false>(p, lds, img);
+    } else {
+        riccati_gain_body<T, NX, NU, D, MODE, FF, REC, ARR, LIN, RL, false, true>(p, lds, img);
+    }
 }
 
 // dimensions for which the pass with the feed-forward recursion inside keeps its operands in registers (at n = 9 it spills
@@ -726,7 +760,7 @@ __global__ __launch_bounds__(64, ISLS_GAIN_OCC) void riccati_gain_kernel(GainP<T
 constexpr bool gain_ff_dims(int n, int m) { return n * n + n * (n + m) <= 100; }
 
 template <typename T>
-int launch_gain(const isls_gain_args &a, hipStream_t s, const isls_ff_args *ff, bool *did_ff, bool require_ff)
+int launch_gain(const isls_gain_args &a, hipStream_t s, const isls_ff_args *ff, bool *did_ff, bool require_ff, bool shared)
 {
     if (did_ff) *did_ff = false;
     if (a.B < 0 || a.N < 1 || !a.A.p || !a.Bm.p || !a.Cxx.p || !a.Cuu.p || !a.K) return ISLS_ERR_ARG;
@@ -754,6 +788,8 @@ int launch_gain(const isls_gain_args &a, hipStream_t s, const isls_ff_args *ff, 
         else return ISLS_ERR_UNSUPPORTED;
     }
     p.lin_par = (const T *)a.lin_par; p.lin_par_sb = a.lin_par_sb;
+    // shared records (gain_inputs_shared): the structured double-integrator form has them; the caller's readers rely on it
+    if (shared && (!lin_di || !gain_inputs_shared(a) || !dims_supported(a.n, a.m))) return ISLS_ERR_ARG;
     // the first feed-forward pass rides along when it would run on this pass's records with time-invariant Qr / Rr rows
     const bool with_ff = ff && gain_ff_dims(a.n, a.m) && a.rec && ff->rec == a.rec && ff->k && ff->B == a.B && ff->N == a.N && ff->n == a.n && ff->m == a.m &&
                          ff->solve_mode == a.solve_mode && ff->active == a.active && ff->c0x.p && ff->c0u.p &&
@@ -769,7 +805,8 @@ int launch_gain(const isls_gain_args &a, hipStream_t s, const isls_ff_args *ff, 
 #define LAUNCH_G(NX_, NU_, MODE_, FF_, REC_, ARR_) \
     hipLaunchKernelGGL((riccati_gain_kernel<T, NX_, NU_, kGainDepth, MODE_, FF_, REC_, ARR_>), dim3(grid), dim3(64), 0, s, p)
 #define LAUNCH_GL(NX_, NU_, MODE_, FF_) \
-    hipLaunchKernelGGL((riccati_gain_kernel<T, NX_, NU_, kGainDepth, MODE_, FF_, true, false, 1>), dim3(grid), dim3(64), 0, s, p)
+    do { if (shared) hipLaunchKernelGGL((riccati_gain_kernel<T, NX_, NU_, kGainDepth, MODE_, FF_, true, false, 1, true, true>), dim3(grid), dim3(64), 0, s, p); \
+         else hipLaunchKernelGGL((riccati_gain_kernel<T, NX_, NU_, kGainDepth, MODE_, FF_, true, false, 1>), dim3(grid), dim3(64), 0, s, p); } while (0)
 #define LAUNCH_GC(NX_, NU_, MODE_, FF_) /* dense arithmetic, lean records (the car) */      \
     hipLaunchKernelGGL((riccati_gain_kernel<T, NX_, NU_, kGainDepth, MODE_, FF_, true, false, 0, true>), dim3(grid), dim3(64), 0, s, p)
 #define LAUNCH_M(NX_, NU_, MODE_)                                                           \
@@ -807,8 +844,8 @@ int launch_gain(const isls_gain_args &a, hipStream_t s, const isls_ff_args *ff, 
     if (did_ff) *did_ff = with_ff;
     return check_launch();
 }
-template int launch_gain<double>(const isls_gain_args &, hipStream_t, const isls_ff_args *, bool *, bool);
-template int launch_gain<float>(const isls_gain_args &, hipStream_t, const isls_ff_args *, bool *, bool);
+template int launch_gain<double>(const isls_gain_args &, hipStream_t, const isls_ff_args *, bool *, bool, bool);
+template int launch_gain<float>(const isls_gain_args &, hipStream_t, const isls_ff_args *, bool *, bool, bool);
 
 
 }  // namespace isls

@@ -262,11 +262,15 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec_kernel(FfRecP<T> p)
 //             fac):  (A'v)_0 = v_0, (A'v)_1 = v_1, (A'v)_2 = a02 v_0 + a12 v_1 + v_2, (A'v)_3 = a03 v_0 + a13 v_1 + a23 v_2 + v_3,
 //             B'v = (b20 v_2, dt v_3)
 // -- the same products as the dense form in another association (results equal up to rounding, same tolerance against the oracle).
+// SH (launch_ff's `shared`, LIN_DI): the batch has ONE set of records, in slot 0 of block 0 (riccati.hip); every slot of every
+// wavefront stages that record.  The table is N lean records (22 KB at N = 100, n = 6, m = 3) that every wavefront of the launch
+// reads again: plain loads, so that it stays in the caches, where the per-trajectory records stream through with `nt`.
 constexpr int LIN_NONE = 0, LIN_DI = 1, LIN_ARM3R = 2, LIN_CAR = 3;
 
-template <typename T, int NX, int NU, int D, int OCC, int MODE, int LIN = LIN_NONE>
+template <typename T, int NX, int NU, int D, int OCC, int MODE, int LIN = LIN_NONE, bool SH = false>
 __global__ __launch_bounds__(64, OCC) void riccati_ffrec2_kernel(FfRecP<T> p)
 {
+    static_assert(!SH || LIN == LIN_DI, "shared records: the structured double-integrator form");
     static_assert(LIN != LIN_DI || NX == 2 * NU, "double integrator: n = 2 d, m = d");
     static_assert(LIN != LIN_ARM3R || (NX == 9 && NU == 3), "planar 3R arm: n = 9, m = 3");
     static_assert(LIN != LIN_CAR || (NX == 4 && NU == 2), "car: n = 4, m = 2");
@@ -312,14 +316,14 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec2_kernel(FfRecP<T> p)
     // A slot that shadows another trajectory still reads its own place in the run (whatever the gain pass left there) but
     // restages the shadowed slot's record below, so it computes exactly what that slot computes.
     constexpr int BW = TPW * RW, NP = TPW * SW / 2, JR = (NP + kWave - 1) / kWave;
-    const T *bR = p.rec + (int64_t)bx * N * BW;
+    const T *bR = p.rec + (SH ? (int64_t)0 : (int64_t)bx * N * BW);
     uint32_t oR[JR];
     int dR[JR];
 #pragma unroll
     for (int j = 0; j < JR; ++j) {
         const int q = lane + kWave * j;
         const int w = 2 * (q < NP ? q : NP - 1);               // word within the staged words of the wavefront's slots
-        oR[j] = (uint32_t)w;                                   // (SW == RW in both layouts: the staged words are the record)
+        oR[j] = (uint32_t)(SH ? w % SW : w);                   // (SW == RW in both layouts: the staged words are the record)
         dR[j] = q < NP ? (w / SW) * SLOT + (w % SW) : TPW * SLOT + DUMP_OFF;
     }
     // where this lane READS its slot's record: its own slot, or the shadowed one
@@ -367,8 +371,10 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec2_kernel(FfRecP<T> p)
         const int t = __builtin_amdgcn_readfirstlane(tq);
         const T *r = bR + (int64_t)t * BW;
 #pragma unroll
-        for (int j = 0; j < JR; ++j)                            // the records stream through once per pass: 78 -> 71 us with `nt`
-            g.rr[j] = ld_stream(reinterpret_cast<const V2 *>(r + oR[j]));
+        for (int j = 0; j < JR; ++j) {                          // the records stream through once per pass: 78 -> 71 us with `nt`
+            if constexpr (SH) g.rr[j] = *reinterpret_cast<const V2 *>(r + oR[j]);
+            else g.rr[j] = ld_stream(reinterpret_cast<const V2 *>(r + oR[j]));
+        }
         const uint32_t tu = (uint32_t)t;
         g.c0 = pc0[tu * c0st];
         g.hv = ph[tu * hst];
@@ -582,11 +588,12 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec2_kernel(FfRecP<T> p)
 #endif
 // the one-hand-off kernel in the form `lin` selects (the structured forms exist for the dimensions their models have)
 template <typename T, int NX, int NU, int D, int DL, int OCC, int MODE>
-static void launch_ffrec2(int lin, dim3 grid, hipStream_t s, const FfRecP<T> &p)
+static void launch_ffrec2(int lin, bool shared, dim3 grid, hipStream_t s, const FfRecP<T> &p)
 {
     if constexpr (NX == 2 * NU) {
         if (lin == LIN_DI) {
-            hipLaunchKernelGGL((riccati_ffrec2_kernel<T, NX, NU, DL, OCC, MODE, LIN_DI>), grid, dim3(64), 0, s, p);
+            if (shared) hipLaunchKernelGGL((riccati_ffrec2_kernel<T, NX, NU, DL, OCC, MODE, LIN_DI, true>), grid, dim3(64), 0, s, p);
+            else hipLaunchKernelGGL((riccati_ffrec2_kernel<T, NX, NU, DL, OCC, MODE, LIN_DI>), grid, dim3(64), 0, s, p);
             return;
         }
     }
@@ -606,7 +613,7 @@ static void launch_ffrec2(int lin, dim3 grid, hipStream_t s, const FfRecP<T> &p)
 }
 
 template <typename T>
-int launch_ff_record(const isls_ff_args &a, hipStream_t s)
+int launch_ff_record(const isls_ff_args &a, hipStream_t s, bool shared)
 {
     if ((int64_t)a.N * rec_stride(a.n, a.m) * 64 >= ((int64_t)1 << 31)) return ISLS_ERR_UNSUPPORTED;
     FfRecP<T> p;
@@ -642,14 +649,15 @@ int launch_ff_record(const isls_ff_args &a, hipStream_t s)
         if (!a.lin_par) return ISLS_ERR_ARG;
         if (!rowc || segmented) return ISLS_ERR_UNSUPPORTED;
     }
+    if (shared && (lin != LIN_DI || a.lin_par_sb != 0)) return ISLS_ERR_ARG;   // one set of records: the form that writes them
     p.lin_par = (const T *)a.lin_par; p.lin_par_sb = a.lin_par_sb;
     // the one-hand-off kernel addresses a step of c0x / c0u with a 32-bit offset
     const int64_t c0lim = ((int64_t)1 << 31) / (a.N > 1 ? a.N - 1 : 1);
     if (rowc && (a.c0x.st < 0 || a.c0u.st < 0 || a.c0x.st >= c0lim || a.c0u.st >= c0lim)) return ISLS_ERR_UNSUPPORTED;
 #define LAUNCH2(NX_, NU_, MODE_)                                                                                        \
     {                                                                                                                   \
-        if (segmented) launch_ffrec2<T, NX_, NU_, ISLS_FF2_SEG_DEPTH, ISLS_FF2_SEG_DEPTH, (NX_ * NX_ > 64 ? 1 : 2), MODE_>(lin, dim3(grid, p.nseg, p.ncol), s, p); /* n = 9: 256 registers spill */ \
-        else launch_ffrec2<T, NX_, NU_, ISLS_FF2_SEQ_DEPTH, ISLS_FF2_LEAN_DEPTH, 1, MODE_>(lin, dim3(grid, 1, p.ncol), s, p);                  \
+        if (segmented) launch_ffrec2<T, NX_, NU_, ISLS_FF2_SEG_DEPTH, ISLS_FF2_SEG_DEPTH, (NX_ * NX_ > 64 ? 1 : 2), MODE_>(lin, false, dim3(grid, p.nseg, p.ncol), s, p); /* n = 9: 256 registers spill */ \
+        else launch_ffrec2<T, NX_, NU_, ISLS_FF2_SEQ_DEPTH, ISLS_FF2_LEAN_DEPTH, 1, MODE_>(lin, shared, dim3(grid, 1, p.ncol), s, p);          \
     }
 #define CALL(NX_, NU_)                                                                                                  \
     {                                                                                                                   \
@@ -668,7 +676,7 @@ int launch_ff_record(const isls_ff_args &a, hipStream_t s)
 #undef LAUNCH2
     return check_launch();
 }
-template int launch_ff_record<double>(const isls_ff_args &, hipStream_t);
-template int launch_ff_record<float>(const isls_ff_args &, hipStream_t);
+template int launch_ff_record<double>(const isls_ff_args &, hipStream_t, bool);
+template int launch_ff_record<float>(const isls_ff_args &, hipStream_t, bool);
 
 }  // namespace isls

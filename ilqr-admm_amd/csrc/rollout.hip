@@ -29,7 +29,7 @@ constexpr bool family_table_consistent()
 static_assert(family_table_consistent(), "families.def: a family's (n, m) is not in the pair list, or a pair has no ISLS_MODEL_LTI family");
 
 template <typename T>
-int launch_rollout(const isls_rollout_args &a, hipStream_t s, const isls_admm_args *fused, bool *did_fuse, bool last)
+int launch_rollout(const isls_rollout_args &a, hipStream_t s, const isls_admm_args *fused, bool *did_fuse, bool last, const void *shared_rec)
 {
     if (did_fuse) *did_fuse = false;
     if (a.B < 0 || a.N < 1 || a.L < 1 || a.L > 64) return ISLS_ERR_ARG;
@@ -41,11 +41,18 @@ int launch_rollout(const isls_rollout_args &a, hipStream_t s, const isls_admm_ar
     if (a.wq.p && (!a.zx || !a.lx)) return ISLS_ERR_ARG;
     if (a.wr.p && (!a.zu || !a.lu)) return ISLS_ERR_ARG;
     if (a.B == 0) return ISLS_OK;
+    if (shared_rec && !dims_supported(a.n, a.m)) return ISLS_ERR_ARG;
     if (!dims_supported(a.n, a.m)) return launch_rollout_generic<T>(a, s);     // generic.hip (no fused ADMM update: *did_fuse stays false)
     RoP<T> p;
     p.B = a.B; p.N = a.N; p.L = a.L; p.flags = a.flags;
     p.par = (const T *)a.model_par; p.par_sb = a.model_par_sb;
-    p.K = (const T *)a.K; p.k = (const T *)a.k; p.xhat = (const T *)a.xhat; p.uhat = (const T *)a.uhat;
+    p.K = (const T *)a.K; p.K_sb = (int64_t)a.N * a.m * a.n; p.K_st = a.m * a.n;
+    if (shared_rec) {
+        // the batch's one set of lean records [K | fac] (riccati.hip): slot 0 of block 0, a step's run of 64 / (n + m) slots apart
+        // (K leads the record and the stride is even: the pair loads keep their alignment)
+        p.K = (const T *)shared_rec; p.K_sb = 0; p.K_st = (kWave / (a.n + a.m)) * rec_lean_stride(a.n, a.m);
+    }
+    p.k = (const T *)a.k; p.xhat = (const T *)a.xhat; p.uhat = (const T *)a.uhat;
     p.x0 = (const T *)a.x0; p.alphas = (const T *)a.alphas;
     p.Qtab = (const T *)a.Qtab; p.ztab = (const T *)a.ztab; p.Qtab_sb = a.Qtab_sb; p.ztab_sb = a.ztab_sb;
     p.seq = a.seq; p.qnz = a.q_nonzero;
@@ -86,8 +93,8 @@ int launch_rollout(const isls_rollout_args &a, hipStream_t s, const isls_admm_ar
     if (did_fuse) *did_fuse = rc == ISLS_OK && p.fa_on != 0;   // the family launcher drops the fused update when the stage does not fit
     return rc;
 }
-template int launch_rollout<double>(const isls_rollout_args &, hipStream_t, const isls_admm_args *, bool *, bool);
-template int launch_rollout<float>(const isls_rollout_args &, hipStream_t, const isls_admm_args *, bool *, bool);
+template int launch_rollout<double>(const isls_rollout_args &, hipStream_t, const isls_admm_args *, bool *, bool, const void *);
+template int launch_rollout<float>(const isls_rollout_args &, hipStream_t, const isls_admm_args *, bool *, bool, const void *);
 
 template <typename T>
 int launch_dense_closed_loop(const isls_dense_loop_args &a, hipStream_t s)

@@ -69,6 +69,10 @@ struct RoP {
     View<T> fa_xlo, fa_xhi, fa_ulo, fa_uhi;
     int32_t *fa_active, *fa_iters;
     int64_t cpar_sb;               // a user cost's parameters: 0 = shared, else one row of that many words per trajectory
+    // where K_t is read: trajectory b's K_0 at K + b * K_sb, a step further K_st words on.  The K array: N m n and m n; the
+    // batch's one set of lean records (launch_rollout's shared_rec): 0 and the words between two steps of a record slot
+    int64_t K_sb;
+    int K_st;
 };
 
 // ---- cost of the user's own (isls.costs.Custom) ---------------------------------------------------
@@ -328,10 +332,10 @@ struct RoWOp {
 // uses them): a branch in the fetch, even a wave-uniform one, makes the compiler wait for vmcnt(0) in the replay loop and
 // the ring of operands in flight is gone.
 template <typename T, int NX, int NU, int RPL>
-__device__ __forceinline__ void ro_wfetch(RoWOp<T, NX, RPL> &o, const T *wK, const T *wk, const T *wxh, const T *wuh, int i, int last)
+__device__ __forceinline__ void ro_wfetch(RoWOp<T, NX, RPL> &o, const T *wK, int kst, const T *wk, const T *wxh, const T *wuh, int i, int last)
 {
     const int ii = i < last ? i : last;
-    const T *qK = wK + (int64_t)ii * (NU * NX), *qk = wk + (int64_t)ii * NU;
+    const T *qK = wK + (int64_t)(ii * kst), *qk = wk + (int64_t)ii * NU;
 #pragma unroll
     for (int e = 0; e < RPL * NX; ++e) o.K[e] = qK[e];
 #pragma unroll
@@ -346,7 +350,7 @@ __device__ __forceinline__ void ro_wfetch(RoWOp<T, NX, RPL> &o, const T *wK, con
 
 template <typename T, int NX, int NU, int MODEL, int RL, int WD, bool STAGE>
 __device__ __forceinline__ void ro_replay(const Model<T, NX, NU, MODEL> &model, int c, int ind, bool valid, bool accept, bool stage_on,
-                                          int N, int NSEG, int S, int64_t bN, T alpha_w, const T *pK, const T *pk, const T *pxh,
+                                          int N, int NSEG, int S, int64_t bN, T alpha_w, const T *pK, int kst, const T *pk, const T *pxh,
                                           const T *puh, const T *ck, T *stage, int uoff, T *ubuf, int gl, T *x_out, T *u_out)
 {
     constexpr int RPL = NU / RL;                               // control rows per lane
@@ -364,15 +368,15 @@ __device__ __forceinline__ void ro_replay(const Model<T, NX, NU, MODEL> &model, 
     // instruction of the loop is conditional
     {
         const bool wl = valid;
-        const T *wK = pK + (bN + t0) * NU * NX + r0 * NX, *wk = pk + (bN + t0) * NU + r0;
+        const T *wK = pK + (int64_t)t0 * kst + r0 * NX, *wk = pk + (bN + t0) * NU + r0;   // pK: the trajectory's K_0, kst words per step
         const bool has_xh = pxh != nullptr, has_uh = puh != nullptr;      // uniform
         const T xhm = has_xh ? T(1) : T(0), uhm = has_uh ? T(1) : T(0);
-        const T *wxh = has_xh ? pxh + (bN + t0) * NX : pK + bN * NU * NX, *wuh = has_uh ? puh + (bN + t0) * NU + r0 : pK + bN * NU * NX;
+        const T *wxh = has_xh ? pxh + (bN + t0) * NX : pK, *wuh = has_uh ? puh + (bN + t0) * NU + r0 : pK;
         const int last = N - 1 - t0;                           // iterations beyond it repeat step N-1 (loads only)
         WOp ring[WD];
 #pragma unroll
         for (int d = 0; d < WD; ++d) {
-            ro_wfetch<T, NX, NU, RPL>(ring[d], wK, wk, wxh, wuh, d, last);
+            ro_wfetch<T, NX, NU, RPL>(ring[d], wK, kst, wk, wxh, wuh, d, last);
             __builtin_amdgcn_sched_barrier(0);
         }
         T *xo = x_out + (bN + t0) * NX, *uo = u_out + (bN + t0) * NU + r0;   // direct stores when the stage does not fit
@@ -390,7 +394,7 @@ __device__ __forceinline__ void ro_replay(const Model<T, NX, NU, MODEL> &model, 
                 const int i = i0 + d, t = t0 + i;
                 const bool in = wl && i < S && t < t1;
                 const WOp o = ring[d];
-                ro_wfetch<T, NX, NU, RPL>(ring[d], wK, wk, wxh, wuh, i + WD, last);
+                ro_wfetch<T, NX, NU, RPL>(ring[d], wK, kst, wk, wxh, wuh, i + WD, last);
                 T uown[RPL], u[NU];
 #pragma unroll
                 for (int r = 0; r < RPL; ++r) {
@@ -492,6 +496,7 @@ __global__ __launch_bounds__(64, OCC) void rollout_kernel(RoP<T> p)
     const bool cand = valid && c < L;
     const int bb = inbatch ? b : blockIdx.x * TPW;             // idle lanes shadow the block's first trajectory (loads only)
     const int64_t bN = (int64_t)bb * N;
+    const T *const Kb = p.K + (int64_t)bb * p.K_sb;            // K_0 of the trajectory (or of the batch: RoP::K_sb)
     T *slot = lds + s * SLOT;
     T *c_aug = slot, *c_pln = c_aug + GL, *mdl = c_pln + GL;
     T *recs = static_cast<T *>(__builtin_assume_aligned(mdl + LY::mdl_elems(MDLW), W == 2 ? 2 * sizeof(T) : sizeof(T)));
@@ -519,13 +524,13 @@ __global__ __launch_bounds__(64, OCC) void rollout_kernel(RoP<T> p)
         pl.q = c < GL ? c + GL * j : (1 << 20);                // extra idle lanes stage nothing
         ro_plan_group<W>(pl, has_wq, p.zx + bN * NX, p.lx + bN * NX, NX, O_RX, NX);
         ro_plan_group<W>(pl, has_wr, p.zu + bN * NU, p.lu + bN * NU, NU, O_RU, NU);
-        ro_plan_group<W>(pl, true, p.K + bN * NU * NX, (const T *)nullptr, NU * NX, O_K, NU * NX);
+        ro_plan_group<W>(pl, true, Kb, (const T *)nullptr, NU * NX, O_K, p.K_st);
         ro_plan_group<W>(pl, true, p.k + bN * NU, (const T *)nullptr, NU, O_KK, NU);
         ro_plan_group<W>(pl, has_xh, p.xhat + bN * NX, (const T *)nullptr, NX, O_XH, NX);
         ro_plan_group<W>(pl, has_uh, p.uhat + bN * NU, (const T *)nullptr, NU, O_UH, NU);
         ro_plan_group<W>(pl, wq_var, wq_var ? p.wq.at(bb, 0) : (const T *)nullptr, (const T *)nullptr, NX, O_WQ, (int)p.wq.st);
         ro_plan_group<W>(pl, wr_var, wr_var ? p.wr.at(bb, 0) : (const T *)nullptr, (const T *)nullptr, NU, O_WR, (int)p.wr.st);
-        pa[j] = pl.done ? pl.a : p.K + bN * NU * NX;
+        pa[j] = pl.done ? pl.a : Kb;
         stp[j] = pl.done ? (int64_t)pl.st * (int64_t)sizeof(T) : 0;
         dst[j] = pl.done ? pl.off : O_DUMP;
         if (j == 0) {
@@ -823,16 +828,16 @@ __global__ __launch_bounds__(64, OCC) void rollout_kernel(RoP<T> p)
         // family), and with a stage cost inlined into the search the fourth stage pushed one variant or another 8 bytes past that
         constexpr int WDR = (UC && OCC == 2 && NX >= 9) ? 3 : 4;
         if (p.seg_lanes > 1 && stage_on)
-            ro_replay<T, NX, NU, MODEL, NU, WDR, true>(model, c, ind, valid, accept, stage_on, N, NSEG, S, bN, alpha_w, p.K, p.k, pxh, puh, ck,
+            ro_replay<T, NX, NU, MODEL, NU, WDR, true>(model, c, ind, valid, accept, stage_on, N, NSEG, S, bN, alpha_w, Kb, p.K_st, p.k, pxh, puh, ck,
                                                      stage, uoff, c_aug, GL, p.x_out, p.u_out);
         else if (p.seg_lanes > 1)
-            ro_replay<T, NX, NU, MODEL, NU, WDR, false>(model, c, ind, valid, accept, stage_on, N, NSEG, S, bN, alpha_w, p.K, p.k, pxh, puh, ck,
+            ro_replay<T, NX, NU, MODEL, NU, WDR, false>(model, c, ind, valid, accept, stage_on, N, NSEG, S, bN, alpha_w, Kb, p.K_st, p.k, pxh, puh, ck,
                                                       stage, uoff, c_aug, GL, p.x_out, p.u_out);
         else if (stage_on)
-            ro_replay<T, NX, NU, MODEL, 1, 2, true>(model, c, ind, valid, accept, stage_on, N, NSEG, S, bN, alpha_w, p.K, p.k, pxh, puh, ck,
+            ro_replay<T, NX, NU, MODEL, 1, 2, true>(model, c, ind, valid, accept, stage_on, N, NSEG, S, bN, alpha_w, Kb, p.K_st, p.k, pxh, puh, ck,
                                                     stage, uoff, c_aug, GL, p.x_out, p.u_out);
         else
-            ro_replay<T, NX, NU, MODEL, 1, 2, false>(model, c, ind, valid, accept, stage_on, N, NSEG, S, bN, alpha_w, p.K, p.k, pxh, puh, ck,
+            ro_replay<T, NX, NU, MODEL, 1, 2, false>(model, c, ind, valid, accept, stage_on, N, NSEG, S, bN, alpha_w, Kb, p.K_st, p.k, pxh, puh, ck,
                                                      stage, uoff, c_aug, GL, p.x_out, p.u_out);
     } else if (x_early) {
         ro_xreplay<T, NX, NU, MODEL>(model, c, ind, N, NSEG, S, ck, stage, ustage);

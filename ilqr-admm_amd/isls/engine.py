@@ -121,6 +121,7 @@ class Engine:
         # buffers made on first use, and the argument blocks cached over the engine's buffers
         self._ffrec = self._seg_bufs = self._advance_args = None
         self._rec_lean = False                               # the last gain pass wrote self._ffrec in the lean layout
+        self._rec_shared = False                             # ... as the batch's ONE set of records (the outer driver: records_shared)
         self._outer_args = self._outer_rec = self._outer_seg = self._outer_lin_state = self._outer_log = None
 
     # ---- optional per-kernel-family event timing (bench.py) -------------------------------------------------
@@ -451,12 +452,15 @@ class Engine:
         (which only those passes would read) are not written.  `seg`: the segment plan those passes will use (ff_lin);
         `weights_as_is`: the caller's passes take Qr, Rr as they are, not in the terminal-block form."""
         lin = self.ff_lin(rec, seg, weights_as_is)
-        self._rec_lean = lin is not None
+        self._rec_lean, self._rec_shared = lin is not None, False      # the single launch writes a record per trajectory
         self.kern._call("riccati_gain", self.sfx, self._gain_block(active, rec, lin), _stream_ptr())
 
     def rec_lin(self, rec, seg=None):
         """The hint for a feed-forward pass on `rec` as the last gain pass left it: lean records need the structured form (and
         raise when it does not apply any more), dense ones the dense form."""
+        if rec is not None and self._rec_shared:
+            raise capi.IslsError("the outer driver left one set of records for the whole batch (records_shared), which a feed-forward "
+                                 "pass of its own cannot read: run the gain pass again")
         if rec is None or not self._rec_lean:
             return None
         lin = self.ff_lin(rec, seg)
@@ -464,6 +468,22 @@ class Engine:
             raise capi.IslsError("the gain pass wrote the records in the model-structured layout, which this feed-forward pass cannot "
                                  "read (weights, segments or A, B changed since): run the gain pass again")
         return lin
+
+    @property
+    def records_shared(self):
+        """True when the last gain pass on ff_record() was the outer driver's and it kept ONE set of records for the whole batch:
+        the argument block declared the same A, B, Cxx, Cuu (Cux) for every trajectory -- the double integrator's structured form
+        with one parameter row, batch-shared Hessian tables, the sequential recursion (csrc/capi.hip decides from the same
+        fields).  Only the driver's own passes read that layout."""
+        return self._rec_shared
+
+    def _outer_shares_records(self):
+        a = self._outer_args
+        g, f = a.gain, a.ff
+        return bool(a.J > 0 and not a.skip_gain and self.fast_dims and self._outer_rec is not None and self._outer_seg is None
+                    and g.lin_on and g.lin_model == capi.MODEL_DI and g.lin_par and g.lin_par_sb == 0
+                    and g.Cxx.sb == 0 and g.Cuu.sb == 0 and (not g.Cux.p or g.Cux.sb == 0)
+                    and f.lin_on and f.lin_par_sb == 0)
 
     def feedforward(self, active=None, seg=None, rec=None):
         self.kern._call("riccati_ff", self.sfx, self._ff_block(active, rec, seg, self.rec_lin(rec, seg)), _stream_ptr())
@@ -534,6 +554,7 @@ class Engine:
             self._outer_lin_state = state
         if self._outer_rec is not None:                        # the driver's gain pass leaves the records in this layout
             self._rec_lean = bool(self._outer_args.gain.lin_on)
+            self._rec_shared = self._outer_shares_records()
         self.kern._call("ilqr_admm_outer", self.sfx, self._outer_args, _stream_ptr())
 
     def accept_x_step(self, tol_cost=-1.0, tol_osc=-1.0):

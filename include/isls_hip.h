@@ -138,7 +138,18 @@ typedef struct isls_gain_args {
                             * trajectories per wavefront, so that a wavefront streams one contiguous burst per step;
                             * steps t = N-1 are not written.  Scratch semantics: the places of trajectories that are
                             * inactive (or past the batch in the last wavefront) are overwritten too, with a copy of
-                            * another trajectory's record -- a consumer must use the same `active` mask as this pass   */
+                            * another trajectory's record -- a consumer must use the same `active` mask as this pass.
+                            * SHARED layout (isls_ilqr_admm_outer_* only; the single-kernel entry points always write and read a
+                            * record per trajectory): when the block declares the same inputs for every trajectory -- lin_on with
+                            * ISLS_MODEL_DI and lin_par_sb == 0, Cxx.sb == 0, Cuu.sb == 0, Cux.p == NULL or Cux.sb == 0 -- and the
+                            * driver's own feed-forward passes (ff.rec == rec, same hint, sequential: no segments) and line
+                            * searches read these records, K_t and fac_t are the same for the whole batch and the driver keeps
+                            * ONE set of lean records: written by the first wavefront alone (its T slots hold identical copies;
+                            * the other wavefronts compute the same values and skip the record stores), read by every
+                            * trajectory's feed-forward pass and line search from slot 0 of block 0.  Decided from these declared
+                            * strides and hints, never from addresses or values.  K [B,N,m,n] is still written for every active
+                            * trajectory; k, status and the `active` semantics are per trajectory as before.  After such a call
+                            * the buffer holds nothing a pass outside the driver could read                                    */
     int32_t lin_on;        /* != 0 (rec given, Quu / fac / Qux NULL; else ISLS_ERR_UNSUPPORTED): A and Bm are what isls_linearize_*
                             * wrote for `lin_model`.  The records are then written LEAN -- [K | fac | model words] only, at their own
                             * dense stride in the same buffer -- for feed-forward passes with the same hint (isls_ff_args.lin_on); a
