@@ -147,6 +147,7 @@ ISLS_ENTRY(accept_step, isls_accept_args, launch_accept, a->B == 0)
 ISLS_ENTRY(project_rows, isls_project_args, launch_project, false)
 ISLS_ENTRY(sls_admm, isls_sls_admm_args, launch_sls_admm, false)
 ISLS_ENTRY(dense_closed_loop, isls_dense_loop_args, launch_dense_closed_loop, false)
+ISLS_ENTRY(mc_closed_loop, isls_mc_loop_args, launch_mc_closed_loop, false)
 ISLS_ENTRY(sls_controller, isls_sls_controller_args, launch_sls_controller, false)
 ISLS_ENTRY(columns_rollout, isls_columns_args, launch_columns_rollout, false)
 ISLS_ENTRY(columns_admm, isls_columns_admm_args, launch_columns_admm, false)
@@ -172,6 +173,11 @@ ISLS_TYPED_PAIR(reduce_convergence_table, (int32_t B, const void *cost, const vo
                 return launch_reduce<T>(B, cost, res, active, status, table, (hipStream_t)stream, rank, world);)
 
 ISLS_API int64_t isls_sls_controller_work_elems(int32_t B, int32_t N, int32_t n) { return sls_controller_work_elems(B, N, n); }
+
+ISLS_API int64_t isls_mc_work_elems(int32_t P, int32_t M, int32_t N, int32_t n, int32_t m, int32_t K_form)
+{
+    return mc_work_elems(P, M, N, n, m, K_form);
+}
 
 ISLS_API int32_t isls_ff_segments(int32_t N, int32_t nseg_requested, int32_t *seg_len)
 {

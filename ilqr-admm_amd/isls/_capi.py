@@ -162,6 +162,23 @@ class DenseLoopArgs(C.Structure):
                 ("x0", C.c_void_p), ("x_log", C.c_void_p), ("u_log", C.c_void_p)]
 
 
+class McLoopArgs(C.Structure):
+    """isls_mc_loop_args: the Monte-Carlo closed loop of a batch of controllers (isls/montecarlo.py)"""
+    _fields_ = [("P", C.c_int32), ("M", C.c_int32), ("N", C.c_int32), ("n", C.c_int32), ("m", C.c_int32),
+                ("model", C.c_int32), ("K_form", C.c_int32), ("_pad", C.c_int32),
+                ("model_par", C.c_void_p), ("par_sb", C.c_int64),
+                ("K", C.c_void_p), ("k", C.c_void_p), ("K_sb", C.c_int64), ("k_sb", C.c_int64),
+                ("xhat", C.c_void_p), ("uhat", C.c_void_p), ("xhat_sb", C.c_int64), ("uhat_sb", C.c_int64),
+                ("x0s", C.c_void_p), ("x0", C.c_void_p), ("x0_sb", C.c_int64), ("x0_std", C.c_void_p),
+                ("w", C.c_void_p), ("noise_std", C.c_void_p), ("seed", C.c_uint64),
+                ("problem0", C.c_int32), ("sample0", C.c_int32),
+                ("u_lo", View), ("u_hi", View), ("x_lo", View), ("x_hi", View),
+                ("viol_u", C.c_void_p), ("viol_x", C.c_void_p), ("viol_any", C.c_void_p),
+                ("u_min", C.c_void_p), ("u_max", C.c_void_p), ("x_min", C.c_void_p), ("x_max", C.c_void_p),
+                ("x_log", C.c_void_p), ("u_log", C.c_void_p), ("w_out", C.c_void_p), ("x0_out", C.c_void_p),
+                ("work", C.c_void_p), ("work_elems", C.c_int64)]
+
+
 class SlsControllerArgs(C.Structure):
     _fields_ = [("B", C.c_int32), ("N", C.c_int32), ("n", C.c_int32), ("m", C.c_int32), ("A", View), ("Bm", View),
                 ("PHI_U", C.c_void_p), ("du", C.c_void_p), ("K", C.c_void_p), ("k", C.c_void_p), ("flags", C.c_void_p),
@@ -197,10 +214,10 @@ class AdvanceArgs(C.Structure):
 
 # names every build of the library must export (checked by tests/test_capi_host.py)
 EXPORTED = [f"isls_{k}_{s}" for s in ("f64", "f32") for k in
-            ("riccati_gain", "riccati_ff", "riccati_gain_ff", "riccati_ff_prepare", "rollout_ls", "admm_update", "project_rows", "sls_admm", "sls_closed_loop", "columns_rollout", "columns_admm", "dense_closed_loop", "sls_controller", "expand_quadratic", "linearize",
+            ("riccati_gain", "riccati_ff", "riccati_gain_ff", "riccati_ff_prepare", "rollout_ls", "admm_update", "project_rows", "sls_admm", "sls_closed_loop", "columns_rollout", "columns_admm", "dense_closed_loop", "mc_closed_loop", "sls_controller", "expand_quadratic", "linearize",
              "accept_step", "reduce_convergence", "reduce_convergence_table", "ilqr_admm_outer", "outer_advance", "columns_iteration",
              "user_model_step", "user_cost_value", "user_cost_expand")] + \
-           ["isls_ff_segments", "isls_ff_record_elems", "isls_sls_controller_work_elems", "isls_version", "isls_dims_supported", "isls_dims_generic", "isls_error_string", "isls_timing_create",
+           ["isls_ff_segments", "isls_ff_record_elems", "isls_sls_controller_work_elems", "isls_mc_work_elems", "isls_version", "isls_dims_supported", "isls_dims_generic", "isls_error_string", "isls_timing_create",
             "isls_timing_destroy", "isls_timing_reset", "isls_timing_pause", "isls_timing_read_ms",
             "isls_user_model_create", "isls_user_model_log", "isls_user_model_code", "isls_user_model_load",
             "isls_user_cost_create", "isls_user_cost_log", "isls_user_cost_code", "isls_user_cost_load"]
@@ -236,6 +253,8 @@ def load_hip_library(path=None):
     lib.isls_ff_record_elems.restype = lib.isls_sls_controller_work_elems.restype = C.c_int64
     lib.isls_ff_record_elems.argtypes = [i32, i32, i32, i32]
     lib.isls_sls_controller_work_elems.argtypes = [i32, i32, i32]
+    lib.isls_mc_work_elems.restype = C.c_int64
+    lib.isls_mc_work_elems.argtypes = [i32, i32, i32, i32, i32, i32]
     lib.isls_timing_create.restype = C.c_void_p
     lib.isls_timing_destroy.restype = None
     lib.isls_timing_destroy.argtypes = [C.c_void_p]
@@ -437,6 +456,11 @@ def ff_record_elems(B, N, n, m):
 def sls_controller_work_elems(B, N, n):
     """isls_sls_controller_work_elems: the N(N-1)/2 blocks of Phi_x below its diagonal and xd [N, n], per problem."""
     return B * (N * (N - 1) // 2 * n * n + N * n)
+
+
+def mc_work_elems(P, M, N, n, m, K_form):
+    """isls_mc_work_elems: dx of every (sample, step) of a dense controller's loop, samples padded to whole workgroups."""
+    return P * (-(-M // 128) * 128) * N * n if K_form == 1 else 0
 
 
 def _record(rec, B, N, n, m):
@@ -849,6 +873,10 @@ class Kernels:
 
     def columns_iteration(self, it, sfx, stream=None):
         return self._call("columns_iteration", sfx, it, stream)
+
+    def mc_closed_loop(self, a, sfx, stream=None):
+        """isls_mc_closed_loop on a filled McLoopArgs (isls/montecarlo.py builds it)"""
+        return self._call("mc_closed_loop", sfx, a, stream)
 
     def sls_closed_loop(self, A, Bm, K, k, x0, x_log, u_log, stream=None):
         M, N, n = x_log.shape

@@ -534,6 +534,26 @@ class iSLS(Base):
         x, u = x_log.cpu().numpy().astype(np.float64), u_log.cpu().numpy().astype(np.float64)
         return (x[0], u[0]) if single else (x, u)
 
+    def monte_carlo(self, K, k, samples=None, x0=None, x0_std=None, noise_scale=0.0, seed=0, u_bounds=None, x_bounds=None,
+                    return_trajectories=False, x0s=None, w=None, absolute=False, **chunks):
+        """Monte-Carlo validation of every problem's controller in one launch (isls/montecarlo.py, isls_mc_closed_loop_*):
+        `samples` closed loops of each of the `batch` problems about ITS OWN nominal through the forward model (a built-in
+        descriptor or models.Custom), u_i = K dx + k + uhat_i with dx = x - xhat (absolute=True: u_i = K x + k, the form of
+        get_trajectory_dp).  Initial states x0 + x0_std o z (x0 default: every problem's xhat_0) or explicit x0s [B,M,n];
+        process noise noise_scale o z drawn on the device with `seed`, or explicit w [B,M,N,n].  K, k, the bounds and the
+        result as in SLS.monte_carlo.  A forward model that is a Python callable is refused: no host loop stands behind this."""
+        from . import montecarlo
+        e = self.engine
+        if self._host_model or e.model is None:
+            raise capi.IslsError("monte_carlo runs on the device: set forward_model to an isls.models descriptor (models.Custom for a "
+                                 "model of your own), not a Python callable")
+        xhat, uhat = (None, None) if absolute else (e.xhat, e.uhat)
+        if x0 is None and x0s is None:
+            x0 = e.xhat[:, 0].contiguous()
+        return montecarlo.run(e, e.model, e.model_par, K, k, self.N, self.x_dim, self.u_dim, samples=samples, x0=x0, x0_std=x0_std,
+                              x0s=x0s, noise_scale=noise_scale, w=w, seed=seed, u_bounds=u_bounds, x_bounds=x_bounds, xhat=xhat,
+                              uhat=uhat, problems=self.batch, return_trajectories=return_trajectories, **chunks)
+
     # ---- batch-form iLQR (isls/isls.py:135-228) through the Riccati kernels ---------------------------------------------
     def rollout_batch(self, x_nom, u_nom):
         """Open-loop rollouts from x_nom[0] (isls/isls.py:135-154): u_nom [L,N,m] (or [B,L,N,m]) -> (x_log, u_nom)."""

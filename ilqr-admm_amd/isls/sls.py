@@ -414,6 +414,23 @@ class SLS(Base):
                                stream=torch.cuda.current_stream().cuda_stream)
         return x_log.cpu().numpy().astype(np.float64), u_log.cpu().numpy().astype(np.float64)
 
+    def monte_carlo(self, K, k, samples=None, x0=None, x0_std=None, noise_scale=0.0, seed=0, u_bounds=None, x_bounds=None,
+                    return_trajectories=False, x0s=None, w=None, **chunks):
+        """Monte-Carlo validation of P controllers in one launch (isls/montecarlo.py, isls_mc_closed_loop_*): `samples` closed
+        loops x_{i+1} = A x_i + B u_i + w_i of every controller from x0 + x0_std o z (x0 [n] or [P,n], default 0), process
+        noise noise_scale o z drawn on the device with `seed` -- or explicit x0s [P,M,n] / w [P,M,N,n].  K [N,m,n] / [P,N,m,n]
+        (stage-local gains) or [N m, N n] / [P, N m, N n] (dense causal), k to match; numpy or torch (torch stays on the
+        device).  u_bounds / x_bounds = (lo, hi), each a scalar, [d], [N,d], [P,1,d], [P,N,d] or None.  Returns a
+        MonteCarloResult: viol_u, viol_x, viol_any, u_min, u_max, x_min, x_max (+ x, u, w, x0 with return_trajectories)."""
+        from . import montecarlo
+        e = self.engine
+        par = e._t(np.concatenate([np.asarray(self.A, dtype=np.float64).reshape(-1), np.asarray(self.B, dtype=np.float64).reshape(-1)]))
+        if x0 is None and x0s is None:
+            x0 = np.zeros(self.x_dim)
+        return montecarlo.run(e, capi.MODEL_LTI, par, K, k, self.N, self.x_dim, self.u_dim, samples=samples, x0=x0, x0_std=x0_std,
+                              x0s=x0s, noise_scale=noise_scale, w=w, seed=seed, u_bounds=u_bounds, x_bounds=x_bounds,
+                              return_trajectories=return_trajectories, **chunks)
+
     def get_trajectory_batch(self, x0, us, noise_scale=0):
         """Open loop: the control sequence us [N,m] applied from every initial state x0 [M,n] (isls/sls_base.py:61-74)."""
         K = np.zeros((self.N, self.u_dim, self.x_dim))

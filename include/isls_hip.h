@@ -794,6 +794,71 @@ int isls_user_cost_value_f32(int32_t id, int32_t R, int32_t N, const void *par, 
 int isls_user_cost_expand_f64(const isls_expand_args *a, void *Cux, void *stream);
 int isls_user_cost_expand_f32(const isls_expand_args *a, void *Cux, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Monte-Carlo validation of a batch of controllers: M closed loops of each of P problems through its forward model and its own
+ * controller, from random (or given) initial states and under random (or given) process noise, in one launch
+ * (get_trajectory_sls, isls/isls_base.py:28-42 and isls/sls_base.py:91-105; get_trajectory_dp / _batch, isls/sls_base.py:61-89):
+ *   dx_j = x_j - xhat_j ;  K_form 0:  u_i = (K_i dx_i + k_i) + uhat_i                         K [P,N,m,n],     k [P,N,m]
+ *                          K_form 1:  u_i = ((K [dx_0 .. dx_i, 0 ..])_i + k_i) + uhat_i        K [P, N m, N n], k [P, N m]
+ *   x_{i+1} = f(x_i, u_i) + w_i       (the control first, then the step, then the noise: the reference's order)
+ * Every sum runs over j ascending from 0; entries of a dense K right of block i are never read.  xhat / uhat NULL: 0 (absolute
+ * form).  A batch stride (`_sb`, in elements) of 0 shares the operand over the problems: K_sb == k_sb == 0 is one controller for
+ * all of them.  model / model_par / par_sb as in isls_dense_loop_args / isls_rollout_args (built-in ids, user-model ids); the
+ * families of csrc/families.def run at their own dimensions, ISLS_MODEL_LTI (par = [A(n*n), B(n*m)]) at any n <= 16, m <= 8.
+ * Initial states: x0s [P,M,n] (explicit), or x0 [P,n] (stride x0_sb) with x0_std [n] (nullable: no spread):
+ *   x0 = mean + x0_std o z.  Noise: none, w [P,M,N,n] (explicit; w_{N-1} is read and unused), or noise_std [n] with `seed`:
+ *   w_i = noise_std o z.  The normals z are Philox4x32-10 / Box-Muller draws that depend on (seed, problem0 + problem,
+ *   sample0 + sample, step, coordinate) only -- not on the launch shape or on how a caller cuts P or M into chunks: the layout is
+ *   part of this ABI, written out in csrc/philox.hpp.  The normals are fp64; the _f32 entry point rounds std * z and
+ *   mean + std * z once.  32-bit uniforms cut the tails at about 6.8 sigma.
+ * Bounds (views [.,.,m] / [.,.,n]; each nullable: that side is free; sb / st = 0 shares them over problems / steps) and the
+ * statistics, each nullable:
+ *   viol_u int32 [P,N,m], viol_x int32 [P,N,n]: samples with u_i[c] < u_lo or > u_hi (x likewise) at that step and coordinate;
+ *   viol_any int32 [P]: samples with any violation anywhere (of the bounds given);
+ *   u_min, u_max [P,N,m], x_min, x_max [P,N,n]: extrema over the samples.
+ *   They are ACCUMULATED (integer atomic adds, atomic min / max: order-independent, the same bits whatever the launch shape):
+ *   THE CALLER ZEROES THE COUNTS and sets the minima to +inf, the maxima to -inf before the first launch; chunks over M add up.
+ * Trajectories, each nullable (all NULL: statistics only): x_log [P,M,N,n], u_log [P,M,N,m], w_out [P,M,N,n] (the noise used;
+ * written only when there is noise), x0_out [P,M,n].
+ * work: caller-owned scratch of isls_mc_work_elems(...) elements (0 for K_form 0), opaque; work_elems its size.
+ * ISLS_ERR_ARG before any launch: a NULL model_par / K / k, both or neither of x0s and x0 (or x0s with x0_std), w together with
+ * noise_std, P < 0, M < 0, N < 1, n outside [1,16], m outside [1,8], K_form not 0 / 1, a negative stride, K_form 1 with work
+ * NULL or work_elems too small.  ISLS_ERR_UNSUPPORTED: a model without a kernel at (n, m).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct isls_mc_loop_args {
+    int32_t P, M, N, n, m;
+    int32_t model;
+    int32_t K_form;
+    int32_t _pad;
+    const void *model_par;
+    int64_t par_sb;
+    const void *K, *k;
+    int64_t K_sb, k_sb;
+    const void *xhat, *uhat;        /* [.,N,n], [.,N,m] nullable */
+    int64_t xhat_sb, uhat_sb;
+    const void *x0s;                /* [P,M,n], or NULL with: */
+    const void *x0;                 /* [.,n] mean */
+    int64_t x0_sb;
+    const void *x0_std;             /* [n] nullable */
+    const void *w;                  /* [P,M,N,n] nullable */
+    const void *noise_std;          /* [n] nullable */
+    uint64_t seed;
+    int32_t problem0, sample0;      /* counter offsets of this launch's first problem / sample (a caller's chunks) */
+    isls_view u_lo, u_hi;           /* [.,.,m] */
+    isls_view x_lo, x_hi;           /* [.,.,n] */
+    int32_t *viol_u, *viol_x, *viol_any;
+    void *u_min, *u_max, *x_min, *x_max;
+    void *x_log, *u_log, *w_out, *x0_out;
+    void *work;
+    int64_t work_elems;
+} isls_mc_loop_args;
+
+/* elements of the scratch buffer of isls_mc_closed_loop_* (0 for K_form 0 and for invalid dimensions) */
+int64_t isls_mc_work_elems(int32_t P, int32_t M, int32_t N, int32_t n, int32_t m, int32_t K_form);
+
+int isls_mc_closed_loop_f64(const isls_mc_loop_args *a, void *stream);
+int isls_mc_closed_loop_f32(const isls_mc_loop_args *a, void *stream);
+
 int isls_version(void);
 /* 1 when the kernels are instantiated for state dimension n and control dimension m (the pairs are compile-time template
  * arguments: csrc/isls_common.hpp ISLS_FOR_EACH_DIMS), else 0: every entry point returns ISLS_ERR_UNSUPPORTED for other pairs. */
