@@ -154,6 +154,7 @@ ISLS_ENTRY(columns_admm, isls_columns_admm_args, launch_columns_admm, false)
 ISLS_ENTRY(columns_iteration, isls_columns_iteration_args, launch_columns_iteration, false)
 ISLS_ENTRY(outer_advance, isls_advance_args, launch_advance, false)
 ISLS_ENTRY(ilqr_admm_outer, isls_outer_args, outer_iteration, false)
+ISLS_ENTRY(reg_update, isls_reg_update_args, launch_reg_update, false)
 
 ISLS_TYPED_PAIR(riccati_gain_ff, (const isls_gain_args *g, const isls_ff_args *ff, void *stream),
                 if (!g || !ff) return ISLS_ERR_ARG;
@@ -161,6 +162,9 @@ ISLS_TYPED_PAIR(riccati_gain_ff, (const isls_gain_args *g, const isls_ff_args *f
                 bool done = false;
                 const int rc = launch_gain<T>(*g, (hipStream_t)stream, ff, &done, /*require_ff=*/true);
                 return rc != ISLS_OK ? rc : (done ? ISLS_OK : ISLS_ERR_UNSUPPORTED);)
+ISLS_TYPED_PAIR(riccati_gain_reg, (const isls_gain_args *g, const isls_ff_args *ff, const isls_reg_args *r, void *stream),
+                if (!g || !r) return ISLS_ERR_ARG;
+                return launch_gain_reg<T>(*g, (hipStream_t)stream, ff, *r);)
 ISLS_TYPED_PAIR(sls_closed_loop, (int32_t M, int32_t N, int32_t n, int32_t m, const void *A, const void *B, const void *K, const void *k,
                                   const void *x0, void *x_log, void *u_log, void *stream),
                 return launch_sls_closed_loop<T>(M, N, n, m, A, B, K, k, x0, x_log, u_log, (hipStream_t)stream);)

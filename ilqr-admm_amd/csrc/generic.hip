@@ -28,9 +28,13 @@ struct GenGainP {
     T *K, *Quu, *fac, *Qux;
     int32_t *status;
     const int32_t *active;
+    const T *reg_mu;               // REG form (isls_reg_args): mu[B] on the diagonal of Cuu_t (reg_on_x: and of Cxx_t), t <= N-2
+    int reg_on_x;
 };
 
-template <typename T>
+// REG (isls_riccati_gain_reg_*): the pass on Cuu_t + mu_b I (and Cxx_t + mu_b I): the term enters the diagonal words of Quu / Qxx
+// in LDS with the cost entry, ahead of the product (the roundings of a pass on materialised tables)
+template <typename T, bool REG = false>
 __global__ __launch_bounds__(64) void gain_generic_kernel(GenGainP<T> p)
 {
     constexpr int MN = kGenMaxN, MM = kGenMaxM;
@@ -41,6 +45,8 @@ __global__ __launch_bounds__(64) void gain_generic_kernel(GenGainP<T> p)
     if (p.active && p.active[b] == 0) return;
     const int N = p.N, n = p.n, m = p.m;
     const int64_t bN = (int64_t)b * N;
+    T mu_u = T(0), mu_x = T(0);
+    if constexpr (REG) { mu_u = p.reg_mu[b]; mu_x = p.reg_on_x ? mu_u : T(0); }
     for (int e = tid; e < m * n; e += kWave) { p.K[(bN + N - 1) * m * n + e] = T(0); p.Qux[(bN + N - 1) * m * n + e] = T(0); }
     for (int e = tid; e < m * m; e += kWave) { p.Quu[(bN + N - 1) * m * m + e] = T(0); p.fac[(bN + N - 1) * m * m + e] = T(0); }
     {
@@ -72,7 +78,8 @@ __global__ __launch_bounds__(64) void gain_generic_kernel(GenGainP<T> p)
             const int i = e / n, j = e - i * n;
             T s = T(0);
             for (int k = 0; k < n; ++k) s += AtV[i * n + k] * As[k * n + j];
-            Qxx[e] = Cxx[e] + s;
+            if constexpr (REG) Qxx[e] = (i == j ? Cxx[e] + mu_x : Cxx[e]) + s;
+            else Qxx[e] = Cxx[e] + s;
         }
         for (int e = tid; e < m * n; e += kWave) {
             const int r = e / n, j = e - r * n;
@@ -84,7 +91,8 @@ __global__ __launch_bounds__(64) void gain_generic_kernel(GenGainP<T> p)
             const int r = e / m, c = e - r * m;
             T s = T(0);
             for (int k = 0; k < n; ++k) s += BtV[r * n + k] * Bs[k * m + c];
-            Quu[e] = Cuu[e] + s;
+            if constexpr (REG) Quu[e] = (r == c ? Cuu[e] + mu_u : Cuu[e]) + s;
+            else Quu[e] = Cuu[e] + s;
         }
         __syncthreads();
         if (tid == 0) {                                            // upper Cholesky Quu = U'U (column order of dpotf2 'U')
@@ -163,7 +171,7 @@ __global__ __launch_bounds__(64) void gain_generic_kernel(GenGainP<T> p)
 }
 
 template <typename T>
-int launch_gain_generic(const isls_gain_args &a, hipStream_t s)
+int launch_gain_generic(const isls_gain_args &a, hipStream_t s, const isls_reg_args *reg)
 {
     if (!dims_generic(a.n, a.m)) return ISLS_ERR_UNSUPPORTED;
     if (a.rec || !a.Quu || !a.fac || !a.Qux) return ISLS_ERR_UNSUPPORTED;      // array form only: no packed records here
@@ -172,11 +180,13 @@ int launch_gain_generic(const isls_gain_args &a, hipStream_t s)
     p.A = View<T>(a.A); p.Bm = View<T>(a.Bm); p.Cxx = View<T>(a.Cxx); p.Cuu = View<T>(a.Cuu); p.Cux = View<T>(a.Cux);
     p.K = (T *)a.K; p.Quu = (T *)a.Quu; p.fac = (T *)a.fac; p.Qux = (T *)a.Qux;
     p.status = a.status; p.active = a.active;
-    hipLaunchKernelGGL((gain_generic_kernel<T>), dim3(a.B), dim3(64), 0, s, p);
+    p.reg_mu = reg ? (const T *)reg->mu : nullptr; p.reg_on_x = reg ? reg->on_x : 0;
+    if (reg) hipLaunchKernelGGL((gain_generic_kernel<T, true>), dim3(a.B), dim3(64), 0, s, p);
+    else hipLaunchKernelGGL((gain_generic_kernel<T>), dim3(a.B), dim3(64), 0, s, p);
     return check_launch();
 }
-template int launch_gain_generic<double>(const isls_gain_args &, hipStream_t);
-template int launch_gain_generic<float>(const isls_gain_args &, hipStream_t);
+template int launch_gain_generic<double>(const isls_gain_args &, hipStream_t, const isls_reg_args *);
+template int launch_gain_generic<float>(const isls_gain_args &, hipStream_t, const isls_reg_args *);
 
 // ------------------------------------------------------------------------------------------------------------------------
 // Feed-forward pass (isls/isls.py:285-302, isls/sls.py:168-202) on the arrays of the gain pass.

@@ -281,7 +281,11 @@ template <typename T> int launch_accept(const isls_accept_args &a, hipStream_t s
 template <typename T> int launch_advance(const isls_advance_args &a, hipStream_t s);
 // any (n <= 16, m <= 8) without an instantiation of the fast kernels: generic.hip (array form, one trajectory per wavefront)
 bool dims_generic(int n, int m);
-template <typename T> int launch_gain_generic(const isls_gain_args &a, hipStream_t s);
+template <typename T> int launch_gain_generic(const isls_gain_args &a, hipStream_t s, const isls_reg_args *reg = nullptr);
+// regularize.hip: the gain pass on Cuu + mu I (isls_riccati_gain_reg_*; ff != nullptr: with the first feed-forward pass inside, or
+// ISLS_ERR_UNSUPPORTED) and the per-trajectory mu / delta schedule (isls_reg_update_*)
+template <typename T> int launch_gain_reg(const isls_gain_args &a, hipStream_t s, const isls_ff_args *ff, const isls_reg_args &reg);
+template <typename T> int launch_reg_update(const isls_reg_update_args &a, hipStream_t s);
 template <typename T> int launch_ff_generic(const isls_ff_args &a, hipStream_t s);
 template <typename T> int launch_rollout_generic(const isls_rollout_args &a, hipStream_t s);
 template <typename T> int launch_reduce(int32_t B, const void *cost, const void *res, const int32_t *active,

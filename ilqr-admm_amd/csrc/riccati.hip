@@ -41,6 +41,8 @@ struct GainP {
     T *kff;
     const T *lin_par;              // LIN form (isls_gain_args.lin_on): the model's parameters, batch stride lin_par_sb
     int64_t lin_par_sb;
+    const T *reg_mu;               // REG form (isls_reg_args): mu[B], added to the diagonal of Cuu_t (reg_on_x: and of Cxx_t), t <= N-2
+    int reg_on_x;
 };
 
 // 1/sqrt(a) by v_rsq + two coupled Newton steps (g -> sqrt(a), h -> 1/(2 sqrt(a))): 9 instructions against the ~30 of
@@ -119,6 +121,11 @@ __device__ __forceinline__ bool chol_upper_rd(const T (&A)[M][M], T (&U)[M][M], 
 // of the loop picked once per wavefront (RS), not a predicate on the stores.  K, k and status stay per trajectory.  Block 0 must
 // write the records even when none of its trajectories is active: it then runs the recursion on trajectory 0's operands
 // (loads only) and aims the K / k stores at spare words of the record buffer behind its own run.
+// REG (isls_riccati_gain_reg_*): the pass runs on Cuu_t + mu_b I (reg_on_x: and Cxx_t + mu_b I) for t <= N-2 -- the lane that owns
+// row i of the stack adds its trajectory's mu to its own diagonal word of the cost row, crow[i], before the row enters the sums,
+// so the factorisation, the V update, A + B K, the records and the feed-forward recursion inside all see the regularised block
+// (the same roundings as a pass on materialised tables).  mu_b is loaded once per slot ahead of the step loop; a slot without
+// a trajectory of its own takes the mu of the one it shadows (exact copies, as above).  Dense LIN = 0 forms only.
 // (words of the slots' LDS records: the kernel declares them, the body checks the count against its layout)
 template <int NX, int NU>
 __host__ __device__ constexpr int gain_lds_words(bool ff)
@@ -126,9 +133,10 @@ __host__ __device__ constexpr int gain_lds_words(bool ff)
     constexpr int W = NX + NU;
     return (kWave / W) * ((NX * NX + NX * W + NU * W + NU * NX + (ff ? 2 * W + NX + 2 * NU : W)) | 1);   // TPW slots, see the body
 }
-template <typename T, int NX, int NU, int D, int MODE, bool FF, bool REC, bool ARR, int LIN, bool RL, bool SH, bool RS>
+template <typename T, int NX, int NU, int D, int MODE, bool FF, bool REC, bool ARR, int LIN, bool RL, bool SH, bool RS, bool REG = false>
 __device__ __forceinline__ void riccati_gain_body(const GainP<T> &p, T *lds, T *img)
 {
+    static_assert(!REG || (LIN == 0 && !RL && !SH), "regularised pass: the dense forms with a record per trajectory");
     static_assert(LIN == 0 || NX == 2 * NU, "double integrator: n = 2 d, m = d");
     static_assert(!RL || (REC && !ARR), "lean records: record form without the Quu / fac / Qux arrays");
     static_assert(!SH || (REC && !ARR), "shared records: record form without the Quu / fac / Qux arrays");
@@ -196,6 +204,8 @@ __device__ __forceinline__ void riccati_gain_body(const GainP<T> &p, T *lds, T *
     const int64_t a_st = p.A.st, b_st = p.Bm.st;
     const T zmask = (xl || has_cux) ? T(1) : T(0);            // Cux absent -> 0
     const T xmask = xl ? T(1) : T(0);
+    T reg_l = T(0);                                            // REG form: what this lane adds to its diagonal word
+    if constexpr (REG) reg_l = (!xl || p.reg_on_x) ? p.reg_mu[bb] : T(0);
     // LIN form: the lane's column of [A B] (see the kernel's head)
     T l_a = T(0), l_b0 = T(0), l_b1 = T(0), l_c1 = T(0), l_c2 = T(0), colc[NX];
     int l_r1 = 0, l_r2 = 0;
@@ -532,8 +542,16 @@ __device__ __forceinline__ void riccati_gain_body(const GainP<T> &p, T *lds, T *
             if constexpr (flush_prev) send_at(t + 1, std::integral_constant<int, NX + k>{});
         });
         }
+        if constexpr (REG) {
+#pragma unroll
+            for (int c = 0; c < W; ++c) {                      // the lane's diagonal word of [Cxx; Cux Cuu] is crow[i]
+                const T cv = (c == i) ? g.crow[c] + reg_l : g.crow[c];
+                M[c] = (c < NX) ? fma(cv, zmask, M[c]) : cv + M[c];
+            }
+        } else {
 #pragma unroll
         for (int c = 0; c < W; ++c) M[c] = (c < NX) ? fma(g.crow[c], zmask, M[c]) : g.crow[c] + M[c];   // one rounding either way
+        }
         __builtin_amdgcn_sched_barrier(0);
         fetch(t - RD > 0 ? t - RD : 0, g);                     // refill this ring entry (clamped, unconditional): ~RD - 0.5 steps ahead
         // (3) u-lanes publish their row of [Qux Quu] (x-lanes write the dump words)
@@ -742,7 +760,7 @@ __device__ __forceinline__ void riccati_gain_body(const GainP<T> &p, T *lds, T *
     if (valid && i == 0 && !pd_ok && p.status) atomicOr(&p.status[b], ISLS_ST_NOT_PD);
 }
 
-template <typename T, int NX, int NU, int D, int MODE, bool FF, bool REC, bool ARR, int LIN = 0, bool RL = (LIN == 1), bool SH = false>
+template <typename T, int NX, int NU, int D, int MODE, bool FF, bool REC, bool ARR, int LIN = 0, bool RL = (LIN == 1), bool SH = false, bool REG = false>
 __global__ __launch_bounds__(64, ISLS_GAIN_OCC) void riccati_gain_kernel(GainP<T> p)
 {
     __shared__ T lds[gain_lds_words<NX, NU>(FF)];
@@ -751,7 +769,7 @@ __global__ __launch_bounds__(64, ISLS_GAIN_OCC) void riccati_gain_kernel(GainP<T
         if (blockIdx.x == 0) riccati_gain_body<T, NX, NU, D, MODE, FF, REC, ARR, LIN, RL, true, true>(p, lds, img);
         else riccati_gain_body<T, NX, NU, D, MODE, FF, REC, ARR, LIN, RL, true, false>(p, lds, img);
     } else {
-        riccati_gain_body<T, NX, NU, D, MODE, FF, REC, ARR, LIN, RL, false, true>(p, lds, img);
+        riccati_gain_body<T, NX, NU, D, MODE, FF, REC, ARR, LIN, RL, false, true, REG>(p, lds, img);
     }
 }
 
@@ -759,22 +777,53 @@ __global__ __launch_bounds__(64, ISLS_GAIN_OCC) void riccati_gain_kernel(GainP<T
 // into scratch memory: the first feed-forward pass then stays a launch of its own)
 constexpr bool gain_ff_dims(int n, int m) { return n * n + n * (n + m) <= 100; }
 
-template <typename T>
-int launch_gain(const isls_gain_args &a, hipStream_t s, const isls_ff_args *ff, bool *did_ff, bool require_ff, bool shared)
+// what both launchers check and fill before they pick a kernel
+inline int gain_args_check(const isls_gain_args &a)
 {
-    if (did_ff) *did_ff = false;
     if (a.B < 0 || a.N < 1 || !a.A.p || !a.Bm.p || !a.Cxx.p || !a.Cuu.p || !a.K) return ISLS_ERR_ARG;
     // Quu, fac, Qux: all three or none; none only with records (every consumer then reads those)
     if ((!a.Quu || !a.Qux || !a.fac) && (!a.rec || a.Quu || a.Qux || a.fac)) return ISLS_ERR_ARG;
     if (a.solve_mode != ISLS_SOLVE_CHOL && a.solve_mode != ISLS_SOLVE_INV) return ISLS_ERR_ARG;
-    if (a.B == 0) return ISLS_OK;
-    if (!dims_supported(a.n, a.m)) return require_ff ? ISLS_OK : launch_gain_generic<T>(a, s);   // generic.hip (no ff pass inside)
-    GainP<T> p;
+    return ISLS_OK;
+}
+template <typename T>
+inline void gain_args_fill(const isls_gain_args &a, GainP<T> &p)
+{
     p.B = a.B; p.N = a.N; p.mode = a.solve_mode;
     p.A = View<T>(a.A); p.Bm = View<T>(a.Bm); p.Cxx = View<T>(a.Cxx); p.Cuu = View<T>(a.Cuu); p.Cux = View<T>(a.Cux);
     p.K = (T *)a.K; p.Quu = (T *)a.Quu; p.fac = (T *)a.fac; p.Qux = (T *)a.Qux; p.rec = (T *)a.rec;
     p.status = a.status; p.active = a.active;
     p.xhat = p.uhat = p.zx = p.lx = p.zu = p.lu = nullptr; p.kff = nullptr;
+    p.lin_par = nullptr; p.lin_par_sb = 0;
+    p.reg_mu = nullptr; p.reg_on_x = 0;
+}
+// the first feed-forward pass rides along when it would run on this pass's records with time-invariant Qr / Rr rows
+inline bool gain_ff_rides(const isls_gain_args &a, const isls_ff_args *ff)
+{
+    return ff && gain_ff_dims(a.n, a.m) && a.rec && ff->rec == a.rec && ff->k && ff->B == a.B && ff->N == a.N && ff->n == a.n && ff->m == a.m &&
+           ff->solve_mode == a.solve_mode && ff->active == a.active && ff->c0x.p && ff->c0u.p &&
+           (!ff->Qr.p || ff->Qr.st == 0) && (!ff->Rr.p || ff->Rr.st == 0) && (!ff->Qr.p || (ff->zx && ff->lx)) &&
+           (!ff->Rr.p || (ff->zu && ff->lu)) && !a.Qux && !ff->Qr_term && ff->_pad <= 1;
+}
+template <typename T>
+inline void gain_ff_fill(const isls_ff_args *ff, GainP<T> &p)
+{
+    p.c0x = View<T>(ff->c0x); p.c0u = View<T>(ff->c0u); p.Qr = View<T>(ff->Qr); p.Rr = View<T>(ff->Rr);
+    p.xhat = (const T *)ff->xhat; p.uhat = (const T *)ff->uhat;
+    p.zx = (const T *)ff->zx; p.lx = (const T *)ff->lx; p.zu = (const T *)ff->zu; p.lu = (const T *)ff->lu;
+    p.kff = (T *)ff->k;
+}
+
+#ifndef ISLS_GAIN_REG_TU
+template <typename T>
+int launch_gain(const isls_gain_args &a, hipStream_t s, const isls_ff_args *ff, bool *did_ff, bool require_ff, bool shared)
+{
+    if (did_ff) *did_ff = false;
+    if (const int rc = gain_args_check(a); rc != ISLS_OK) return rc;
+    if (a.B == 0) return ISLS_OK;
+    if (!dims_supported(a.n, a.m)) return require_ff ? ISLS_OK : launch_gain_generic<T>(a, s);   // generic.hip (no ff pass inside)
+    GainP<T> p;
+    gain_args_fill(a, p);
     // model-structured form (isls_gain_args.lin_on): on the record forms the drivers use; the caller switches it off by not
     // giving the hint (isls.Engine.use_model_structure, for the gain pass and its readers together)
     if (ff && ff->rec == a.rec && a.rec && (ff->lin_on != 0) != (a.lin_on != 0)) return ISLS_ERR_ARG;   // one layout for writer and reader
@@ -790,18 +839,9 @@ int launch_gain(const isls_gain_args &a, hipStream_t s, const isls_ff_args *ff, 
     p.lin_par = (const T *)a.lin_par; p.lin_par_sb = a.lin_par_sb;
     // shared records (gain_inputs_shared): the structured double-integrator form has them; the caller's readers rely on it
     if (shared && (!lin_di || !gain_inputs_shared(a) || !dims_supported(a.n, a.m))) return ISLS_ERR_ARG;
-    // the first feed-forward pass rides along when it would run on this pass's records with time-invariant Qr / Rr rows
-    const bool with_ff = ff && gain_ff_dims(a.n, a.m) && a.rec && ff->rec == a.rec && ff->k && ff->B == a.B && ff->N == a.N && ff->n == a.n && ff->m == a.m &&
-                         ff->solve_mode == a.solve_mode && ff->active == a.active && ff->c0x.p && ff->c0u.p &&
-                         (!ff->Qr.p || ff->Qr.st == 0) && (!ff->Rr.p || ff->Rr.st == 0) && (!ff->Qr.p || (ff->zx && ff->lx)) &&
-                         (!ff->Rr.p || (ff->zu && ff->lu)) && !a.Qux && !ff->Qr_term && ff->_pad <= 1;
+    const bool with_ff = gain_ff_rides(a, ff);
     if (require_ff && !with_ff) return ISLS_OK;
-    if (with_ff) {
-        p.c0x = View<T>(ff->c0x); p.c0u = View<T>(ff->c0u); p.Qr = View<T>(ff->Qr); p.Rr = View<T>(ff->Rr);
-        p.xhat = (const T *)ff->xhat; p.uhat = (const T *)ff->uhat;
-        p.zx = (const T *)ff->zx; p.lx = (const T *)ff->lx; p.zu = (const T *)ff->zu; p.lu = (const T *)ff->lu;
-        p.kff = (T *)ff->k;
-    }
+    if (with_ff) gain_ff_fill(ff, p);
 #define LAUNCH_G(NX_, NU_, MODE_, FF_, REC_, ARR_) \
     hipLaunchKernelGGL((riccati_gain_kernel<T, NX_, NU_, kGainDepth, MODE_, FF_, REC_, ARR_>), dim3(grid), dim3(64), 0, s, p)
 #define LAUNCH_GL(NX_, NU_, MODE_, FF_) \
@@ -846,6 +886,7 @@ int launch_gain(const isls_gain_args &a, hipStream_t s, const isls_ff_args *ff, 
 }
 template int launch_gain<double>(const isls_gain_args &, hipStream_t, const isls_ff_args *, bool *, bool, bool);
 template int launch_gain<float>(const isls_gain_args &, hipStream_t, const isls_ff_args *, bool *, bool, bool);
+#endif  // ISLS_GAIN_REG_TU
 
 
 }  // namespace isls

@@ -11,6 +11,7 @@ from .admm import ADMM  # noqa: F401
 from .utils import get_double_integrator_AB, find_mus, find_precs  # noqa: F401
 from .projections import *  # noqa: F401,F403
 from .projections import Box, identify_box  # noqa: F401
+from .regularization import Regularization  # noqa: F401
 
 
 def __getattr__(name):

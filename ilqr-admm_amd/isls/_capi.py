@@ -19,7 +19,8 @@ except Exception:  # pragma: no cover
 
 ABI_VERSION = 107            # ISLS_VERSION of include/isls_hip.h these ctypes structs mirror
 OK, ERR_ARG, ERR_UNSUPPORTED, ERR_LAUNCH, ERR_COMPILE = 0, -1, -2, -3, -4
-ST_NOT_PD, ST_NAN_COST, ST_LS_REJECT = 1, 2, 4
+ST_NOT_PD, ST_NAN_COST, ST_LS_REJECT, ST_REG_MAX = 1, 2, 4, 8
+REG_AFTER_GAIN, REG_AFTER_LS = 0, 1             # isls_reg_update_args.mode
 SOLVE_CHOL, SOLVE_INV = 0, 1
 MODEL_LTI, MODEL_ARM3R, MODEL_CAR, MODEL_DI, MODEL_TASSA = 0, 1, 2, 3, 4
 MODEL_USER_BASE, USER_MAX_PAR = 1024, 16      # ids of user models (isls_user_model_create), parameters per model at most
@@ -45,6 +46,18 @@ class GainArgs(C.Structure):
                 ("K", C.c_void_p), ("Quu", C.c_void_p), ("fac", C.c_void_p), ("Qux", C.c_void_p),
                 ("status", C.c_void_p), ("active", C.c_void_p), ("rec", C.c_void_p),
                 ("lin_on", C.c_int32), ("lin_model", C.c_int32), ("lin_par", C.c_void_p), ("lin_par_sb", C.c_int64)]
+
+
+class RegArgs(C.Structure):
+    """isls_reg_args: per-trajectory mu of the regularised gain pass"""
+    _fields_ = [("mu", C.c_void_p), ("on_x", C.c_int32), ("_pad", C.c_int32)]
+
+
+class RegUpdateArgs(C.Structure):
+    """isls_reg_update_args: the mu / delta schedule"""
+    _fields_ = [("B", C.c_int32), ("mode", C.c_int32), ("status", C.c_void_p), ("active", C.c_void_p),
+                ("mu", C.c_void_p), ("delta", C.c_void_p), ("retry", C.c_void_p), ("count", C.c_void_p),
+                ("factor", C.c_double), ("mu_min", C.c_double), ("mu_max", C.c_double)]
 
 
 class FfSeg(C.Structure):
@@ -216,7 +229,7 @@ class AdvanceArgs(C.Structure):
 EXPORTED = [f"isls_{k}_{s}" for s in ("f64", "f32") for k in
             ("riccati_gain", "riccati_ff", "riccati_gain_ff", "riccati_ff_prepare", "rollout_ls", "admm_update", "project_rows", "sls_admm", "sls_closed_loop", "columns_rollout", "columns_admm", "dense_closed_loop", "mc_closed_loop", "sls_controller", "expand_quadratic", "linearize",
              "accept_step", "reduce_convergence", "reduce_convergence_table", "ilqr_admm_outer", "outer_advance", "columns_iteration",
-             "user_model_step", "user_cost_value", "user_cost_expand")] + \
+             "user_model_step", "user_cost_value", "user_cost_expand", "riccati_gain_reg", "reg_update")] + \
            ["isls_ff_segments", "isls_ff_record_elems", "isls_sls_controller_work_elems", "isls_mc_work_elems", "isls_version", "isls_dims_supported", "isls_dims_generic", "isls_error_string", "isls_timing_create",
             "isls_timing_destroy", "isls_timing_reset", "isls_timing_pause", "isls_timing_read_ms",
             "isls_user_model_create", "isls_user_model_log", "isls_user_model_code", "isls_user_model_load",
@@ -704,6 +717,23 @@ class Kernels:
     def riccati_gain_ff(self, gain, ff, sfx, stream=None):
         """Gain pass + first feed-forward pass in one launch (argument blocks from gain_args / ff_args)."""
         self._invoke("riccati_gain_ff", sfx, C.byref(gain), C.byref(ff), stream=stream)
+
+    def riccati_gain_reg(self, gain, ff, mu, on_x, sfx, stream=None):
+        """Gain pass on Cuu + mu I (on_x: and Cxx + mu I), mu [B] per trajectory; ff: the first feed-forward pass inside (or None)."""
+        if tuple(mu.shape) != (gain.B,) or _sfx(mu) != sfx or not _contiguous(mu):
+            raise ValueError(f"mu: contiguous [{gain.B}] of the pass's dtype")
+        reg = RegArgs(mu=_ptr(mu), on_x=int(bool(on_x)))
+        self._invoke("riccati_gain_reg", sfx, C.byref(gain), C.byref(ff) if ff is not None else None, C.byref(reg), stream=stream)
+
+    def reg_update(self, mode, status, mu, delta, factor, mu_min, mu_max, active=None, retry=None, count=None, stream=None):
+        """The mu / delta schedule (isls_reg_update_*): mode REG_AFTER_GAIN or REG_AFTER_LS."""
+        B = int(mu.shape[0])
+        for x, name in ((mu, "mu"), (delta, "delta")):
+            if tuple(x.shape) != (B,) or x.dtype != mu.dtype or not _contiguous(x):
+                raise ValueError(f"{name}: contiguous [{B}]")
+        a = RegUpdateArgs(B=B, mode=int(mode), status=_ptr(status), active=_ptr(active), mu=_ptr(mu), delta=_ptr(delta),
+                          retry=_ptr(retry), count=_ptr(count), factor=float(factor), mu_min=float(mu_min), mu_max=float(mu_max))
+        return self._call("reg_update", _sfx(mu), a, stream)
 
     @staticmethod
     def project_args(y_in, y_out, sets, rho=1.0, max_iter=200, threshold=1e-4, iters=None, active=None, cols=None,

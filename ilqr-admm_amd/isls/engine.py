@@ -123,6 +123,11 @@ class Engine:
         self._rec_lean = False                               # the last gain pass wrote self._ffrec in the lean layout
         self._rec_shared = False                             # ... as the batch's ONE set of records (the outer driver: records_shared)
         self._outer_args = self._outer_rec = self._outer_seg = self._outer_lin_state = self._outer_log = None
+        # per-trajectory regularisation of the gain pass (set_regularization): settings, mu, delta, and the retry loop's scratch
+        self.reg = None
+        self.reg_mu, self.reg_delta = z(B), torch.ones(B, dtype=dtype, device=self.device)
+        self._reg_retry, self._reg_count = zi(B), zi(1)
+        self.reg_gain_launches = 0                           # gain launches of the last regularised pass (1 + retries)
 
     # ---- optional per-kernel-family event timing (bench.py) -------------------------------------------------
     def timed(self, name):
@@ -196,6 +201,14 @@ class Engine:
             with torch.cuda.device(self.device):
                 # with a model: the pair's module (line search, expansion, nominal cost); without one yet: expansion and cost
                 capi.user_cost_load(self.cost_model, -1 if self.model is None else self.model, self.dtype)
+
+    def set_regularization(self, reg):
+        """A `Regularization` (or None: the plain passes) for the gain passes from now on; mu restarts at mu_init, delta at 1.
+        While one is set the engine runs the general layout (_structure_applies), as it does for a user cost."""
+        self.reg = reg
+        self.reg_mu.fill_(0.0 if reg is None else reg.mu_init)
+        self.reg_delta.fill_(1.0)
+        self._outer_args = self._advance_args = None
 
     def set_quadratic_cost(self, zs, Qs, seq, u_std):
         """Via-point quadratic cost (Base.set_quadratic_cost, isls/base.py:81-89); zs [nvia,n] or [B,nvia,n]."""
@@ -343,7 +356,7 @@ class Engine:
         every step (Qr: or all but the last, which the passes take as the terminal block Qr_term)."""
         # (a user cost has a full stage Hessian, Cux included, which the structured passes do not take: refused, not guessed)
         return (self.fast_dims and self.use_model_structure and self.model in (capi.MODEL_DI, capi.MODEL_ARM3R, capi.MODEL_CAR)
-                and (self._w_invariant or self._w_terminal) and not self.user_cost)
+                and (self._w_invariant or self._w_terminal) and not self.user_cost and self.reg is None)
 
     def _structure_expected(self):
         """Will the passes of this engine get the model hint, as far as can be told before A, B are linearised: the structured
@@ -453,7 +466,47 @@ class Engine:
         `weights_as_is`: the caller's passes take Qr, Rr as they are, not in the terminal-block form."""
         lin = self.ff_lin(rec, seg, weights_as_is)
         self._rec_lean, self._rec_shared = lin is not None, False      # the single launch writes a record per trajectory
+        if self.reg is not None:
+            self._gain_regularised(active, rec)
+            return
         self.kern._call("riccati_gain", self.sfx, self._gain_block(active, rec, lin), _stream_ptr())
+
+    def _gain_regularised(self, active, rec, ff=None):
+        """The gain pass on Cuu + mu I with the retry loop: pass, schedule (mu rises where Quu was not positive definite, the bit is
+        cleared), read the one counter, launch again while it is non-zero.  Every launch takes the caller's mask, so the records
+        and K of every active trajectory end as one pass given the final mu would leave them (a trajectory that never failed
+        recomputes with its mu unchanged).  A trajectory at the end of the ladder keeps ISLS_ST_NOT_PD and gets ISLS_ST_REG_MAX."""
+        r = self.reg
+        g = self._gain_block(active, rec, None)
+        self.reg_gain_launches = 0
+        while True:
+            self.kern.riccati_gain_reg(g, ff, self.reg_mu, r.on_x, self.sfx, stream=_stream_ptr())
+            self.reg_gain_launches += 1
+            self._reg_count.zero_()
+            self.kern.reg_update(capi.REG_AFTER_GAIN, self.status, self.reg_mu, self.reg_delta, r.factor, r.mu_min, r.mu_max,
+                                 active=active, retry=self._reg_retry, count=self._reg_count, stream=_stream_ptr())
+            if int(self._reg_count.item()) == 0:
+                return
+
+    def backward_pass_regularised(self, active=None):
+        """K and k of one regularised backward sweep, as iterate_once_dp needs them.  On the pairs whose gain pass carries the
+        first feed-forward pass (row-per-lane kernels, n n + n (n + m) <= 100) and with ADMM weights that are the same at every
+        step, both come from the one launch on the packed records (a retry repeats both); otherwise the gain pass on the arrays
+        and the feed-forward pass behind it."""
+        rec = self.ff_record()
+        fused = (rec is not None and self.n * self.n + self.n * (self.n + self.m) <= 100 and self._w_invariant)
+        if not fused:
+            self.gain(active=active)
+            self.feedforward(active=active)
+            return
+        self._rec_lean = self._rec_shared = False
+        self._gain_regularised(active, rec, self._ff_block(active, rec, None, None))
+
+    def reg_after_line_search(self, active=None):
+        """The schedule behind a line search with the acceptance test: mu rises where it was rejected, falls where it was accepted."""
+        r = self.reg
+        self.kern.reg_update(capi.REG_AFTER_LS, self.status, self.reg_mu, self.reg_delta, r.factor, r.mu_min, r.mu_max,
+                             active=active, stream=_stream_ptr())
 
     def rec_lin(self, rec, seg=None):
         """The hint for a feed-forward pass on `rec` as the last gain pass left it: lean records need the structured form (and
@@ -530,12 +583,20 @@ class Engine:
         """Marshal the argument block of isls_ilqr_admm_outer once; it stays valid while buffers are not re-allocated.
         begin_done: the caller ends every outer iteration with `advance()`, which also makes the ADMM restart of the next one."""
         rec = self.ff_record()
-        seg = self.ff_seg(ff_nseg)
+        if self.reg is not None and rec is None:
+            raise capi.IslsError("a regularisation needs the row-per-lane kernels in the outer driver (the generic (x_dim, u_dim) pairs "
+                                 "have no packed records): use solve / iterate_once_dp")
+        # regularised: the gain pass runs ahead of the driver with its retry loop (run_outer), the driver skips its own and reads the
+        # records sequentially (the segment operators would have to be prepared behind that pass)
+        if self.reg is not None and begin_done:
+            raise capi.IslsError("a regularisation and begin_done: the ADMM restart must follow the regularised gain pass, which may "
+                                 "stop trajectories (build_outer(begin_done=False))")
+        seg = None if self.reg is not None else self.ff_seg(ff_nseg)
         lin = self.ff_lin(rec, seg)
         act = self.admm_active
         self._outer_args = capi.OuterArgs(gain=self._gain_block(act, rec, lin), ff=self._ff_block(act, rec, seg, lin),
                                           ro=self._rollout_block(L, act), admm=self._admm_block(tol_abs, tol_rel, act),
-                                          J=int(J), skip_gain=0, begin_done=int(bool(begin_done)), log=capi._ptr(log),
+                                          J=int(J), skip_gain=int(self.reg is not None), begin_done=int(bool(begin_done)), log=capi._ptr(log),
                                           outer_active=capi._ptr(self.outer_active))
         self._outer_rec, self._outer_seg, self._outer_log = rec, seg, log
         self._outer_lin_state = (self._ab_src, self.use_model_structure)
@@ -552,6 +613,14 @@ class Engine:
             for a in (self._outer_args.gain, self._outer_args.ff):
                 capi.Kernels._set_lin(a, lin, self.B, self.dtype)
             self._outer_lin_state = state
+        if self.reg is not None:
+            # the regularised gain pass, with retries, on the driver's records and the mask the driver's passes will use (its start
+            # sets admm_active <- outer_active); a trajectory at the end of the ladder stops here, the others go on
+            self._rec_lean = self._rec_shared = False
+            self._gain_regularised(self.outer_active, self._outer_rec)
+            self.outer_active.mul_(((self.status & capi.ST_NOT_PD) == 0).to(torch.int32))
+            self.kern._call("ilqr_admm_outer", self.sfx, self._outer_args, _stream_ptr())
+            return
         if self._outer_rec is not None:                        # the driver's gain pass leaves the records in this layout
             self._rec_lean = bool(self._outer_args.gain.lin_on)
             self._rec_shared = self._outer_shares_records()

@@ -170,6 +170,18 @@ class iSLS(Base):
         """Per-trajectory status bits (ISLS_ST_*): non-PD Quu, NaN cost, line search rejected."""
         return self.engine.status.cpu().numpy()
 
+    @property
+    def reg_mu(self):
+        """Per-trajectory mu [B] of the regularisation in use (the `regularization=` of the last solver call; zeros without one)."""
+        return self.engine.reg_mu.cpu().numpy()
+
+    def _set_regularization(self, regularization):
+        from .regularization import Regularization
+        if regularization is not None and not isinstance(regularization, Regularization):
+            raise TypeError("regularization must be an isls.Regularization or None")
+        if regularization is not None or self.engine.reg is not None:
+            self.engine.set_regularization(regularization)
+
     def reset(self):
         self.cost_log = []
         self.engine.status.zero_()
@@ -261,13 +273,22 @@ class iSLS(Base):
         x, u = np.stack(xs, axis=1), np.stack(us, axis=1)
         return (x[0], u[0]) if self.batch == 1 else (x, u)
 
-    def iterate_once_dp(self, max_line_search=15, verbose=False, Cts=None, cts=None, _linearized=False):
+    _KEEP = object()                                            # regularization=: leave the engine's setting (and its mu) as it is
+
+    def iterate_once_dp(self, max_line_search=15, verbose=False, Cts=None, cts=None, _linearized=False, regularization=_KEEP):
         """Backward pass + line search over alphas[:max_line_search] with the NaN rule and the acceptance test
-        (isls/isls.py:336-374).  Returns (fp_success, K, k); fp_success is a bool, or a bool array when batched."""
+        (isls/isls.py:336-374).  Returns (fp_success, K, k); fp_success is a bool, or a bool array when batched.
+        regularization: an `isls.Regularization` (mu restarts at mu_init) or None for the plain pass; not given: the setting of the
+        last call stays, with its mu.  With one, a Quu that is not positive definite makes the gain pass run again with a raised
+        mu instead of raising LinAlgError, and mu follows the verdict of the line search."""
         e = self.engine
+        if regularization is not iSLS._KEEP:
+            self._set_regularization(regularization)
         if not _linearized and not self._user_AB:
             self._linearize(None)
         self._expand(Cts, cts)
+        if e.reg is not None:
+            return self._iterate_once_dp_regularised(max_line_search, verbose)
         e.status.zero_()
         e.gain(active=e.outer_active)
         e.feedforward(active=e.outer_active)
@@ -286,11 +307,39 @@ class iSLS(Base):
         self.cost_log.append(self.cost)
         return ok, self.K, self.k
 
+    def _iterate_once_dp_regularised(self, max_line_search, verbose):
+        """iterate_once_dp with a regularisation: gain pass with retries; a trajectory at the end of the ladder stops (outer_active
+        <- 0, ISLS_ST_NOT_PD | ISLS_ST_REG_MAX stay in its status), the others run the line search; then the schedule on its verdict."""
+        e = self.engine
+        e.status.mul_((e.outer_active == 0).to(torch.int32))    # the status of the trajectories still iterating restarts
+        e.backward_pass_regularised(active=e.outer_active)
+        e.outer_active.mul_(((e.status & capi.ST_NOT_PD) == 0).to(torch.int32))
+        self._line_search(max_line_search, flags=capi.RO_NAN_TO_1E5 | capi.RO_ACCEPT_TEST, active=e.outer_active)
+        e.reg_after_line_search(active=e.outer_active)
+        st = e.status.cpu().numpy()
+        ok = (st & (capi.ST_LS_REJECT | capi.ST_NOT_PD)) == 0
+        e.accept_x_step()                                       # rejected trajectories received their nominal back
+        if self.batch == 1:
+            if ok[0]:
+                self.cost_log.append(self.cost)
+            elif verbose:
+                print("Forward pass failed with a cost of", float(e.cost_new[0]))
+            return bool(ok[0]), self.K, self.k
+        self.cost_log.append(self.cost)
+        return ok, self.K, self.k
+
     def solve(self, get_AB=None, get_Cs=None, is_dynamics_linear=False, is_cost_quadratic=False, method='dp',
-              max_iter=100, max_line_search_iter=25, tol_fun=1e-5, tol_grad=1e-4, verbose=False):
-        """iLQR outer loop with the reference's stop rules (isls/isls.py:54-132), per trajectory when batched."""
+              max_iter=100, max_line_search_iter=25, tol_fun=1e-5, tol_grad=1e-4, verbose=False, regularization=None):
+        """iLQR outer loop with the reference's stop rules (isls/isls.py:54-132), per trajectory when batched.
+        regularization: an `isls.Regularization`.  A Quu that is not positive definite then raises that trajectory's mu and
+        repeats the gain pass instead of raising LinAlgError; a rejected line search raises mu and the trajectory goes on from its
+        unchanged nominal instead of stopping; an accepted step lowers mu.  A trajectory stops when its step was accepted and
+        small, or when its ladder ended (ISLS_ST_REG_MAX in `status`).  `reg_mu` holds the final mu."""
         if method not in ('dp', 'batch'):
             raise NotImplementedError("method must be 'dp' or 'batch' (the reference raises for 'sls' too, isls.py:121-122)")
+        if regularization is not None and method == 'batch':
+            raise capi.IslsError("solve(method='batch') does not serve a regularisation (its column passes have no such term); use method='dp'")
+        self._set_regularization(regularization)
         e = self.engine
         e.outer_active.fill_(1)
         prev = np.atleast_1d(np.array(self.cost, dtype=np.float64)).copy()
@@ -314,7 +363,10 @@ class iSLS(Base):
             # reference: |diff(cost_log[-2:])| < tol_fun (a rejected step leaves cost_log untouched, so the test
             # is on the last two ACCEPTED costs), then `not fp_success`
             small = np.abs(cur - prev) < tol_fun
-            stop = act & ((okv & small) | ~okv)
+            if e.reg is not None:                               # a rejected trajectory goes on with a raised mu
+                stop = act & ((okv & small) | ((e.status.cpu().numpy() & capi.ST_REG_MAX) != 0))
+            else:
+                stop = act & ((okv & small) | ~okv)
             prev = np.where(act & okv, cur, prev)
             act &= ~stop
             e.outer_active.copy_(torch.as_tensor(act.astype(np.int32), device=e.device))
@@ -343,14 +395,15 @@ class iSLS(Base):
             raise ValueError("a callable cost_function needs get_Cs (its gradient / Hessian along the nominal)")
 
     def solve_ilqr(self, get_AB=None, max_ilqr_iter=100, max_line_search_iter=25, dp=True, verbose=False, **kw):
-        """Notebook-era name (Car notebooks :254): iLQR with the quadratic cost set by set_cost_variables."""
+        """Notebook-era name (Car notebooks :254): iLQR with the quadratic cost set by set_cost_variables.  Further keywords
+        (`regularization=` among them) go to `solve`."""
         return self.solve(get_AB, method='dp' if dp else 'batch', max_iter=max_ilqr_iter, max_line_search_iter=max_line_search_iter,
                           verbose=verbose, **kw)
 
     # ---- iLQR-ADMM (DP form) --------------------------------------------------------------------------------
     def ilqr_admm(self, get_AB=None, get_Cs=None, project_x=False, project_u=False, max_iter=20,
                   max_line_search_iter=20, max_admm_iter=20, rho_x=None, rho_u=None, alpha=1, tol=1e-3,
-                  verbose=False, log=False, k_max=None, max_line_search=None, threshold=None):
+                  verbose=False, log=False, k_max=None, max_line_search=None, threshold=None, regularization=None):
         """Outer loop of isls/isls.py:420-499 with the Riccati (DP) inner solve.  Per outer iteration:
         linearise, expand, then max_admm_iter x [ff pass, line search over alphas[:max_line_search_iter] without
         acceptance test, z/lambda update] with lambda reset and z warm-started, nominal <- last x-step, and the
@@ -362,6 +415,12 @@ class iSLS(Base):
         tol = threshold if threshold is not None else tol
         e = self.engine
         px, pu, host_proj = self._setup_admm(project_x, project_u, rho_x, rho_u, alpha)
+        if regularization is not None and host_proj:
+            raise capi.IslsError("ilqr_admm through the host (a projection or a model / cost given as a Python callable) does not serve "
+                                 "a regularisation; use Box / ConvexSets projections and device models")
+        # regularization: the gain pass of every outer iteration runs with its retry loop ahead of the driver (Engine.run_outer);
+        # no schedule on the line search, which has no acceptance test here
+        self._set_regularization(regularization)
         J = int(max_admm_iter)
         logbuf = torch.zeros(J, self.batch, 2, dtype=e.dtype, device=e.device)
         e.outer_active.fill_(1)
@@ -379,7 +438,7 @@ class iSLS(Base):
             e.accept_x_step(tol_cost=1e-3, tol_osc=1e-3)
             self.cost_log.append(self.cost)
             st = e.status.cpu().numpy()
-            if (st & capi.ST_NOT_PD).any():
+            if e.reg is None and (st & capi.ST_NOT_PD).any():
                 raise np.linalg.LinAlgError("Quu not positive definite")
             if verbose:
                 print("Iteration number ", j, "iLQR cost: ", self.cost)
@@ -578,6 +637,9 @@ class iSLS(Base):
         about the nominal, i.e. the Riccati solution rolled through the linearised dynamics, plus the dense form's last
         control (column 0 of isls_columns_rollout; SURVEY 8a quirk i)."""
         e = self.engine
+        if e.reg is not None:
+            raise capi.IslsError("the batch-form iLQR (backward_pass_batch, iterate_once_batch, solve(method='batch')) does not serve a "
+                                 "regularisation; use method='dp'")
         if e.user_cost:
             # the column roll-out (isls_columns_rollout) takes Cuu alone: a user cost's x-u cross terms would be dropped
             raise capi.IslsError("the batch-form iLQR (backward_pass_batch, iterate_once_batch, solve(method='batch')) does not serve a "

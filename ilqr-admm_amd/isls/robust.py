@@ -263,7 +263,7 @@ class _LaggedAny:
 
 
 def isls_admm(self, dim, get_AB=None, get_Cs=None, project_x=False, project_u=False, max_admm_iter=20, k_max=20,
-              max_line_search=20, rho_x=None, rho_u=None, alpha=1, threshold=1e-3, verbose=False, log=False):
+              max_line_search=20, rho_x=None, rho_u=None, alpha=1, threshold=1e-3, verbose=False, log=False, regularization=None):
     """Returns (du [N m], phi_u [N m, dim]) of the last ADMM x-step (with a leading batch axis when batch > 1).
 
     project_x / project_u: `projections.ConvexSets` over the rows [nominal + d, phi] (the shift by the nominal of
@@ -272,6 +272,9 @@ def isls_admm(self, dim, get_AB=None, get_Cs=None, project_x=False, project_u=Fa
     the last outer iteration per problem, `self.admm_logs` their (prim, dual) residuals [J, B, 2]."""
     self._check_get_Cs(get_Cs)                                                  # a callable cost needs its get_Cs
     e = self.engine
+    if regularization is not None or e.reg is not None:
+        raise capi.IslsError("isls_admm does not serve a regularisation (its column passes have no such term); use solve / ilqr_admm"
+                             + ("" if regularization is not None else ", or clear the one in use: engine.set_regularization(None)"))
     if e.user_cost:
         # the column passes (isls_columns_*) take Cuu alone: a user cost's x-u cross terms would be dropped without a word
         raise capi.IslsError("isls_admm does not serve a user cost (costs.Custom): its column passes have no Cux term; use solve / "

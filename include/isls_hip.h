@@ -49,6 +49,7 @@ extern "C" {
 #define ISLS_ST_NOT_PD 1     /* Quu not positive definite (reference: LinAlgError from dposv, isls/isls.py:296) */
 #define ISLS_ST_NAN_COST 2   /* a line-search candidate produced a NaN cost (isls/isls.py:362) */
 #define ISLS_ST_LS_REJECT 4  /* no candidate improved the cost (fp_success False, isls/isls.py:365-372) */
+#define ISLS_ST_REG_MAX 8    /* isls_reg_update_*: the regularisation ladder ended (a raise would pass mu_max); the failure bit stays */
 
 /* Quu solve: iLQR path uses Cholesky (isls/isls.py:296), SLS.solve_dp an explicit inverse (isls/sls.py:149-151) */
 #define ISLS_SOLVE_CHOL 0
@@ -253,6 +254,53 @@ int isls_riccati_ff_f32(const isls_ff_args *a, void *stream);
  * solve_mode and active as `g`.  ff->seg is ignored (the sweep is sequential); outputs: everything `g` writes, and ff->k. */
 int isls_riccati_gain_ff_f64(const isls_gain_args *g, const isls_ff_args *ff, void *stream);
 int isls_riccati_gain_ff_f32(const isls_gain_args *g, const isls_ff_args *ff, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Regularised gain pass: exactly isls_riccati_gain_* (ff == NULL) or isls_riccati_gain_ff_* (ff != NULL: the first feed-forward
+ * pass inside, ISLS_ERR_UNSUPPORTED where that entry is) run on Cuu_t + mu_b I for t <= N-2 -- and on Cxx_t + mu_b I for
+ * t <= N-2 when on_x != 0; the terminal block Cxx_{N-1} is left alone.  mu_b >= 0 is per trajectory, so batch-shared Hessian
+ * tables (zero batch stride) stay usable: the term is added inside the kernel.  This is the proximal term mu/2 |du|^2 (+ mu/2
+ * |dx|^2) folded into the stage cost, so K, fac = chol(Quu), the records [A+BK | B | K | fac] and every pass that reads them keep
+ * their meaning.  An all-zero mu gives the bits of the plain entry points -- with one exception of sign: the term enters as
+ * C_ii + mu ahead of the sum, so a diagonal cost entry of -0.0 becomes +0.0, which shows (as +0.0 for -0.0) only where the
+ * accumulated A'VA / B'VB term of that entry is -0.0 as well.
+ * Forms: records + K (g->rec, Quu == fac == Qux == NULL) or the arrays (g->rec == NULL); both together, or g->lin_on, are
+ * ISLS_ERR_UNSUPPORTED.  The generic (n, m) pairs take the array form.  status / active / record scratch semantics: isls_gain_args.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct isls_reg_args {
+    const void *mu;        /* [B], device, the pass's dtype */
+    int32_t on_x;          /* != 0: Cxx_t + mu I as well */
+    int32_t _pad;
+} isls_reg_args;
+
+int isls_riccati_gain_reg_f64(const isls_gain_args *g, const isls_ff_args *ff /* nullable */, const isls_reg_args *r, void *stream);
+int isls_riccati_gain_reg_f32(const isls_gain_args *g, const isls_ff_args *ff /* nullable */, const isls_reg_args *r, void *stream);
+
+/* The schedule of mu (iLQG.m's: Tassa, Erez, Todorov 2012), one flat kernel over the trajectories with active[b] != 0 (nullable:
+ * all) that do not carry ISLS_ST_REG_MAX yet:
+ *   raise: delta = max(factor, delta * factor), mu' = max(mu_min, mu * delta); if mu' > mu_max: status |= ISLS_ST_REG_MAX and mu,
+ *          delta stay (the ladder ended: the failure bit stays too);
+ *   lower: delta = min(1 / factor, delta / factor), mu = mu * delta if that is >= mu_min, else 0.
+ * ISLS_REG_AFTER_GAIN: raise where status has ISLS_ST_NOT_PD, and where the raise succeeded clear that bit, set retry[b] = 1 and
+ *   count one in *count (the caller zeroes it, reads it back and runs the gain pass again while it is non-zero -- with the mask of
+ *   the first launch, or one that covers whole wavefronts: see the scratch semantics of isls_gain_args.rec); retry[b] = 0 elsewhere.
+ * ISLS_REG_AFTER_LS: raise where status has ISLS_ST_LS_REJECT (the bit stays: the caller reads the verdict from it), lower where
+ *   the step was accepted (neither ISLS_ST_LS_REJECT nor ISLS_ST_NOT_PD).  retry / count are not used.
+ * mu, delta: [B] in the entry point's dtype; start a solve with delta = 1. */
+#define ISLS_REG_AFTER_GAIN 0
+#define ISLS_REG_AFTER_LS 1
+typedef struct isls_reg_update_args {
+    int32_t B, mode;
+    int32_t *status;        /* [B] */
+    const int32_t *active;  /* nullable */
+    void *mu, *delta;       /* [B] */
+    int32_t *retry;         /* [B], ISLS_REG_AFTER_GAIN (nullable) */
+    int32_t *count;         /* [1], ISLS_REG_AFTER_GAIN (nullable) */
+    double factor, mu_min, mu_max;
+} isls_reg_update_args;
+
+int isls_reg_update_f64(const isls_reg_update_args *a, void *stream);
+int isls_reg_update_f32(const isls_reg_update_args *a, void *stream);
 
 /* Operators of the time-parallel feed-forward pass (see isls_ffseg): run after the gain pass whenever
  * A, B, K, Quu, fac or Qux changed.  Writes seg.G for t < (nseg-1)*seg_len and seg.Psi for 1 <= s <= nseg-2. */
