@@ -801,19 +801,24 @@ class Kernels:
         a = self.project_args(y_in, y_out, sets, **kw)
         return self._call("project_rows", _sfx(y_in), a, stream)
 
-    def sls_admm(self, Linv, r_side, rr, sets, x_u, alpha=1.0, tol=1e-3, max_iter=50, rho=1.0, inner_max_iter=200,
-                 threshold=1e-4, z=None, lmb=None, logs=None, iters=None, rel_tol=1e-2, stream=None):
+    def sls_admm(self, Linv, r_side, rr, sets, x_u, stream=None, **kw):
         """isls_sls_admm: Linv [R,R], r_side [P,R,D], rr [R], sets as in project_args (A [dim,D] or [P,dim,D] ...)."""
+        return self._call("sls_admm", _sfx(r_side), self.sls_admm_args(Linv, r_side, rr, sets, x_u, **kw), stream)
+
+    @staticmethod
+    def sls_admm_args(Linv, r_side, rr, sets, x_u, alpha=1.0, tol=1e-3, max_iter=50, rho=1.0, inner_max_iter=200,
+                      threshold=1e-4, z=None, lmb=None, logs=None, iters=None, rel_tol=1e-2):
+        """isls_sls_admm_args for the operands of sls_admm"""
         P, R, D = r_side.shape
         _dense(Linv, (R, R), "Linv"), _dense(rr, (R,), "rr"), _dense(x_u, (P, R, D), "x_u")
-        pa = self.project_args(x_u, x_u, sets, rho=rho, max_iter=inner_max_iter, threshold=threshold)
+        pa = Kernels.project_args(x_u, x_u, sets, rho=rho, max_iter=inner_max_iter, threshold=threshold)
         a = SlsAdmmArgs(P=P, R=R, D=D, max_iter=int(max_iter), alpha=float(alpha), tol=float(tol), rel_tol=float(rel_tol),
                         proj=pa)
         a.Linv, a.r_side, a.rr = _ptr(Linv), _ptr(_dense(r_side, (P, R, D), "r_side")), _ptr(rr)
         a.x_u, a.z, a.lmb = _ptr(x_u), _ptr(_dense(z, (P, R, D), "z")), _ptr(_dense(lmb, (P, R, D), "lmb"))
         a.logs, a.iters = _ptr(_dense(logs, (P, int(max_iter), 2), "logs")), _ptr(iters)
         a._keep = pa
-        return self._call("sls_admm", _sfx(r_side), a, stream)
+        return a
 
     def dense_closed_loop(self, model, model_par, K, k, x0, x_log, u_log, xhat=None, uhat=None, stream=None):
         """isls_dense_closed_loop: K [N m, N n], k [N m], x0 [M,n], nominal xhat [N,n] / uhat [N,m] of one problem."""

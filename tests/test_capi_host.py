@@ -93,6 +93,32 @@ def test_argument_validation_without_gpu():
                     np.zeros((3, 5, 1, 1)), np.zeros((3, 5, 1, 1)), np.zeros((3, 5, 2, 2)))   # Qux has the wrong shape
 
 
+def test_sls_admm_refusals_without_gpu():
+    """isls_sls_admm checks its argument block before it touches a device: an empty batch is ISLS_OK (and launches nothing); more
+    rows than the largest workgroup (1025), no iterations, a penalty that is not positive, a set without its A -- each
+    ISLS_ERR_ARG, in both precisions; an unknown set kind is ISLS_ERR_UNSUPPORTED."""
+    k = capi.Kernels(capi.load_hip_library(), prefix="isls_", with_stream=True)
+    for dtype in (np.float64, np.float32):
+        def call(R=8, sets=None, P=3, **kw):
+            z = lambda *shape: np.zeros(shape, dtype=dtype)                              # noqa: E731
+            sets = [dict(kind=capi.SET_BOX, dim=2, A=z(2, 2), b=z(2), par=z(4))] if sets is None else sets
+            return k.sls_admm(z(R, R), z(P, R, 2), z(R), sets, z(P, R, 2), **kw)
+        # the block the refusals start from is itself accepted: with no problem in it every check runs and nothing is launched,
+        # so each refusal below is the work of the one field it changes
+        assert call(P=0) == capi.OK and call(P=0, R=1024) == capi.OK
+        refused = pytest.raises(capi.IslsError, match=rf"-> {capi.ERR_ARG}\b")
+        with refused:
+            call(R=1025)
+        with refused:
+            call(max_iter=0)
+        with refused:
+            call(rho=0.0)
+        with refused:
+            call(sets=[dict(kind=capi.SET_BOX, dim=2, b=np.zeros(2, dtype=dtype), par=np.zeros(4, dtype=dtype))])
+        with pytest.raises(capi.IslsError, match=rf"-> {capi.ERR_UNSUPPORTED}\b"):
+            call(sets=[dict(kind=8, dim=2, A=np.zeros((2, 2), dtype=dtype), b=np.zeros(2, dtype=dtype), par=np.zeros(4, dtype=dtype))])
+
+
 def test_shard_range():
     from isls.shard import shard_range
     for B, W in ((4096, 8), (10, 3), (7, 8)):
