@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "isls_common.hpp"
+#include "gain_memo.hpp"
 
 namespace isls {
 
@@ -66,9 +67,20 @@ static int outer_iteration(const isls_outer_args &a, hipStream_t s)
                         a.ff.m == a.gain.m && a.ff.active == a.gain.active && a.ff._pad <= 1 && a.ro.B == a.gain.B &&
                         a.ro.N == a.gain.N && a.ro.n == a.gain.n && a.ro.m == a.gain.m && a.ro.K == a.gain.K &&
                         a.ro.active == a.gain.active;
+    // The shared table is kept across calls, valid by content (gain_memo.hpp): a device-side check of the recursion's inputs
+    // against the entry's snapshot, the gain launch (which returns at once on a match), the commit of a recomputed table, and
+    // on a match the first feed-forward pass and the K broadcast the gain launch would have done.  All stream-ordered; which of
+    // the launches do the work is decided on the device alone.  Every reader takes the entry's table.
+    GainMemoRef memo;
+    // (an empty batch launches nothing, the gain pass included: no check counted, no entry touched)
+    const bool memo_on = shared && a.gain.B > 0 && gain_memo_acquire<T>(a.gain, s, memo);
+    const void *const shared_rec = memo_on ? memo.table : (shared ? a.gain.rec : nullptr);
+    isls_ff_args ff_sh = a.ff;
+    if (memo_on) ff_sh.rec = memo.table;
     if (!a.skip_gain) {
         {
             ScopedTimer tm(tmg, 0, s);
+            if (memo_on && (rc = launch_gain_memo_check<T>(a.gain, memo, s)) != ISLS_OK) return rc;
             // The gain pass with the recursion inside holds 370-400 registers: one wavefront per SIMD.  While its wavefronts fit
             // the chip's SIMDs that costs nothing; beyond (B > 7168 at n = 6, m = 3 on 256 CUs) the surplus runs as a second round
             // and the launch doubles (123 -> 251 us from B = 4096 to 8192), where the pass without the recursion (<= 256 registers,
@@ -81,7 +93,13 @@ static int outer_iteration(const isls_outer_args &a, hipStream_t s)
             const int lanes = a.gain.n + a.gain.m;
             const int64_t waves = lanes > 0 && lanes <= kWave ? (a.gain.B + kWave / lanes - 1) / (kWave / lanes) : 0;
             const bool fuse_now = a.J > 0 && waves <= simds;
-            if ((rc = launch_gain<T>(a.gain, s, fuse_now ? &a.ff : nullptr, &ff_done, false, shared)) != ISLS_OK) return rc;
+            if ((rc = launch_gain<T>(a.gain, s, fuse_now ? &a.ff : nullptr, &ff_done, false, shared, memo_on ? memo.hdr : nullptr)) != ISLS_OK) return rc;
+            if (memo_on) {                                     // (one timed family with the gain launch they stand in for)
+                if ((rc = launch_gain_memo_commit<T>(a.gain, memo, s)) != ISLS_OK) return rc;
+                // the pass that rode on the gain launch, and the K array, where that launch stood down
+                if (ff_done && (rc = launch_ff<T>(ff_sh, s, true, memo.hdr + kMemoMatch)) != ISLS_OK) return rc;
+                if ((rc = launch_gain_memo_broadcast<T>(a.gain, memo, s)) != ISLS_OK) return rc;
+            }
         }
         if (ff_seg_enabled(a.ff.seg)) {                        // operators of the time-parallel feed-forward pass
             const isls_ff_args &f = a.ff;
@@ -99,11 +117,11 @@ static int outer_iteration(const isls_outer_args &a, hipStream_t s)
     for (int j = 0; j < a.J; ++j) {
         if (!(j == 0 && ff_done)) {
             ScopedTimer tm(tmg, 1, s);
-            if ((rc = launch_ff<T>(a.ff, s, shared)) != ISLS_OK) return rc;
+            if ((rc = launch_ff<T>(memo_on ? ff_sh : a.ff, s, shared)) != ISLS_OK) return rc;
         }
         {
             ScopedTimer tm(tmg, 2, s);
-            if ((rc = launch_rollout<T>(a.ro, s, fuse ? &a.admm : nullptr, &fused, j == a.J - 1 || a.log != nullptr, shared ? a.gain.rec : nullptr)) != ISLS_OK) return rc;
+            if ((rc = launch_rollout<T>(a.ro, s, fuse ? &a.admm : nullptr, &fused, j == a.J - 1 || a.log != nullptr, shared_rec)) != ISLS_OK) return rc;
         }
         if (!fused) {
             ScopedTimer tm(tmg, 3, s);
@@ -199,6 +217,10 @@ ISLS_API int64_t isls_ff_record_elems(int32_t B, int32_t N, int32_t n, int32_t m
 }
 
 ISLS_API int isls_version(void) { return ISLS_VERSION; }
+
+ISLS_API int isls_gain_memo_stats(int64_t *checks, int64_t *matches) { return gain_memo_stats(checks, matches); }
+
+ISLS_API void isls_gain_memo_clear(void) { gain_memo_clear(); }
 
 ISLS_API int32_t isls_dims_supported(int32_t n, int32_t m) { return dims_supported(n, m) ? 1 : 0; }
 

@@ -142,6 +142,38 @@ __device__ __forceinline__ void chol_solve(const T (&U)[M][M], const T (&rd)[M],
     }
 }
 
+// The v / k recursion of the first feed-forward pass exists twice: inside the structured gain pass (riccati.hip, FF, LIN = 1) and
+// as the stand-in pass on the kept table (riccati_ffrec.hip, FU), and the two must agree bit for bit.  Left to the compiler, a
+// sum `acc += a * b` is contracted differently from one kernel to the next (fp32: some pairs become an unfused packed multiply
+// and a packed add), so both kernels write every multiply-add of that recursion through these: always one fused operation.
+// (X = false: the plain expression, for the forms that have no twin.)
+template <bool X = true, typename T>
+__device__ __forceinline__ T ff_mad(T a, T b, T c)
+{
+    if constexpr (X) return fma(a, b, c);
+    else return c + a * b;
+}
+// chol_solve with every update as one fused multiply-add
+template <int M, bool X = true, typename T>
+__device__ __forceinline__ void chol_solve_mad(const T (&U)[M][M], const T (&rd)[M], const T (&b)[M], T (&x)[M])
+{
+    T y[M];
+#pragma unroll
+    for (int i = 0; i < M; ++i) {
+        T s = b[i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) s = X ? fma(-U[k][i], y[k], s) : s - U[k][i] * y[k];
+        y[i] = s * rd[i];
+    }
+#pragma unroll
+    for (int i = M - 1; i >= 0; --i) {
+        T s = y[i];
+#pragma unroll
+        for (int k = i + 1; k < M; ++k) s = X ? fma(-U[i][k], x[k], s) : s - U[i][k] * x[k];
+        x[i] = s * rd[i];
+    }
+}
+
 // 64-lane butterfly sum (every lane ends with the total).
 template <typename T>
 __device__ __forceinline__ T wave_sum(T v)
@@ -245,11 +277,14 @@ inline bool gain_inputs_shared(const isls_gain_args &g)
 // require_ff: launch nothing unless the feed-forward pass can ride along (*did_ff stays false)
 // shared (the outer driver, gain_inputs_shared): one set of records for the whole batch, in slot 0 of block 0 -- the gain pass
 // writes them there only, the feed-forward passes and the line search read them from there (K, k stay per trajectory)
+// memo_hdr (shared only): header words of the gain memo's entry -- every wavefront returns at once where `match` is set
 template <typename T>
 int launch_gain(const isls_gain_args &a, hipStream_t s, const isls_ff_args *ff = nullptr, bool *did_ff = nullptr, bool require_ff = false,
-                bool shared = false);
-template <typename T> int launch_ff(const isls_ff_args &a, hipStream_t s, bool shared = false);
-template <typename T> int launch_ff_record(const isls_ff_args &a, hipStream_t s, bool shared = false);
+                bool shared = false, int32_t *memo_hdr = nullptr);
+// gate (shared only, gain_memo.hpp): the pass stands in for the recursion inside the gain pass -- it runs only where *gate is set,
+// and evaluates v and k with that recursion's sums (riccati.hip FF), so k is what the gain launch would have written, bit for bit
+template <typename T> int launch_ff(const isls_ff_args &a, hipStream_t s, bool shared = false, const int32_t *gate = nullptr);
+template <typename T> int launch_ff_record(const isls_ff_args &a, hipStream_t s, bool shared = false, const int32_t *gate = nullptr);
 template <typename T> int launch_ff_prepare(const isls_ff_prepare_args &a, hipStream_t s);
 template <typename T> int launch_ff_stitch(const isls_ff_args &a, hipStream_t s);
 bool ff_seg_enabled(const isls_ffseg &sg);

@@ -17,6 +17,7 @@
 // while step t is computed; the compiler's counted s_waitcnt vmcnt lets the oldest entry land while the
 // younger ones are still travelling).
 #include "isls_common.hpp"
+#include "gain_memo.hpp"
 
 namespace isls {
 
@@ -43,6 +44,7 @@ struct GainP {
     int64_t lin_par_sb;
     const T *reg_mu;               // REG form (isls_reg_args): mu[B], added to the diagonal of Cuu_t (reg_on_x: and of Cxx_t), t <= N-2
     int reg_on_x;
+    int32_t *memo;                 // SH form, nullable: header words of the gain memo's entry (gain_memo.hpp)
 };
 
 // 1/sqrt(a) by v_rsq + two coupled Newton steps (g -> sqrt(a), h -> 1/(2 sqrt(a))): 9 instructions against the ~30 of
@@ -256,12 +258,14 @@ __device__ __forceinline__ void riccati_gain_body(const GainP<T> &p, T *lds, T *
     const int ff_qdst = !xl ? QU_OFF + a_row : DUMP_OFF + 1;                  // qu_r
     const int ff_ku = xl ? i % NU : a_row;                                    // the entry of k_t this lane stores (x-lanes: a copy)
     const int ff_doff = D_OFF + (xl ? 0 : NX);
+    // the structured form's recursion has a twin (riccati_ffrec.hip, FU): its multiply-adds are written fused (ff_mad)
+    constexpr bool FX = LIN == 1;
     // c_i = c0_i + 2 * (row of Qr / Rr) . d      (isls/sls.py:132-137; riccati_ffrec.hip reg_grad: c0 + 2 * sum, the factor
     // folded into the row -- a power of two, so every product and the sum round exactly as there)
     auto ff_grad = [&](T c0v) -> T {
         T sacc = T(0);
 #pragma unroll
-        for (int j = 0; j < NX; ++j) sacc += ff_row[j] * rec[ff_doff + j];   // j >= lim: zero row entry times a neighbour word
+        for (int j = 0; j < NX; ++j) sacc = ff_mad<FX>(ff_row[j], rec[ff_doff + j], sacc);   // j >= lim: zero row entry times a neighbour word
         return c0v + sacc;
     };
 
@@ -499,11 +503,11 @@ __device__ __forceinline__ void riccati_gain_body(const GainP<T> &p, T *lds, T *
         if constexpr (FF) {
             T sacc = T(0);
 #pragma unroll
-            for (int j = 0; j < NX; ++j) sacc += ff_row[j] * ff_dr[j];   // j >= lim: zero row entry times a neighbour word
+            for (int j = 0; j < NX; ++j) sacc = ff_mad<FX>(ff_row[j], ff_dr[j], sacc);   // j >= lim: zero row entry times a neighbour word
             ff_ci = ff_c0v + sacc;
             T acc = T(0);
 #pragma unroll
-            for (int k = 0; k < NX; ++k) acc += colv[k] * ff_v[k];
+            for (int k = 0; k < NX; ++k) acc = ff_mad<FX>(colv[k], ff_v[k], acc);
             rec[ff_cdst] = ff_ci;
             rec[ff_qdst] = ff_ci + acc;
         }
@@ -598,7 +602,7 @@ __device__ __forceinline__ void riccati_gain_body(const GainP<T> &p, T *lds, T *
             constexpr int k = decltype(KK)::value;
             T ph = colv[k];
             if constexpr (LIN == 1) {
-                ph += (k < NU ? l_b0 : l_b1) * Kc[k % NU];        // row k of B has one entry
+                ph = ff_mad<true>(k < NU ? l_b0 : l_b1, Kc[k % NU], ph);   // row k of B has one entry
             } else {
 #pragma unroll
                 for (int r = 0; r < NU; ++r) ph += Fr[k][NX + r] * Kc[r];
@@ -625,7 +629,7 @@ __device__ __forceinline__ void riccati_gain_body(const GainP<T> &p, T *lds, T *
             for (int r = 0; r < NU; ++r) { cuv[r] = rec[CU_OFF + r]; qu[r] = rec[QU_OFF + r]; }
             if constexpr (MODE == ISLS_SOLVE_CHOL) {
                 T x[NU];
-                chol_solve<NU>(U, rd, qu, x);
+                chol_solve_mad<NU, FX>(U, rd, qu, x);
 #pragma unroll
                 for (int r = 0; r < NU; ++r) kt[r] = -x[r];
             } else {
@@ -633,7 +637,7 @@ __device__ __forceinline__ void riccati_gain_body(const GainP<T> &p, T *lds, T *
                 for (int r = 0; r < NU; ++r) {
                     T a2 = T(0);
 #pragma unroll
-                    for (int c = 0; c < NU; ++c) a2 += inv[r][c] * qu[c];
+                    for (int c = 0; c < NU; ++c) a2 = ff_mad<FX>(inv[r][c], qu[c], a2);
                     kt[r] = -a2;
                 }
             }
@@ -644,9 +648,9 @@ __device__ __forceinline__ void riccati_gain_body(const GainP<T> &p, T *lds, T *
             // v_i = (cx_i + (Phi'v)_i) + (K'cu)_i
             T acc = T(0), kcu = T(0);
 #pragma unroll
-            for (int k = 0; k < NX; ++k) acc += phc[k] * ff_v[k];
+            for (int k = 0; k < NX; ++k) acc = ff_mad<FX>(phc[k], ff_v[k], acc);
 #pragma unroll
-            for (int r = 0; r < NU; ++r) kcu += Kc[r] * cuv[r];
+            for (int r = 0; r < NU; ++r) kcu = ff_mad<FX>(Kc[r], cuv[r], kcu);
             rec[ff_vdst] = (ff_ci + acc) + kcu;                // read again only after the next (a)
         }
         // the lane's W words of the record image (unconditional: surplus lanes own the image's spare slot)
@@ -758,6 +762,9 @@ __device__ __forceinline__ void riccati_gain_body(const GainP<T> &p, T *lds, T *
         for (int j = 0; j < JPS + JK; ++j) send(tlast, j);
     }
     if (valid && i == 0 && !pd_ok && p.status) atomicOr(&p.status[b], ISLS_ST_NOT_PD);
+    if constexpr (SH && RS) {                                  // the run the memo would keep: did its pivots stay positive?
+        if (lane == 0 && p.memo) p.memo[kMemoNotPd] = pd_ok ? 0 : 1;
+    }
 }
 
 template <typename T, int NX, int NU, int D, int MODE, bool FF, bool REC, bool ARR, int LIN = 0, bool RL = (LIN == 1), bool SH = false, bool REG = false>
@@ -766,6 +773,9 @@ __global__ __launch_bounds__(64, ISLS_GAIN_OCC) void riccati_gain_kernel(GainP<T
     __shared__ T lds[gain_lds_words<NX, NU>(FF)];
     __shared__ __align__(16) T img[2 * (kWave / (NX + NU) + 1) * rec_stride(NX, NU)];
     if constexpr (SH) {
+        // gain memo: the check kernel found the inputs of the recursion equal to those the kept table was computed from --
+        // nothing to do for any wavefront (one scalar test ahead of everything; the step loop knows nothing of it)
+        if (p.memo != nullptr && p.memo[kMemoMatch] != 0) return;
         if (blockIdx.x == 0) riccati_gain_body<T, NX, NU, D, MODE, FF, REC, ARR, LIN, RL, true, true>(p, lds, img);
         else riccati_gain_body<T, NX, NU, D, MODE, FF, REC, ARR, LIN, RL, true, false>(p, lds, img);
     } else {
@@ -796,6 +806,7 @@ inline void gain_args_fill(const isls_gain_args &a, GainP<T> &p)
     p.xhat = p.uhat = p.zx = p.lx = p.zu = p.lu = nullptr; p.kff = nullptr;
     p.lin_par = nullptr; p.lin_par_sb = 0;
     p.reg_mu = nullptr; p.reg_on_x = 0;
+    p.memo = nullptr;
 }
 // the first feed-forward pass rides along when it would run on this pass's records with time-invariant Qr / Rr rows
 inline bool gain_ff_rides(const isls_gain_args &a, const isls_ff_args *ff)
@@ -816,7 +827,7 @@ inline void gain_ff_fill(const isls_ff_args *ff, GainP<T> &p)
 
 #ifndef ISLS_GAIN_REG_TU
 template <typename T>
-int launch_gain(const isls_gain_args &a, hipStream_t s, const isls_ff_args *ff, bool *did_ff, bool require_ff, bool shared)
+int launch_gain(const isls_gain_args &a, hipStream_t s, const isls_ff_args *ff, bool *did_ff, bool require_ff, bool shared, int32_t *memo_hdr)
 {
     if (did_ff) *did_ff = false;
     if (const int rc = gain_args_check(a); rc != ISLS_OK) return rc;
@@ -839,6 +850,8 @@ int launch_gain(const isls_gain_args &a, hipStream_t s, const isls_ff_args *ff, 
     p.lin_par = (const T *)a.lin_par; p.lin_par_sb = a.lin_par_sb;
     // shared records (gain_inputs_shared): the structured double-integrator form has them; the caller's readers rely on it
     if (shared && (!lin_di || !gain_inputs_shared(a) || !dims_supported(a.n, a.m))) return ISLS_ERR_ARG;
+    if (memo_hdr && !shared) return ISLS_ERR_ARG;
+    p.memo = memo_hdr;
     const bool with_ff = gain_ff_rides(a, ff);
     if (require_ff && !with_ff) return ISLS_OK;
     if (with_ff) gain_ff_fill(ff, p);
@@ -884,8 +897,8 @@ int launch_gain(const isls_gain_args &a, hipStream_t s, const isls_ff_args *ff, 
     if (did_ff) *did_ff = with_ff;
     return check_launch();
 }
-template int launch_gain<double>(const isls_gain_args &, hipStream_t, const isls_ff_args *, bool *, bool, bool);
-template int launch_gain<float>(const isls_gain_args &, hipStream_t, const isls_ff_args *, bool *, bool, bool);
+template int launch_gain<double>(const isls_gain_args &, hipStream_t, const isls_ff_args *, bool *, bool, bool, int32_t *);
+template int launch_gain<float>(const isls_gain_args &, hipStream_t, const isls_ff_args *, bool *, bool, bool, int32_t *);
 #endif  // ISLS_GAIN_REG_TU
 
 

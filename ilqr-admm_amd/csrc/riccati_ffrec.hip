@@ -45,6 +45,7 @@ struct FfRecP {
     // model-structured form (isls_ff_args.lin_on): only [K | fac] of a record is read; A'v and B'v come from the model
     const T *lin_par;              // model parameters (isls_linearize_args.model_par), batch stride lin_par_sb
     int64_t lin_par_sb;
+    const int32_t *gate;           // FU form: the word that lets the launch run (the gain memo's `match`)
 };
 
 // First form of the pass: Qr / Rr rows that vary with the time step (time-invariant ones take riccati_ffrec2_kernel below).
@@ -265,12 +266,22 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec_kernel(FfRecP<T> p)
 // SH (launch_ff's `shared`, LIN_DI): the batch has ONE set of records, in slot 0 of block 0 (riccati.hip); every slot of every
 // wavefront stages that record.  The table is N lean records (22 KB at N = 100, n = 6, m = 3) that every wavefront of the launch
 // reads again: plain loads, so that it stays in the caches, where the per-trajectory records stream through with `nt`.
+// FU (SH only; launch_ff_record's `gate`): the pass stands in for the v / k recursion INSIDE the gain pass (riccati.hip, FF) on a
+// call whose gain launch returned at once because the gain memo's table is still valid (gain_memo.hpp).  Every wavefront returns
+// at the top unless *gate is set, and v, qu and k are evaluated with that recursion's sums, term by term in its order:
+//     qu_r = cu_r + sum_k [A B][k, n + r] v_k,     v_i = (cx_i + sum_k Phi[k, i] v_k) + sum_r K[r, i] cu_r,     Phi[:, i] = A[:, i] + b K[., i]
+// (the lane's column of [A B] with its exact zeros, as there) instead of A'v + K'(B'v) -- so k is what the gain launch itself
+// would have written, bit for bit, and an outer iteration computes the same whether its table was kept or recomputed.
 constexpr int LIN_NONE = 0, LIN_DI = 1, LIN_ARM3R = 2, LIN_CAR = 3;
 
-template <typename T, int NX, int NU, int D, int OCC, int MODE, int LIN = LIN_NONE, bool SH = false>
+template <typename T, int NX, int NU, int D, int OCC, int MODE, int LIN = LIN_NONE, bool SH = false, bool FU = false>
 __global__ __launch_bounds__(64, OCC) void riccati_ffrec2_kernel(FfRecP<T> p)
 {
     static_assert(!SH || LIN == LIN_DI, "shared records: the structured double-integrator form");
+    static_assert(!FU || SH, "the stand-in for the gain pass's own recursion reads the batch's one table");
+    if constexpr (FU) {
+        if (p.gate[0] == 0) return;                            // uniform, ahead of everything
+    }
     static_assert(LIN != LIN_DI || NX == 2 * NU, "double integrator: n = 2 d, m = d");
     static_assert(LIN != LIN_ARM3R || (NX == 9 && NU == 3), "planar 3R arm: n = 9, m = 3");
     static_assert(LIN != LIN_CAR || (NX == 4 && NU == 2), "car: n = 4, m = 2");
@@ -362,6 +373,19 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec2_kernel(FfRecP<T> p)
     const T sown = LIN == LIN_ARM3R ? ((xl && i < 6) ? T(1) : T(0)) : T(1);
     const T cv = LIN == LIN_DI ? ((xl && i >= NU) ? la : T(0)) : ((xl && i >= 3 && i < 6) ? ldt : T(0));
     const T cj = LIN == LIN_ARM3R ? ((xl && i < 3) ? T(1) : ((xl && i < 6) ? ldt : T(0))) : T(0);
+    // FU form: the lane's column of [A B], zeros included (riccati.hip's colc)
+    T colc[NX];
+#pragma unroll
+    for (int k = 0; k < NX; ++k) colc[k] = T(0);
+    if constexpr (FU) {
+        T c1, c2;
+        int r1, r2;
+        if (xl && i < NU) { c1 = T(1); r1 = i; c2 = T(0); r2 = i; }
+        else if (xl) { c1 = la; r1 = i - NU; c2 = T(1); r2 = i; }
+        else { c1 = lb0; r1 = iu; c2 = lb1; r2 = NU + iu; }
+#pragma unroll
+        for (int k = 0; k < NX; ++k) colc[k] = (k == r1) ? c1 : ((k == r2) ? c2 : T(0));
+    }
 
     struct Stage {
         V2 rr[JR];
@@ -399,7 +423,7 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec2_kernel(FfRecP<T> p)
         T sacc = T(0);
         const T *qT = (p.Qr_term && xl) ? p.Qr_term + (int64_t)bb * p.Qr.sb + i * NX : nullptr;   // the terminal step's own weight row
 #pragma unroll
-        for (int j = 0; j < NX; ++j) sacc += (qT ? T(2) * qT[j] : qrow[j]) * rrec[D_OFF + j];
+        for (int j = 0; j < NX; ++j) sacc = ff_mad<FU>(qT ? T(2) * qT[j] : qrow[j], rrec[D_OFF + j], sacc);
         const T cterm = c0m * term.c0 + sacc;                  // u-lanes: unused
         vcur = (last && xl) ? cterm : T(0);
         rec[o_dst] = xl ? vcur : T(0);                         // v, and qu = 0: the first k the loop emits is k[N-1] = 0 (last segment)
@@ -463,13 +487,13 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec2_kernel(FfRecP<T> p)
             for (int r = 0; r < NU; ++r) {
                 T sacc = T(0);
 #pragma unroll
-                for (int c = 0; c < NU; ++c) sacc += rr2[r][c] * du[c];
+                for (int c = 0; c < NU; ++c) sacc = ff_mad<FU>(rr2[r][c], du[c], sacc);
                 cu[r] = c0u[r] + sacc;
             }
             T sx = T(0);                                       // without a state block qrow = 0 and the sum is +0 exactly:
             if (hasx) {                                        // skip it (uniform)
 #pragma unroll
-                for (int j = 0; j < NX; ++j) sx += qrow[j] * dx[j];
+                for (int j = 0; j < NX; ++j) sx = ff_mad<FU>(qrow[j], dx[j], sx);
             }
             T ci = c0_own + sx;                                // x-lanes: cx_i
 #pragma unroll
@@ -484,6 +508,22 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec2_kernel(FfRecP<T> p)
 #pragma unroll
                 for (int r = 0; r < NU; ++r) kcu += kcol[r] * cu[r];
                 vnew = qi + kcu;
+            } else if constexpr (FU) {
+                T acc = T(0), acc2 = T(0), kcu = T(0), phc[NX];
+#pragma unroll
+                for (int k = 0; k < NX; ++k) acc = ff_mad(colc[k], vv[k], acc);
+#pragma unroll
+                for (int k = 0; k < NX; ++k) {
+                    T ph = colc[k];
+                    ph = ff_mad(k < NU ? lb0 : lb1, kcol[k % NU], ph);   // row k of B has one entry
+                    phc[k] = ph;
+                }
+#pragma unroll
+                for (int k = 0; k < NX; ++k) acc2 = ff_mad(phc[k], vv[k], acc2);
+#pragma unroll
+                for (int r = 0; r < NU; ++r) kcu = ff_mad(kcol[r], cu[r], kcu);
+                qi = ci + acc;                                 // u-lanes: qu_r
+                vnew = (ci + acc2) + kcu;                      // x-lanes: v_i
             } else {
                 T w[NU], jvo = T(0);                           // w = B'v; jvo = (J'v_ee)_o of the lane's own o
                 if constexpr (LIN == LIN_DI) {
@@ -522,21 +562,22 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec2_kernel(FfRecP<T> p)
                 T rd[NU], x[NU];
 #pragma unroll
                 for (int r = 0; r < NU; ++r) rd[r] = fac_h[r][r];
-                chol_solve<NU>(fac_h, rd, qup, x);
+                chol_solve_mad<NU, FU>(fac_h, rd, qup, x);
 #pragma unroll
-                for (int r = 0; r < NU; ++r) kt[r] = T(0) - x[r];     // -x, and +0 for the k[N-1] = 0 the first iteration emits
+                for (int r = 0; r < NU; ++r) kt[r] = FU ? -x[r] : T(0) - x[r];     // -x, and +0 for the k[N-1] = 0 the first iteration emits
             } else {
 #pragma unroll
                 for (int r = 0; r < NU; ++r) {
                     T a2 = T(0);
 #pragma unroll
-                    for (int c = 0; c < NU; ++c) a2 += fac_h[r][c] * qup[c];
-                    kt[r] = T(0) - a2;
+                    for (int c = 0; c < NU; ++c) a2 = ff_mad<FU>(fac_h[r][c], qup[c], a2);
+                    kt[r] = FU ? -a2 : T(0) - a2;
                 }
             }
             T kv = kt[0];
 #pragma unroll
             for (int r = 1; r < NU; ++r) kv = (ku == r) ? kt[r] : kv;
+            if constexpr (FU) kv = (tprev == N - 1) ? T(0) : kv;   // no step pending yet: k[N-1] = +0, as the gain pass writes it
             kbase[(int64_t)tprev * NU] = kv;
             // publish v_i / qu_r (dead steps publish what is there already: vcur, and the pending qu again)
             T outv = xl ? vcur : qi;
@@ -563,7 +604,7 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec2_kernel(FfRecP<T> p)
             T rd[NU], x[NU];
 #pragma unroll
             for (int r = 0; r < NU; ++r) rd[r] = fac_h[r][r];
-            chol_solve<NU>(fac_h, rd, qup, x);
+            chol_solve_mad<NU, FU>(fac_h, rd, qup, x);
 #pragma unroll
             for (int r = 0; r < NU; ++r) kt[r] = -x[r];
         } else {
@@ -571,13 +612,14 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec2_kernel(FfRecP<T> p)
             for (int r = 0; r < NU; ++r) {
                 T a2 = T(0);
 #pragma unroll
-                for (int c = 0; c < NU; ++c) a2 += fac_h[r][c] * qup[c];
+                for (int c = 0; c < NU; ++c) a2 = ff_mad<FU>(fac_h[r][c], qup[c], a2);
                 kt[r] = -a2;
             }
         }
         T kv = kt[0];
 #pragma unroll
         for (int r = 1; r < NU; ++r) kv = (ku == r) ? kt[r] : kv;
+        if constexpr (FU) kv = (tprev == N - 1) ? T(0) : kv;   // N = 1
         kbase[(int64_t)tprev * NU] = kv;
     }
     if (seg > 0 && valid && xl) p.vseg[(((int64_t)col * p.B + b) * p.nseg + seg) * NX + i] = vcur;   // v0 at the segment start
@@ -592,7 +634,8 @@ static void launch_ffrec2(int lin, bool shared, dim3 grid, hipStream_t s, const 
 {
     if constexpr (NX == 2 * NU) {
         if (lin == LIN_DI) {
-            if (shared) hipLaunchKernelGGL((riccati_ffrec2_kernel<T, NX, NU, DL, OCC, MODE, LIN_DI, true>), grid, dim3(64), 0, s, p);
+            if (shared && p.gate) hipLaunchKernelGGL((riccati_ffrec2_kernel<T, NX, NU, DL, OCC, MODE, LIN_DI, true, true>), grid, dim3(64), 0, s, p);
+            else if (shared) hipLaunchKernelGGL((riccati_ffrec2_kernel<T, NX, NU, DL, OCC, MODE, LIN_DI, true>), grid, dim3(64), 0, s, p);
             else hipLaunchKernelGGL((riccati_ffrec2_kernel<T, NX, NU, DL, OCC, MODE, LIN_DI>), grid, dim3(64), 0, s, p);
             return;
         }
@@ -613,7 +656,7 @@ static void launch_ffrec2(int lin, bool shared, dim3 grid, hipStream_t s, const 
 }
 
 template <typename T>
-int launch_ff_record(const isls_ff_args &a, hipStream_t s, bool shared)
+int launch_ff_record(const isls_ff_args &a, hipStream_t s, bool shared, const int32_t *gate)
 {
     if ((int64_t)a.N * rec_stride(a.n, a.m) * 64 >= ((int64_t)1 << 31)) return ISLS_ERR_UNSUPPORTED;
     FfRecP<T> p;
@@ -650,6 +693,9 @@ int launch_ff_record(const isls_ff_args &a, hipStream_t s, bool shared)
         if (!rowc || segmented) return ISLS_ERR_UNSUPPORTED;
     }
     if (shared && (lin != LIN_DI || a.lin_par_sb != 0)) return ISLS_ERR_ARG;   // one set of records: the form that writes them
+    // the stand-in for the recursion inside the gain pass: what gain_ff_rides (riccati.hip) lets that pass take on
+    if (gate && (!shared || a.Qr_term || p.ncol > 1)) return ISLS_ERR_ARG;
+    p.gate = gate;
     p.lin_par = (const T *)a.lin_par; p.lin_par_sb = a.lin_par_sb;
     // the one-hand-off kernel addresses a step of c0x / c0u with a 32-bit offset
     const int64_t c0lim = ((int64_t)1 << 31) / (a.N > 1 ? a.N - 1 : 1);
@@ -676,7 +722,7 @@ int launch_ff_record(const isls_ff_args &a, hipStream_t s, bool shared)
 #undef LAUNCH2
     return check_launch();
 }
-template int launch_ff_record<double>(const isls_ff_args &, hipStream_t, bool);
-template int launch_ff_record<float>(const isls_ff_args &, hipStream_t, bool);
+template int launch_ff_record<double>(const isls_ff_args &, hipStream_t, bool, const int32_t *);
+template int launch_ff_record<float>(const isls_ff_args &, hipStream_t, bool, const int32_t *);
 
 }  // namespace isls

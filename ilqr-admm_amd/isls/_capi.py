@@ -232,6 +232,7 @@ EXPORTED = [f"isls_{k}_{s}" for s in ("f64", "f32") for k in
              "user_model_step", "user_cost_value", "user_cost_expand", "riccati_gain_reg", "reg_update")] + \
            ["isls_ff_segments", "isls_ff_record_elems", "isls_sls_controller_work_elems", "isls_mc_work_elems", "isls_version", "isls_dims_supported", "isls_dims_generic", "isls_error_string", "isls_timing_create",
             "isls_timing_destroy", "isls_timing_reset", "isls_timing_pause", "isls_timing_read_ms",
+            "isls_gain_memo_stats", "isls_gain_memo_clear",
             "isls_user_model_create", "isls_user_model_log", "isls_user_model_code", "isls_user_model_load",
             "isls_user_cost_create", "isls_user_cost_log", "isls_user_cost_code", "isls_user_cost_load"]
 
@@ -286,6 +287,24 @@ def load_hip_library(path=None):
     lib.isls_user_cost_code.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int64)]
     lib.isls_user_cost_load.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     return lib
+
+
+def gain_memo_stats(lib=None):
+    """(checks, matches) of the outer driver's gain memo so far (include/isls_hip.h); synchronises: tests and tools only."""
+    lib = lib or library()
+    c, m = C.c_int64(0), C.c_int64(0)
+    lib.isls_gain_memo_stats.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    rc = lib.isls_gain_memo_stats(C.byref(c), C.byref(m))
+    if rc != OK:
+        raise IslsError(f"isls_gain_memo_stats -> {rc}")
+    return c.value, m.value
+
+
+def gain_memo_clear(lib=None):
+    """Free the gain memo's entries (synchronises)."""
+    lib = lib or library()
+    lib.isls_gain_memo_clear.restype = None
+    lib.isls_gain_memo_clear()
 
 
 _LIB = None

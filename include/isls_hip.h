@@ -908,6 +908,25 @@ int isls_mc_closed_loop_f64(const isls_mc_loop_args *a, void *stream);
 int isls_mc_closed_loop_f32(const isls_mc_loop_args *a, void *stream);
 
 int isls_version(void);
+/* The gain memo of isls_ilqr_admm_outer_*.  Where a batch shares the inputs of the gain recursion (batch stride 0 on Cxx, Cuu,
+ * Cux and on the parameter row of the structured ISLS_MODEL_DI form, sequential feed-forward passes), the driver keeps the one
+ * table of records [K_t | fac_t] in device memory of the library's own, one entry per (device, stream, precision, n, m, N,
+ * solve mode), together with a snapshot of every word the recursion read.  Each call compares the inputs with the snapshot on
+ * the device, in stream order: equal bit patterns (and no NaN) -- the recursion is not run again, K and the first feed-forward
+ * pass are produced from the kept table with the same arithmetic; anything else -- the recursion runs and the entry is
+ * refreshed (never from a pass that met a pivot that is not positive).  Results are bit-identical either way; nothing is keyed
+ * on addresses and there is no switch.  A capturing stream or a failed allocation: the call runs without the memo.
+ * An empty batch (B = 0) launches nothing and touches no entry.
+ * Limits.  An entry (the snapshot and N records: ~75 KB at n = 6, m = 3, N = 100 in double) belongs to a stream HANDLE and
+ * lives until isls_gain_memo_clear: a program that keeps creating streams should call it when it destroys them (a recycled
+ * handle that finds an old entry is harmless -- validity is by content).  One host thread drives a (stream, shape) pair at a
+ * time, as for every stream-ordered call here: two threads enqueueing on the same stream and shape would share one `match`
+ * word.  K is written with 16-byte stores (fp32: 8-byte), like the gain pass's own: K must be aligned accordingly.
+ * isls_gain_memo_stats: device checks and matches so far, summed over the entries (synchronises: for tests and tools).
+ * isls_gain_memo_clear: frees every entry after synchronising its device; no other thread may be inside
+ * isls_ilqr_admm_outer_* meanwhile (a call in flight holds pointers into the entry). */
+int isls_gain_memo_stats(int64_t *checks, int64_t *matches);
+void isls_gain_memo_clear(void);
 /* 1 when the kernels are instantiated for state dimension n and control dimension m (the pairs are compile-time template
  * arguments: csrc/isls_common.hpp ISLS_FOR_EACH_DIMS), else 0: every entry point returns ISLS_ERR_UNSUPPORTED for other pairs. */
 int32_t isls_dims_supported(int32_t n, int32_t m);
