@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "isls_common.hpp"
+#include "covariance.hpp"
 #include "gain_memo.hpp"
 
 namespace isls {
@@ -166,6 +167,7 @@ ISLS_ENTRY(project_rows, isls_project_args, launch_project, false)
 ISLS_ENTRY(sls_admm, isls_sls_admm_args, launch_sls_admm, false)
 ISLS_ENTRY(dense_closed_loop, isls_dense_loop_args, launch_dense_closed_loop, false)
 ISLS_ENTRY(mc_closed_loop, isls_mc_loop_args, launch_mc_closed_loop, false)
+ISLS_ENTRY(cov_closed_loop, isls_cov_args, launch_cov_closed_loop, false)
 ISLS_ENTRY(sls_controller, isls_sls_controller_args, launch_sls_controller, false)
 ISLS_ENTRY(columns_rollout, isls_columns_args, launch_columns_rollout, false)
 ISLS_ENTRY(columns_admm, isls_columns_admm_args, launch_columns_admm, false)

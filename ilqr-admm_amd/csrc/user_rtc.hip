@@ -12,6 +12,7 @@
 #define _GNU_SOURCE                                          // dlmopen
 #endif
 #include <dlfcn.h>
+#include <unistd.h>
 #include <hip/hiprtc.h>
 
 #include <cstring>
@@ -42,6 +43,7 @@ struct Rtc {
     hiprtcResult (*code)(hiprtcProgram, char *);
     hiprtcResult (*lowered)(hiprtcProgram, const char *, const char **);
     hiprtcResult (*destroy)(hiprtcProgram *);
+    char ***env = nullptr;                                   // `environ` of the C library in hiprtc's link namespace (its own copy)
 };
 
 std::string dir_of(const void *addr)
@@ -87,6 +89,7 @@ const Rtc &rtc()
         sym(r.code, "hiprtcGetCode");
         sym(r.lowered, "hiprtcGetLoweredName");
         sym(r.destroy, "hiprtcDestroyProgram");
+        r.env = reinterpret_cast<char ***>(dlsym(h, "environ"));
         r.ok = all;
     });
     return r;
@@ -131,6 +134,10 @@ int compile_program(const std::string &src, const char *file, Program &pg, std::
         return ISLS_ERR_COMPILE;
     }
     const std::string csrc = dir_of(reinterpret_cast<const void *>(&rtc));   // the device headers lie next to the library
+    // A link namespace of its own has a C library of its own, and that one keeps the environment pointer of the moment it was
+    // loaded.  A setenv in the process since then reallocates the array: the compiler's getenv calls would walk a freed block
+    // (seen as a segmentation fault in the first compile after os.environ had grown).  Hand it the current array.
+    if (r.env && r.env != &environ) *r.env = environ;
     hiprtcProgram prog;
     if (r.create(&prog, src.c_str(), file, 0, nullptr, nullptr) != HIPRTC_SUCCESS) {
         log += "hiprtcCreateProgram failed\n";

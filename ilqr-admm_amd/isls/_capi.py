@@ -192,6 +192,19 @@ class McLoopArgs(C.Structure):
                 ("work", C.c_void_p), ("work_elems", C.c_int64)]
 
 
+class CovArgs(C.Structure):
+    """isls_cov_args: mean and covariance of the linearised closed loop of a batch of stage-local controllers (isls/covariance.py)"""
+    _fields_ = [("P", C.c_int32), ("N", C.c_int32), ("n", C.c_int32), ("m", C.c_int32),
+                ("A", View), ("Bm", View),
+                ("K", C.c_void_p), ("k", C.c_void_p), ("K_sb", C.c_int64), ("k_sb", C.c_int64),
+                ("xhat", C.c_void_p), ("uhat", C.c_void_p), ("xhat_sb", C.c_int64), ("uhat_sb", C.c_int64),
+                ("dx0", C.c_void_p), ("dx0_sb", C.c_int64), ("S0", C.c_void_p), ("S0_sb", C.c_int64),
+                ("W", View), ("u_lo", View), ("u_hi", View), ("x_lo", View), ("x_hi", View),
+                ("active", C.c_void_p),
+                ("x_mean", C.c_void_p), ("u_mean", C.c_void_p), ("x_var", C.c_void_p), ("u_var", C.c_void_p),
+                ("x_cov", C.c_void_p), ("u_cov", C.c_void_p), ("p_u", C.c_void_p), ("p_x", C.c_void_p)]
+
+
 class SlsControllerArgs(C.Structure):
     _fields_ = [("B", C.c_int32), ("N", C.c_int32), ("n", C.c_int32), ("m", C.c_int32), ("A", View), ("Bm", View),
                 ("PHI_U", C.c_void_p), ("du", C.c_void_p), ("K", C.c_void_p), ("k", C.c_void_p), ("flags", C.c_void_p),
@@ -227,7 +240,7 @@ class AdvanceArgs(C.Structure):
 
 # names every build of the library must export (checked by tests/test_capi_host.py)
 EXPORTED = [f"isls_{k}_{s}" for s in ("f64", "f32") for k in
-            ("riccati_gain", "riccati_ff", "riccati_gain_ff", "riccati_ff_prepare", "rollout_ls", "admm_update", "project_rows", "sls_admm", "sls_closed_loop", "columns_rollout", "columns_admm", "dense_closed_loop", "mc_closed_loop", "sls_controller", "expand_quadratic", "linearize",
+            ("riccati_gain", "riccati_ff", "riccati_gain_ff", "riccati_ff_prepare", "rollout_ls", "admm_update", "project_rows", "sls_admm", "sls_closed_loop", "columns_rollout", "columns_admm", "dense_closed_loop", "mc_closed_loop", "cov_closed_loop", "sls_controller", "expand_quadratic", "linearize",
              "accept_step", "reduce_convergence", "reduce_convergence_table", "ilqr_admm_outer", "outer_advance", "columns_iteration",
              "user_model_step", "user_cost_value", "user_cost_expand", "riccati_gain_reg", "reg_update")] + \
            ["isls_ff_segments", "isls_ff_record_elems", "isls_sls_controller_work_elems", "isls_mc_work_elems", "isls_version", "isls_dims_supported", "isls_dims_generic", "isls_error_string", "isls_timing_create",
@@ -931,6 +944,10 @@ class Kernels:
     def mc_closed_loop(self, a, sfx, stream=None):
         """isls_mc_closed_loop on a filled McLoopArgs (isls/montecarlo.py builds it)"""
         return self._call("mc_closed_loop", sfx, a, stream)
+
+    def cov_closed_loop(self, a, sfx, stream=None):
+        """isls_cov_closed_loop on a filled CovArgs (isls/covariance.py builds it)"""
+        return self._call("cov_closed_loop", sfx, a, stream)
 
     def sls_closed_loop(self, A, Bm, K, k, x0, x_log, u_log, stream=None):
         M, N, n = x_log.shape

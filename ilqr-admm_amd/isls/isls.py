@@ -613,6 +613,35 @@ class iSLS(Base):
                               x0s=x0s, noise_scale=noise_scale, w=w, seed=seed, u_bounds=u_bounds, x_bounds=x_bounds, xhat=xhat,
                               uhat=uhat, problems=self.batch, return_trajectories=return_trajectories, **chunks)
 
+    def covariance(self, K=None, k=None, x0=None, x0_std=None, x0_cov=None, noise_scale=0.0, noise_cov=None, u_bounds=None,
+                   x_bounds=None, full=False):
+        """Mean and covariance of every problem's closed loop, predicted without a sample (isls/covariance.py,
+        isls_cov_closed_loop_*): the analytic counterpart of monte_carlo.  The loop is the LINEARISED one about the current
+        nominal, Sig_{t+1} = (A_t + B_t K_t) Sig_t (A_t + B_t K_t)' + W_t, Su_t = K_t Sig_t K_t', with the engine's A, Bm: the
+        caller's (get_AB / AB) where they are, else the forward model (an isls.models descriptor; models.Custom through its
+        dual-number linearisation) is linearised first.  A forward model that is a Python callable is therefore served only with
+        the caller's get_AB / AB; no roll-out is needed.  The nominal is ASSUMED dynamically consistent (xhat_{t+1} = f(xhat_t,
+        uhat_t), as after solve / ilqr_admm): the mean is xhat + d with d_{t+1} = (A + B K) d_t + B k_t from d_0 = x0 - xhat_0.
+        K [N,m,n] / [B,N,m,n], k (stage-local gains; default: the engine's own; a dense causal K is a ValueError); x0 [n] / [B,n]
+        (default: xhat_0); x0_std / noise_scale: per-coordinate standard deviations as monte_carlo takes them, or x0_cov /
+        noise_cov: full matrices [n,n], [B,n,n] (the noise also [B,N,n,n]) -- both forms of one quantity: ValueError; the noise
+        acts behind step t as in monte_carlo.  u_bounds / x_bounds = (lo, hi) as in monte_carlo.  Returns a CovarianceResult:
+        x_mean, u_mean, x_var, u_var, p_x, p_u (+ x_cov, u_cov with full=True); its tightened(lo, hi, psi_inv) is the box of
+        ilqr_admm shrunk into a chance constraint."""
+        from . import covariance
+        e = self.engine
+        if not self._user_AB:
+            self._linearize(None)
+        as_torch = isinstance(K, torch.Tensor)                   # the engine's own gains are no torch operand of the caller's
+        K = e.K if K is None else K
+        k = e.k if k is None else k
+        dx0 = None
+        if x0 is not None:
+            dx0 = e._t(x0) - e.xhat[:, 0]
+        return covariance.run(e, e.A, e.Bm, K, k, self.N, self.x_dim, self.u_dim, problems=self.batch, xhat=e.xhat, uhat=e.uhat,
+                              dx0=dx0, x0_std=x0_std, x0_cov=x0_cov, noise_scale=noise_scale, noise_cov=noise_cov,
+                              u_bounds=u_bounds, x_bounds=x_bounds, full=full, as_torch=as_torch)
+
     # ---- batch-form iLQR (isls/isls.py:135-228) through the Riccati kernels ---------------------------------------------
     def rollout_batch(self, x_nom, u_nom):
         """Open-loop rollouts from x_nom[0] (isls/isls.py:135-154): u_nom [L,N,m] (or [B,L,N,m]) -> (x_log, u_nom)."""

@@ -431,6 +431,25 @@ class SLS(Base):
                               x0s=x0s, noise_scale=noise_scale, w=w, seed=seed, u_bounds=u_bounds, x_bounds=x_bounds,
                               return_trajectories=return_trajectories, **chunks)
 
+    def covariance(self, K=None, k=None, x0=None, x0_std=None, x0_cov=None, noise_scale=0.0, noise_cov=None, u_bounds=None,
+                   x_bounds=None, full=False):
+        """Mean and covariance of the closed loops x_{i+1} = A x_i + B (K_i x_i + k_i) + w_i of P stage-local controllers,
+        predicted without a sample (isls/covariance.py, isls_cov_closed_loop_*): the analytic counterpart of monte_carlo on the
+        class's shared A, B.  K [N,m,n] / [P,N,m,n], k to match (default: the gains of the last solve_dp); x0 [n] / [P,n] the mean
+        initial state (default 0); x0_std / noise_scale (standard deviations, as monte_carlo takes them) or x0_cov / noise_cov
+        (full [n,n], [P,n,n]; the noise also [P,N,n,n]) -- both forms of one quantity: ValueError.  A dense causal K is a
+        ValueError: for an SLS design the spread of u is phi_u S0 phi_u'.  Bounds and the CovarianceResult as in
+        iSLS.covariance."""
+        from . import covariance
+        e = self.engine
+        assert self.A is not None, "Set the linear dynamics model by self.AB = [A,B] before calling this method."
+        as_torch = isinstance(K, torch.Tensor)                   # the engine's own gains are no torch operand of the caller's
+        K = e.K if K is None else K
+        k = e.k if k is None else k
+        return covariance.run(e, e.A, e.Bm, K, k, self.N, self.x_dim, self.u_dim, dx0=x0, x0_std=x0_std, x0_cov=x0_cov,
+                              noise_scale=noise_scale, noise_cov=noise_cov, u_bounds=u_bounds, x_bounds=x_bounds, full=full,
+                              as_torch=as_torch)
+
     def get_trajectory_batch(self, x0, us, noise_scale=0):
         """Open loop: the control sequence us [N,m] applied from every initial state x0 [M,n] (isls/sls_base.py:61-74)."""
         K = np.zeros((self.N, self.u_dim, self.x_dim))

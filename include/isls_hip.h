@@ -907,6 +907,52 @@ int64_t isls_mc_work_elems(int32_t P, int32_t M, int32_t N, int32_t n, int32_t m
 int isls_mc_closed_loop_f64(const isls_mc_loop_args *a, void *stream);
 int isls_mc_closed_loop_f32(const isls_mc_loop_args *a, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Closed-loop covariance of a batch of stage-local controllers: the analytic counterpart of isls_mc_closed_loop_*.  The
+ * reference has no covariance code (it samples, or constrains phi_u S0 phi_u' in its SLS form); this is the first and second
+ * moment of the LINEARISED closed loop x_{t+1} = f(x_t, u_t) + w_t, u_t = uhat_t + k_t + K_t (x_t - xhat_t) about a nominal
+ * that is dynamically consistent (xhat_{t+1} = f(xhat_t, uhat_t)), with x_0 ~ (xhat_0 + dx0, S0) and w_t ~ (0, W_t):
+ *   Sig_0 = (S0 + S0')/2 ;  d_0 = dx0 ;  for t = 0 .. N-1, with Phi_t = A_t + B_t K_t:
+ *     xbar_t = xhat_t + d_t ;  ubar_t = uhat_t + (k_t + K_t d_t) ;  Su_t = sym(K_t Sig_t K_t')
+ *     d_{t+1} = Phi_t d_t + B_t k_t ;  Sig_{t+1} = sym(Phi_t Sig_t Phi_t' + W_t) ,  sym(S) = (S + S')/2 entry by entry
+ *   (W_t is added BEHIND step t, the convention of isls_mc_closed_loop_*; W_{N-1} acts on nothing).  Every covariance written is
+ *   exactly symmetric and x_var / u_var are the diagonals of x_cov / u_cov bit for bit.  Every multiply-add is one fused
+ *   operation and every sum runs over its inner index ascending (csrc/covariance.hip writes the order out).
+ * Inputs.  A [.,.,n,n], Bm [.,.,n,m]: views (sb = st = 0: a shared LTI pair).  K [.,N,m,n] (K_sb = 0: one controller for all);
+ * k [.,N,m] nullable (0);  xhat [.,N,n], uhat [.,N,m] nullable (0);  dx0 [.,n] nullable (0);  S0 [.,n,n];  W [.,.,n,n] view,
+ * nullable (no noise; sb = 0 / st = 0 shares it over problems / steps).  `_sb` are batch strides in elements, 0 = shared.
+ * Bounds u_lo, u_hi [.,.,m], x_lo, x_hi [.,.,n]: views as in isls_mc_loop_args, each nullable (that side is free).
+ * Outputs, each nullable: x_mean [P,N,n], u_mean [P,N,m], x_var [P,N,n], u_var [P,N,m], x_cov [P,N,n,n], u_cov [P,N,m,m] and
+ *   p_x [P,N,n], p_u [P,N,m]: the Gaussian probability of lying outside [lo, hi] at that step and coordinate,
+ *   p = erfc((mu - lo) / (sigma sqrt 2))/2 + erfc((hi - mu) / (sigma sqrt 2))/2 (an absent or infinite side contributes 0);
+ *   sigma == 0 exactly (a variance <= 0): p = 1 where mu < lo or mu > hi, else 0.
+ * Problems with active[b] == 0 are skipped: nothing of theirs is written.
+ * The (n, m) pairs of csrc/families.def only (isls_dims_supported), any other pair: ISLS_ERR_UNSUPPORTED.  ISLS_ERR_ARG: a NULL
+ * A, Bm, K or S0, N < 1, P < 0, a negative stride.  P == 0: ISLS_OK, nothing is launched.  No scratch memory, no work buffer.
+ * ------------------------------------------------------------------------------------------- */
+#ifndef __HIPCC_RTC__   /* a host-side entry point: the device code compiled at run time (user models and costs) reads none of it */
+typedef struct isls_cov_args {
+    int32_t P, N, n, m;
+    isls_view A, Bm;                /* [.,.,n,n], [.,.,n,m] */
+    const void *K, *k;              /* [.,N,m,n], [.,N,m] (k nullable) */
+    int64_t K_sb, k_sb;
+    const void *xhat, *uhat;        /* [.,N,n], [.,N,m] nullable */
+    int64_t xhat_sb, uhat_sb;
+    const void *dx0;                /* [.,n] nullable: mean initial deviation x0 - xhat_0 */
+    int64_t dx0_sb;
+    const void *S0;                 /* [.,n,n] initial covariance */
+    int64_t S0_sb;
+    isls_view W;                    /* [.,.,n,n] nullable: process-noise covariance */
+    isls_view u_lo, u_hi;           /* [.,.,m] */
+    isls_view x_lo, x_hi;           /* [.,.,n] */
+    const int32_t *active;          /* [P] nullable */
+    void *x_mean, *u_mean, *x_var, *u_var, *x_cov, *u_cov, *p_u, *p_x;
+} isls_cov_args;
+
+int isls_cov_closed_loop_f64(const isls_cov_args *a, void *stream);
+int isls_cov_closed_loop_f32(const isls_cov_args *a, void *stream);
+#endif
+
 int isls_version(void);
 /* The gain memo of isls_ilqr_admm_outer_*.  Where a batch shares the inputs of the gain recursion (batch stride 0 on Cxx, Cuu,
  * Cux and on the parameter row of the structured ISLS_MODEL_DI form, sequential feed-forward passes), the driver keeps the one
