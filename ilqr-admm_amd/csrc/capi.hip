@@ -68,10 +68,15 @@ static int outer_iteration(const isls_outer_args &a, hipStream_t s)
                         a.ff.m == a.gain.m && a.ff.active == a.gain.active && a.ff._pad <= 1 && a.ro.B == a.gain.B &&
                         a.ro.N == a.gain.N && a.ro.n == a.gain.n && a.ro.m == a.gain.m && a.ro.K == a.gain.K &&
                         a.ro.active == a.gain.active;
-    // The shared table is kept across calls, valid by content (gain_memo.hpp): a device-side check of the recursion's inputs
-    // against the entry's snapshot, the gain launch (which returns at once on a match), the commit of a recomputed table, and
-    // on a match the first feed-forward pass and the K broadcast the gain launch would have done.  All stream-ordered; which of
-    // the launches do the work is decided on the device alone.  Every reader takes the entry's table.
+    // The shared table is kept across calls, valid by content (gain_memo.hpp).  Three launches, stream-ordered:
+    //   check     compares the recursion's inputs with the entry's snapshot (and brings the snapshot up to them);
+    //   gain      stands down on a match; otherwise its block 0 writes the records into the entry's table and marks it filled;
+    //   stand-in  on a match only: the first feed-forward pass the gain launch would have run, which also writes the K array
+    //             from the table's records it stages (a call whose first pass does not ride on the gain launch has no stand-in:
+    //             a K broadcast launch takes its place).
+    // Which of them do the work is decided on the device alone.  Every reader takes the entry's table.  A hit used to be five
+    // launches (check, gain, commit, stand-in, K broadcast): the commit launch did nothing on a hit and cost 4.7 us, the
+    // broadcast 11.8 us behind the stand-in pass's 42.0 us (B = 4096, N = 100, fp64; DESIGN section 5 has the figures since).
     GainMemoRef memo;
     // (an empty batch launches nothing, the gain pass included: no check counted, no entry touched)
     const bool memo_on = shared && a.gain.B > 0 && gain_memo_acquire<T>(a.gain, s, memo);
@@ -94,12 +99,14 @@ static int outer_iteration(const isls_outer_args &a, hipStream_t s)
             const int lanes = a.gain.n + a.gain.m;
             const int64_t waves = lanes > 0 && lanes <= kWave ? (a.gain.B + kWave / lanes - 1) / (kWave / lanes) : 0;
             const bool fuse_now = a.J > 0 && waves <= simds;
-            if ((rc = launch_gain<T>(a.gain, s, fuse_now ? &a.ff : nullptr, &ff_done, false, shared, memo_on ? memo.hdr : nullptr)) != ISLS_OK) return rc;
-            if (memo_on) {                                     // (one timed family with the gain launch they stand in for)
-                if ((rc = launch_gain_memo_commit<T>(a.gain, memo, s)) != ISLS_OK) return rc;
+            if ((rc = launch_gain<T>(a.gain, s, fuse_now ? &a.ff : nullptr, &ff_done, false, shared, memo_on ? memo.hdr : nullptr,
+                                      memo_on ? memo.table : nullptr)) != ISLS_OK)
+                return rc;
+            if (memo_on) {                                     // (one timed family with the gain launch it stands in for)
                 // the pass that rode on the gain launch, and the K array, where that launch stood down
-                if (ff_done && (rc = launch_ff<T>(ff_sh, s, true, memo.hdr + kMemoMatch)) != ISLS_OK) return rc;
-                if ((rc = launch_gain_memo_broadcast<T>(a.gain, memo, s)) != ISLS_OK) return rc;
+                if (ff_done) rc = launch_ff<T>(ff_sh, s, true, memo.hdr + kMemoMatch, a.gain.K);
+                else rc = launch_gain_memo_broadcast<T>(a.gain, memo, s);
+                if (rc != ISLS_OK) return rc;
             }
         }
         if (ff_seg_enabled(a.ff.seg)) {                        // operators of the time-parallel feed-forward pass

@@ -1,4 +1,4 @@
-// gain_memo.hip -- the memo of the batch-shared Riccati gain table (gain_memo.hpp): its entries and its three small kernels.
+// gain_memo.hip -- the memo of the batch-shared Riccati gain table (gain_memo.hpp): its entries and its two small kernels.
 #include <mutex>
 #include <vector>
 
@@ -37,32 +37,28 @@ __device__ __forceinline__ void memo_for_each(const MemoIn<T> &in, int tid, int 
 __device__ __forceinline__ uint64_t memo_bits(double v) { return __builtin_bit_cast(uint64_t, v); }
 __device__ __forceinline__ uint32_t memo_bits(float v) { return __builtin_bit_cast(uint32_t, v); }
 
+// One workgroup.  Besides the verdict it leaves the snapshot equal to the inputs: a word that differs is replaced on the spot (the
+// value is in a register already), so a miss needs no second sweep over the inputs -- block 0 of the gain launch that follows
+// writes the table and sets `filled` (riccati.hip).  Between the two the entry is marked unfilled: a gain launch that never
+// ran (a failed launch) cannot leave a new snapshot next to an old table.
 template <typename T>
-__global__ __launch_bounds__(1024) void gain_memo_check_kernel(MemoIn<T> in, const T *snap, int32_t *hdr, int64_t *cnt)
+__global__ __launch_bounds__(1024) void gain_memo_check_kernel(MemoIn<T> in, T *snap, int32_t *hdr, int64_t *cnt)
 {
     int diff = 0;
     memo_for_each(in, (int)threadIdx.x, (int)blockDim.x, [&](const T *src, int w) {
         const T v = *src;
-        diff |= (memo_bits(v) != memo_bits(snap[w])) || (v != v);       // bit patterns; a NaN never matches
+        const bool other = memo_bits(v) != memo_bits(snap[w]);               // bit patterns
+        if (other) snap[w] = v;
+        diff |= other || (v != v);                                           // a NaN never matches
     });
     const int any = __syncthreads_or(diff);
     if (threadIdx.x == 0) {
         const int match = (hdr[kMemoFilled] != 0 && !any) ? 1 : 0;
         hdr[kMemoMatch] = match;
+        if (!match) hdr[kMemoFilled] = 0;
         cnt[0] += 1;
         cnt[1] += match;
     }
-}
-
-template <typename T>
-__global__ __launch_bounds__(1024) void gain_memo_commit_kernel(MemoIn<T> in, T *snap, const T *rec, T *table, int run_words, int32_t *hdr)
-{
-    if (hdr[kMemoMatch]) return;
-    memo_for_each(in, (int)threadIdx.x, (int)blockDim.x, [&](const T *src, int w) { snap[w] = *src; });
-    for (int w = threadIdx.x; w < run_words; w += blockDim.x) table[w] = rec[w];
-    __syncthreads();
-    // a recursion that met a pivot that is not positive is never kept: its table serves this call's readers only
-    if (threadIdx.x == 0) hdr[kMemoFilled] = hdr[kMemoNotPd] ? 0 : 1;
 }
 
 template <typename T>
@@ -150,23 +146,11 @@ static MemoIn<T> memo_inputs(const isls_gain_args &g)
 template <typename T>
 int launch_gain_memo_check(const isls_gain_args &g, const GainMemoRef &ref, hipStream_t s)
 {
-    hipLaunchKernelGGL((gain_memo_check_kernel<T>), dim3(1), dim3(1024), 0, s, memo_inputs<T>(g), (const T *)ref.snap, ref.hdr, ref.cnt);
+    hipLaunchKernelGGL((gain_memo_check_kernel<T>), dim3(1), dim3(1024), 0, s, memo_inputs<T>(g), (T *)ref.snap, ref.hdr, ref.cnt);
     return check_launch();
 }
 template int launch_gain_memo_check<double>(const isls_gain_args &, const GainMemoRef &, hipStream_t);
 template int launch_gain_memo_check<float>(const isls_gain_args &, const GainMemoRef &, hipStream_t);
-
-template <typename T>
-int launch_gain_memo_commit(const isls_gain_args &g, const GainMemoRef &ref, hipStream_t s)
-{
-    // steps 0 .. N-2 of block 0's run (the gain pass writes no record for the terminal step; the table's last step stays zero)
-    const int run_words = (g.N - 1) * memo_step_words(g.n, g.m);
-    hipLaunchKernelGGL((gain_memo_commit_kernel<T>), dim3(1), dim3(1024), 0, s, memo_inputs<T>(g), (T *)ref.snap, (const T *)g.rec, (T *)ref.table,
-                       run_words, ref.hdr);
-    return check_launch();
-}
-template int launch_gain_memo_commit<double>(const isls_gain_args &, const GainMemoRef &, hipStream_t);
-template int launch_gain_memo_commit<float>(const isls_gain_args &, const GainMemoRef &, hipStream_t);
 
 template <typename T>
 int launch_gain_memo_broadcast(const isls_gain_args &g, const GainMemoRef &ref, hipStream_t s)

@@ -277,14 +277,18 @@ inline bool gain_inputs_shared(const isls_gain_args &g)
 // require_ff: launch nothing unless the feed-forward pass can ride along (*did_ff stays false)
 // shared (the outer driver, gain_inputs_shared): one set of records for the whole batch, in slot 0 of block 0 -- the gain pass
 // writes them there only, the feed-forward passes and the line search read them from there (K, k stay per trajectory)
-// memo_hdr (shared only): header words of the gain memo's entry -- every wavefront returns at once where `match` is set
+// memo_hdr, memo_table (shared only, both or none): header words and table of the gain memo's entry -- every wavefront returns at
+// once where `match` is set; otherwise block 0 writes its records into the table instead of a.rec and sets `filled` at its end
 template <typename T>
 int launch_gain(const isls_gain_args &a, hipStream_t s, const isls_ff_args *ff = nullptr, bool *did_ff = nullptr, bool require_ff = false,
-                bool shared = false, int32_t *memo_hdr = nullptr);
+                bool shared = false, int32_t *memo_hdr = nullptr, void *memo_table = nullptr);
 // gate (shared only, gain_memo.hpp): the pass stands in for the recursion inside the gain pass -- it runs only where *gate is set,
-// and evaluates v and k with that recursion's sums (riccati.hip FF), so k is what the gain launch would have written, bit for bit
-template <typename T> int launch_ff(const isls_ff_args &a, hipStream_t s, bool shared = false, const int32_t *gate = nullptr);
-template <typename T> int launch_ff_record(const isls_ff_args &a, hipStream_t s, bool shared = false, const int32_t *gate = nullptr);
+// and evaluates v and k with that recursion's sums (riccati.hip FF), so k is what the gain launch would have written, bit for bit.
+// K_fill (with gate, required): the K array of the gain launch it stands in for, which the pass writes from the records it stages
+template <typename T>
+int launch_ff(const isls_ff_args &a, hipStream_t s, bool shared = false, const int32_t *gate = nullptr, void *K_fill = nullptr);
+template <typename T>
+int launch_ff_record(const isls_ff_args &a, hipStream_t s, bool shared = false, const int32_t *gate = nullptr, void *K_fill = nullptr);
 template <typename T> int launch_ff_prepare(const isls_ff_prepare_args &a, hipStream_t s);
 template <typename T> int launch_ff_stitch(const isls_ff_args &a, hipStream_t s);
 bool ff_seg_enabled(const isls_ffseg &sg);

@@ -45,6 +45,7 @@ struct GainP {
     const T *reg_mu;               // REG form (isls_reg_args): mu[B], added to the diagonal of Cuu_t (reg_on_x: and of Cxx_t), t <= N-2
     int reg_on_x;
     int32_t *memo;                 // SH form, nullable: header words of the gain memo's entry (gain_memo.hpp)
+    T *memo_table;                 // ... and its table (with memo): where block 0's records go instead of rec
 };
 
 // 1/sqrt(a) by v_rsq + two coupled Newton steps (g -> sqrt(a), h -> 1/(2 sqrt(a))): 9 instructions against the ~30 of
@@ -123,6 +124,10 @@ __device__ __forceinline__ bool chol_upper_rd(const T (&A)[M][M], T (&U)[M][M], 
 // of the loop picked once per wavefront (RS), not a predicate on the stores.  K, k and status stay per trajectory.  Block 0 must
 // write the records even when none of its trajectories is active: it then runs the recursion on trajectory 0's operands
 // (loads only) and aims the K / k stores at spare words of the record buffer behind its own run.
+// With the gain memo (p.memo, gain_memo.hpp) block 0's records go straight into the entry's table, which every reader of the call
+// takes, and behind its step loop block 0 marks the entry filled unless a pivot was not positive: the check kernel of the call
+// has finished before the launch starts and nothing else reads the entry while it runs, so no launch is needed to commit.  The
+// other wavefronts read the entry's `match` word and nothing else of it.
 // REG (isls_riccati_gain_reg_*): the pass runs on Cuu_t + mu_b I (reg_on_x: and Cxx_t + mu_b I) for t <= N-2 -- the lane that owns
 // row i of the stack adds its trajectory's mu to its own diagonal word of the cost row, crow[i], before the row enters the sums,
 // so the factorisation, the V update, A + B K, the records and the feed-forward recursion inside all see the regularised block
@@ -372,7 +377,8 @@ __device__ __forceinline__ void riccati_gain_body(const GainP<T> &p, T *lds, T *
         fd[j] = 2 * (pq < NPAIR ? pq : NPAIR - 1);
         fw[j] = (fd[j] / RSW) * RW + RSRC + fd[j] % RSW;       // (dense records: fw == fd)
     }
-    T *const recg = REC ? p.rec + (int64_t)bx * N * (TPW * RSW) : nullptr;   // the wavefront's records, step 0
+    T *recg = REC ? p.rec + (int64_t)bx * N * (TPW * RSW) : nullptr;         // the wavefront's records, step 0
+    if constexpr (SH && RS) recg = p.memo_table ? p.memo_table : recg;      // block 0 (bx == 0): the memo's table
     // where K and k leave for: the arrays, or (records only) N (NU NX + NU) spare words behind block 0's run of the buffer
     static_assert(!SH || TPW * RSW + NU * NX + NU <= TPW * RW, "spare words of the record buffer behind block 0's run");
     T *const spare = (SH && RS) ? p.rec + (int64_t)N * (TPW * RSW) : nullptr;
@@ -762,8 +768,9 @@ __device__ __forceinline__ void riccati_gain_body(const GainP<T> &p, T *lds, T *
         for (int j = 0; j < JPS + JK; ++j) send(tlast, j);
     }
     if (valid && i == 0 && !pd_ok && p.status) atomicOr(&p.status[b], ISLS_ST_NOT_PD);
-    if constexpr (SH && RS) {                                  // the run the memo would keep: did its pivots stay positive?
-        if (lane == 0 && p.memo) p.memo[kMemoNotPd] = pd_ok ? 0 : 1;
+    if constexpr (SH && RS) {
+        // the run is in the memo's table: kept unless a pivot was not positive (such a table serves this call's readers only)
+        if (lane == 0 && p.memo) { p.memo[kMemoNotPd] = pd_ok ? 0 : 1; p.memo[kMemoFilled] = pd_ok ? 1 : 0; }
     }
 }
 
@@ -806,7 +813,7 @@ inline void gain_args_fill(const isls_gain_args &a, GainP<T> &p)
     p.xhat = p.uhat = p.zx = p.lx = p.zu = p.lu = nullptr; p.kff = nullptr;
     p.lin_par = nullptr; p.lin_par_sb = 0;
     p.reg_mu = nullptr; p.reg_on_x = 0;
-    p.memo = nullptr;
+    p.memo = nullptr; p.memo_table = nullptr;
 }
 // the first feed-forward pass rides along when it would run on this pass's records with time-invariant Qr / Rr rows
 inline bool gain_ff_rides(const isls_gain_args &a, const isls_ff_args *ff)
@@ -827,7 +834,8 @@ inline void gain_ff_fill(const isls_ff_args *ff, GainP<T> &p)
 
 #ifndef ISLS_GAIN_REG_TU
 template <typename T>
-int launch_gain(const isls_gain_args &a, hipStream_t s, const isls_ff_args *ff, bool *did_ff, bool require_ff, bool shared, int32_t *memo_hdr)
+int launch_gain(const isls_gain_args &a, hipStream_t s, const isls_ff_args *ff, bool *did_ff, bool require_ff, bool shared, int32_t *memo_hdr,
+                void *memo_table)
 {
     if (did_ff) *did_ff = false;
     if (const int rc = gain_args_check(a); rc != ISLS_OK) return rc;
@@ -850,8 +858,8 @@ int launch_gain(const isls_gain_args &a, hipStream_t s, const isls_ff_args *ff, 
     p.lin_par = (const T *)a.lin_par; p.lin_par_sb = a.lin_par_sb;
     // shared records (gain_inputs_shared): the structured double-integrator form has them; the caller's readers rely on it
     if (shared && (!lin_di || !gain_inputs_shared(a) || !dims_supported(a.n, a.m))) return ISLS_ERR_ARG;
-    if (memo_hdr && !shared) return ISLS_ERR_ARG;
-    p.memo = memo_hdr;
+    if ((memo_hdr && !shared) || (memo_hdr != nullptr) != (memo_table != nullptr)) return ISLS_ERR_ARG;
+    p.memo = memo_hdr; p.memo_table = (T *)memo_table;
     const bool with_ff = gain_ff_rides(a, ff);
     if (require_ff && !with_ff) return ISLS_OK;
     if (with_ff) gain_ff_fill(ff, p);
@@ -897,8 +905,8 @@ int launch_gain(const isls_gain_args &a, hipStream_t s, const isls_ff_args *ff, 
     if (did_ff) *did_ff = with_ff;
     return check_launch();
 }
-template int launch_gain<double>(const isls_gain_args &, hipStream_t, const isls_ff_args *, bool *, bool, bool, int32_t *);
-template int launch_gain<float>(const isls_gain_args &, hipStream_t, const isls_ff_args *, bool *, bool, bool, int32_t *);
+template int launch_gain<double>(const isls_gain_args &, hipStream_t, const isls_ff_args *, bool *, bool, bool, int32_t *, void *);
+template int launch_gain<float>(const isls_gain_args &, hipStream_t, const isls_ff_args *, bool *, bool, bool, int32_t *, void *);
 #endif  // ISLS_GAIN_REG_TU
 
 

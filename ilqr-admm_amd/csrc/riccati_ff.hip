@@ -300,7 +300,7 @@ __global__ __launch_bounds__(64, OCC) void riccati_ff_kernel(FfP<T> p)
 }
 
 template <typename T>
-int launch_ff(const isls_ff_args &a, hipStream_t s, bool shared, const int32_t *gate)
+int launch_ff(const isls_ff_args &a, hipStream_t s, bool shared, const int32_t *gate, void *K_fill)
 {
     if (a.B < 0 || a.N < 1 || !a.c0x.p || !a.c0u.p || !a.k) return ISLS_ERR_ARG;
     if (!a.rec && (!a.A.p || !a.Bm.p || !a.K || !a.Quu || !a.fac || !a.Qux)) return ISLS_ERR_ARG;
@@ -313,7 +313,7 @@ int launch_ff(const isls_ff_args &a, hipStream_t s, bool shared, const int32_t *
         return ISLS_ERR_UNSUPPORTED;
     if (a.B == 0) return ISLS_OK;
     if (shared && (!a.rec || !dims_supported(a.n, a.m))) return ISLS_ERR_ARG; // the batch's one set of records: record path only
-    if (gate && !shared) return ISLS_ERR_ARG;
+    if ((gate && !shared) || (gate != nullptr) != (K_fill != nullptr)) return ISLS_ERR_ARG;
     if (!dims_supported(a.n, a.m)) return launch_ff_generic<T>(a, s);          // generic.hip
     if ((a._pad > 1 || a.Qr_term) && !a.rec) return ISLS_ERR_UNSUPPORTED;     // feedback columns in one launch, terminal weight block: record path only
     if (a.rec) {                                               // packed records of the gain pass: riccati_ffrec.hip
@@ -321,7 +321,7 @@ int launch_ff(const isls_ff_args &a, hipStream_t s, bool shared, const int32_t *
         if (sg && (a.seg.nseg > 16 || !a.seg.Psi || !a.seg.v || (int64_t)a.seg.nseg * a.seg.seg_len < a.N - 1 ||
                    (int64_t)(a.seg.nseg - 1) * a.seg.seg_len >= a.N - 1))
             return ISLS_ERR_ARG;
-        const int rc = launch_ff_record<T>(a, s, shared, gate);
+        const int rc = launch_ff_record<T>(a, s, shared, gate, K_fill);
         if (rc != ISLS_OK || !sg) return rc;
         return launch_ff_stitch<T>(a, s);
     }
@@ -361,7 +361,7 @@ int launch_ff(const isls_ff_args &a, hipStream_t s, bool shared, const int32_t *
     if (rc != ISLS_OK || !segmented) return rc;
     return launch_ff_stitch<T>(a, s);
 }
-template int launch_ff<double>(const isls_ff_args &, hipStream_t, bool, const int32_t *);
-template int launch_ff<float>(const isls_ff_args &, hipStream_t, bool, const int32_t *);
+template int launch_ff<double>(const isls_ff_args &, hipStream_t, bool, const int32_t *, void *);
+template int launch_ff<float>(const isls_ff_args &, hipStream_t, bool, const int32_t *, void *);
 
 }  // namespace isls

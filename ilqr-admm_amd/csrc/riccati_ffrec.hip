@@ -46,6 +46,7 @@ struct FfRecP {
     const T *lin_par;              // model parameters (isls_linearize_args.model_par), batch stride lin_par_sb
     int64_t lin_par_sb;
     const int32_t *gate;           // FU form: the word that lets the launch run (the gain memo's `match`)
+    T *Kfill;                      // FU form: the K array of the gain launch the pass stands in for
 };
 
 // First form of the pass: Qr / Rr rows that vary with the time step (time-invariant ones take riccati_ffrec2_kernel below).
@@ -272,6 +273,12 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec_kernel(FfRecP<T> p)
 //     qu_r = cu_r + sum_k [A B][k, n + r] v_k,     v_i = (cx_i + sum_k Phi[k, i] v_k) + sum_r K[r, i] cu_r,     Phi[:, i] = A[:, i] + b K[., i]
 // (the lane's column of [A B] with its exact zeros, as there) instead of A'v + K'(B'v) -- so k is what the gain launch itself
 // would have written, bit for bit, and an outer iteration computes the same whether its table was kept or recomputed.
+// The gain launch would also have written the K array: the FU pass has every step's [K | fac] in its slots' LDS anyway, so it
+// reads the K blocks back lane-linearly in the step's one batch of reads (pair e of the TPW blocks for lane e, as the gain pass
+// does with its record image) and sends them to K[b, t] as one 16-byte streaming store per lane and step (n = 6, m = 3: 63 pairs),
+// unconditional like every memory instruction of the loop: the pairs of a slot without an active trajectory go where the first
+// active slot's go (the records are the batch's one set: same words to the same address), so an inactive trajectory's K stays
+// untouched.  The K broadcast launch this replaces took 11.8 us behind the pass's 42.0 us at B = 4096, N = 100.
 constexpr int LIN_NONE = 0, LIN_DI = 1, LIN_ARM3R = 2, LIN_CAR = 3;
 
 template <typename T, int NX, int NU, int D, int OCC, int MODE, int LIN = LIN_NONE, bool SH = false, bool FU = false>
@@ -412,6 +419,25 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec2_kernel(FfRecP<T> p)
     const int ic = xl ? i : 0;
     const int ku = xl ? i % NU : iu;                           // the entry of k this lane stores (x-lanes: copies)
     T *const kbase = p.k + ((int64_t)col * p.B + bb) * N * NU + ku;
+    // FU form: the lane's pieces of the K blocks (see the kernel's head): where they are in LDS, where they go at t = 0
+    static_assert(!FU || ((NU * NX) % 2 == 0 && K_OFF % 2 == 0), "K leaves as aligned pairs");
+    constexpr int KU = NU * NX / 2, JK = FU ? (TPW * KU + kWave - 1) / kWave : 0, JKA = JK > 0 ? JK : 1;
+    int kso[JKA];
+    int64_t kgo[JKA];
+#pragma unroll
+    for (int j = 0; j < JK; ++j) {
+        const int e = lane + kWave * j;
+        const bool in = e < TPW * KU;                           // lanes past the last piece repeat piece 0 of the first active slot
+        const int sl = in ? e / KU : bsh - bx * TPW, pc = in ? e - (e / KU) * KU : 0;
+        const int bk = bx * TPW + sl;
+        const bool ok = bk < p.B && (p.active == nullptr || p.active[bk] != 0);
+        kso[j] = sl * SLOT + K_OFF + 2 * pc;
+        kgo[j] = (int64_t)(ok ? bk : bsh) * N * (NU * NX) + 2 * pc;
+    }
+    if constexpr (FU) {                                        // K[N-1] = 0
+#pragma unroll
+        for (int j = 0; j < JK; ++j) st_stream(reinterpret_cast<V2 *>(p.Kfill + kgo[j] + (int64_t)(N - 1) * (NU * NX)), V2{T(0), T(0)});
+    }
 
     // ---- terminal step: v = cx[N-1] (last segment; the others start from v_in = 0), qu = 0 -> k[t_hi + 1] ... -------------
     T vcur;
@@ -462,6 +488,9 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec2_kernel(FfRecP<T> p)
             // ---- one batch of reads ----
             T dx[NX], du[NU], c0u[NU], col[NX], vv[NX], kcol[NU], facn[NU][NU], qup[NU];
             T v_own = T(0), v_oth = T(0), jm[NJ > 0 ? NJ : 1];
+            V2 fk[JKA];                                        // FU: first of the batch, so that it can leave while the rest arrives
+#pragma unroll
+            for (int j = 0; j < JK; ++j) fk[j] = *reinterpret_cast<const V2 *>(lds + kso[j]);
 #pragma unroll
             for (int j = 0; j < NX; ++j) {
                 dx[j] = rrec[D_OFF + j];
@@ -481,6 +510,12 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec2_kernel(FfRecP<T> p)
                 for (int c = 0; c < NU; ++c) facn[r][c] = rrec[FAC_OFF + r * NU + c];
             }
             __builtin_amdgcn_sched_barrier(0);
+            if constexpr (FU) {                                // K_t on its way (a dead step sends step t_lo's again)
+                const int64_t tk = t > t_lo ? t : t_lo;
+#pragma unroll
+                for (int j = 0; j < JK; ++j) st_stream(reinterpret_cast<V2 *>(p.Kfill + kgo[j] + tk * (NU * NX)), fk[j]);
+                __builtin_amdgcn_sched_barrier(0);
+            }
             // cu (every lane), c_i, the lane's column of [Phi | B] against v
             T cu[NU];
 #pragma unroll
@@ -656,7 +691,7 @@ static void launch_ffrec2(int lin, bool shared, dim3 grid, hipStream_t s, const 
 }
 
 template <typename T>
-int launch_ff_record(const isls_ff_args &a, hipStream_t s, bool shared, const int32_t *gate)
+int launch_ff_record(const isls_ff_args &a, hipStream_t s, bool shared, const int32_t *gate, void *K_fill)
 {
     if ((int64_t)a.N * rec_stride(a.n, a.m) * 64 >= ((int64_t)1 << 31)) return ISLS_ERR_UNSUPPORTED;
     FfRecP<T> p;
@@ -694,8 +729,8 @@ int launch_ff_record(const isls_ff_args &a, hipStream_t s, bool shared, const in
     }
     if (shared && (lin != LIN_DI || a.lin_par_sb != 0)) return ISLS_ERR_ARG;   // one set of records: the form that writes them
     // the stand-in for the recursion inside the gain pass: what gain_ff_rides (riccati.hip) lets that pass take on
-    if (gate && (!shared || a.Qr_term || p.ncol > 1)) return ISLS_ERR_ARG;
-    p.gate = gate;
+    if (gate && (!shared || a.Qr_term || p.ncol > 1 || !K_fill)) return ISLS_ERR_ARG;
+    p.gate = gate; p.Kfill = (T *)K_fill;
     p.lin_par = (const T *)a.lin_par; p.lin_par_sb = a.lin_par_sb;
     // the one-hand-off kernel addresses a step of c0x / c0u with a 32-bit offset
     const int64_t c0lim = ((int64_t)1 << 31) / (a.N > 1 ? a.N - 1 : 1);
@@ -722,7 +757,7 @@ int launch_ff_record(const isls_ff_args &a, hipStream_t s, bool shared, const in
 #undef LAUNCH2
     return check_launch();
 }
-template int launch_ff_record<double>(const isls_ff_args &, hipStream_t, bool, const int32_t *);
-template int launch_ff_record<float>(const isls_ff_args &, hipStream_t, bool, const int32_t *);
+template int launch_ff_record<double>(const isls_ff_args &, hipStream_t, bool, const int32_t *, void *);
+template int launch_ff_record<float>(const isls_ff_args &, hipStream_t, bool, const int32_t *, void *);
 
 }  // namespace isls
