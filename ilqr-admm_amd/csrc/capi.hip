@@ -55,7 +55,7 @@ static int outer_iteration(const isls_outer_args &a, hipStream_t s)
         return rc;
     bool ff_done = false;                                      // the gain pass ran the first feed-forward pass as well
     // the gain pass writes the records in the layout its hint selects and the feed-forward passes read them in theirs
-    if (a.J > 0 && a.gain.rec && a.ff.rec == a.gain.rec && (a.gain.lin_on != 0) != (a.ff.lin_on != 0)) return ISLS_ERR_ARG;
+    if (a.J > 0 && !lin_hints_agree(a.gain, a.ff)) return ISLS_ERR_ARG;
     if (a.ff.lin_on && ff_seg_enabled(a.ff.seg)) return ISLS_ERR_UNSUPPORTED;   // the segment operators need the dense records
     // One set of records for the whole batch (isls_gain_args.rec in include/isls_hip.h): the declared strides and hints say that
     // every trajectory has the same A, B, Cxx, Cuu, Cux, this call's gain pass writes the records its own feed-forward passes and

@@ -8,7 +8,7 @@
 //                      slot in LDS and read as broadcasts):  G_t = Gamma_t Phi_{t+1}..Phi_{t1-1}, Psi_s = Phi_{t0}..Phi_{t1-1}.
 //   ff_stitch_kernel   after the segments of riccati_ff_kernel ran from v_in = 0: v_in(s-1) = v0(t0_s) + Psi_s v_in(s),
 //                      then k_t += G_t v_in(seg(t)) for every step outside the last segment (HBM-bound stream over G).
-#include "isls_common.hpp"
+#include "riccati_shared.hpp"
 
 namespace isls {
 
@@ -154,6 +154,8 @@ __global__ __launch_bounds__(64) void ff_prepare_kernel(FfPrepP<T> p)
                 for (int k = 0; k < NX; ++k) acc += rec[AB_OFF + k * W + NX + r] * psi[k];
                 qu[r] = acc;
             }
+            // (k_from_factor's text, kept here: with the factor block read ahead of the branch on `mode` the fp64 kernel at
+            // n = m = 2 takes 130 registers instead of 128, one wavefront per SIMD less -- DESIGN section 5)
             if (mode == ISLS_SOLVE_CHOL) {
                 T U[NU][NU], rd[NU], x[NU];
 #pragma unroll
@@ -280,26 +282,13 @@ __global__ __launch_bounds__(64) void ff_prepare_rec_kernel(FfPrepP<T> p)
                 for (int k = 0; k < NX; ++k) acc += rec[B_OFF + k * NU + r] * psi[k];
                 qu[r] = acc;
             }
-            if (mode == ISLS_SOLVE_CHOL) {
-                T U[NU][NU], rd[NU], x[NU];
+            T fac[NU][NU];
 #pragma unroll
-                for (int r = 0; r < NU; ++r) {
+            for (int r = 0; r < NU; ++r) {
 #pragma unroll
-                    for (int c = 0; c < NU; ++c) U[r][c] = rec[FAC_OFF + r * NU + c];
-                    rd[r] = U[r][r];
-                }
-                chol_solve<NU>(U, rd, qu, x);
-#pragma unroll
-                for (int r = 0; r < NU; ++r) kap[r] = -x[r];
-            } else {
-#pragma unroll
-                for (int r = 0; r < NU; ++r) {
-                    T acc = T(0);
-#pragma unroll
-                    for (int c = 0; c < NU; ++c) acc += rec[FAC_OFF + r * NU + c] * qu[c];
-                    kap[r] = -acc;
-                }
+                for (int c = 0; c < NU; ++c) fac[r][c] = rec[FAC_OFF + r * NU + c];
             }
+            k_from_factor<NU>(mode, fac, qu, kap);
 #pragma unroll
             for (int i = 0; i < NX; ++i) psi[i] = live ? pn[i] : psi[i];
             if (valid && live) {
@@ -359,7 +348,7 @@ __global__ __launch_bounds__(256) void ff_stitch_kernel(int B, int N, int nseg, 
     }
 }
 
-static bool seg_ok(const isls_ffseg &sg, int N)
+bool ff_seg_ok(const isls_ffseg &sg, int N)
 {
     if (sg.nseg < 2 || sg.nseg > kMaxFfSeg || sg.seg_len < 1 || !sg.G || !sg.Psi || !sg.v) return false;
     const int steps = N - 1;
@@ -375,7 +364,7 @@ int launch_ff_prepare(const isls_ff_prepare_args &a, hipStream_t s)
     if (!a.rec && (!a.A.p || !a.Bm.p || !a.K || !a.Quu || !a.fac || !a.Qux)) return ISLS_ERR_ARG;
     if (a.solve_mode != ISLS_SOLVE_CHOL && a.solve_mode != ISLS_SOLVE_INV) return ISLS_ERR_ARG;
     if (!ff_seg_enabled(a.seg)) return ISLS_OK;                // sequential recursion: nothing to prepare
-    if (!seg_ok(a.seg, a.N)) return ISLS_ERR_ARG;
+    if (!ff_seg_ok(a.seg, a.N)) return ISLS_ERR_ARG;
     if (a.rec) {                                               // operators from the packed records of the gain pass
         if (a.B == 0) return ISLS_OK;
         FfPrepP<T> pr = {};
@@ -418,7 +407,7 @@ template int launch_ff_prepare<float>(const isls_ff_prepare_args &, hipStream_t)
 template <typename T>
 int launch_ff_stitch(const isls_ff_args &a, hipStream_t s)
 {
-    if (!seg_ok(a.seg, a.N)) return ISLS_ERR_ARG;
+    if (!ff_seg_ok(a.seg, a.N)) return ISLS_ERR_ARG;
     const int grid = (a.B + kStitchTraj - 1) / kStitchTraj;
 #define CALL(NX_, NU_)                                                                                         \
     hipLaunchKernelGGL((ff_stitch_kernel<T, NX_, NU_>), dim3(grid, a._pad > 1 ? a._pad : 1), dim3(256), 0, s, a.B, a.N, a.seg.nseg, \

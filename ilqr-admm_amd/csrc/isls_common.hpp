@@ -142,11 +142,11 @@ __device__ __forceinline__ void chol_solve(const T (&U)[M][M], const T (&rd)[M],
     }
 }
 
-// The v / k recursion of the first feed-forward pass exists twice: inside the structured gain pass (riccati.hip, FF, LIN = 1) and
-// as the stand-in pass on the kept table (riccati_ffrec.hip, FU), and the two must agree bit for bit.  Left to the compiler, a
-// sum `acc += a * b` is contracted differently from one kernel to the next (fp32: some pairs become an unfused packed multiply
-// and a packed add), so both kernels write every multiply-add of that recursion through these: always one fused operation.
-// (X = false: the plain expression, for the forms that have no twin.)
+// The v / k recursion of the first feed-forward pass runs in two kernels -- inside the structured gain pass (riccati_gain_kernel.hpp,
+// FF, LIN = 1) and as the stand-in pass on the kept table (riccati_ffrec.hip, FU) -- which must agree bit for bit.  Both call one
+// text of its sums (riccati_shared.hpp).  Left to the compiler, a sum `acc += a * b` is contracted differently from one kernel to
+// the next (fp32: some pairs become an unfused packed multiply and a packed add), so that text writes every multiply-add through
+// these: always one fused operation.  (X = false: the plain expression, for the forms that run in one kernel only.)
 template <bool X = true, typename T>
 __device__ __forceinline__ T ff_mad(T a, T b, T c)
 {
@@ -260,7 +260,27 @@ __host__ __device__ constexpr int rec_stride(int n, int m) { return (n * n + 2 *
 // (the same buffer: isls_ff_record_elems covers the dense layout, the lean one uses a prefix of it).
 __host__ __device__ constexpr int rec_lean_stride(int n, int m) { return (m * n + m * m + rec_model_words(n, m) + 1) & ~1; }
 
+// The model hint of the gain pass and the feed-forward passes (isls_gain_args / isls_ff_args: lin_on, lin_model), decoded once:
+// the form it selects (riccati_ffrec.hip describes the forms; the gain pass runs LIN_DI structured and the others dense, with
+// lean records in all three) or ISLS_ERR_ARG (dimensions the model does not have) / ISLS_ERR_UNSUPPORTED (a model without a form).
+constexpr int LIN_NONE = 0, LIN_DI = 1, LIN_ARM3R = 2, LIN_CAR = 3;
 #ifndef __HIPCC_RTC__
+inline int lin_form(int lin_on, int lin_model, int n, int m, int *form)
+{
+    *form = LIN_NONE;
+    if (!lin_on) return ISLS_OK;
+    if (lin_model == ISLS_MODEL_DI) { if (n != 2 * m) return ISLS_ERR_ARG; *form = LIN_DI; }
+    else if (lin_model == ISLS_MODEL_ARM3R) { if (n != 9 || m != 3) return ISLS_ERR_ARG; *form = LIN_ARM3R; }
+    else if (lin_model == ISLS_MODEL_CAR) { if (n != 4 || m != 2) return ISLS_ERR_ARG; *form = LIN_CAR; }
+    else return ISLS_ERR_UNSUPPORTED;
+    return ISLS_OK;
+}
+// one record layout for writer and reader: a feed-forward pass on the gain pass's records carries the same hint
+inline bool lin_hints_agree(const isls_gain_args &g, const isls_ff_args &ff)
+{
+    return !g.rec || ff.rec != g.rec || (g.lin_on != 0) == (ff.lin_on != 0);
+}
+
 // Do all trajectories of the batch share the inputs of the gain recursion (A, B, Cxx, Cuu, Cux), as far as the strides and hints
 // of the argument block DECLARE it (addresses and values are never compared)?  Then K_t and fac_t are the same for all of them
 // and the outer driver keeps one set of lean records.  The structured double-integrator form only: its A, B are functions of
@@ -283,7 +303,7 @@ template <typename T>
 int launch_gain(const isls_gain_args &a, hipStream_t s, const isls_ff_args *ff = nullptr, bool *did_ff = nullptr, bool require_ff = false,
                 bool shared = false, int32_t *memo_hdr = nullptr, void *memo_table = nullptr);
 // gate (shared only, gain_memo.hpp): the pass stands in for the recursion inside the gain pass -- it runs only where *gate is set,
-// and evaluates v and k with that recursion's sums (riccati.hip FF), so k is what the gain launch would have written, bit for bit.
+// and evaluates v and k with that recursion's sums (riccati_gain_kernel.hpp FF), so k is what the gain launch would have written, bit for bit.
 // K_fill (with gate, required): the K array of the gain launch it stands in for, which the pass writes from the records it stages
 template <typename T>
 int launch_ff(const isls_ff_args &a, hipStream_t s, bool shared = false, const int32_t *gate = nullptr, void *K_fill = nullptr);
@@ -292,6 +312,7 @@ int launch_ff_record(const isls_ff_args &a, hipStream_t s, bool shared = false, 
 template <typename T> int launch_ff_prepare(const isls_ff_prepare_args &a, hipStream_t s);
 template <typename T> int launch_ff_stitch(const isls_ff_args &a, hipStream_t s);
 bool ff_seg_enabled(const isls_ffseg &sg);
+bool ff_seg_ok(const isls_ffseg &sg, int N);   // the arguments of an enabled time-parallel form: buffers, and nseg x seg_len tiling N - 1 steps
 int ff_segments(int N, int nseg_req, int *seg_len);
 template <typename T>
 // last = false (fused form only): further ADMM iterations of the same outer iteration follow, the x-step of a trajectory that

@@ -1,8 +1,7 @@
 // regularize.hip -- per-trajectory Levenberg-Marquardt regularisation of the Riccati gain pass (include/isls_hip.h:
 // isls_riccati_gain_reg_*, isls_reg_update_*).  The REG instantiations of riccati_gain_kernel live in this object, next to the
-// schedule kernel: the kernel template is riccati.hip's, compiled here without its own launcher.
-#define ISLS_GAIN_REG_TU 1
-#include "riccati.hip"
+// schedule kernel.
+#include "riccati_gain_kernel.hpp"
 
 namespace isls {
 
@@ -23,26 +22,15 @@ int launch_gain_reg(const isls_gain_args &a, hipStream_t s, const isls_ff_args *
     gain_args_fill(a, p);
     if (with_ff) gain_ff_fill(ff, p);
     p.reg_mu = (const T *)reg.mu; p.reg_on_x = reg.on_x != 0;
-#define LAUNCH_R(NX_, NU_, MODE_, FF_, REC_, ARR_) \
-    hipLaunchKernelGGL((riccati_gain_kernel<T, NX_, NU_, kGainDepth, MODE_, FF_, REC_, ARR_, 0, false, false, true>), dim3(grid), dim3(64), 0, s, p)
-#define LAUNCH_M(NX_, NU_, MODE_)                                                           \
-    {                                                                                       \
-        if (with_ff) {                                                                      \
-            if constexpr (gain_ff_dims(NX_, NU_)) LAUNCH_R(NX_, NU_, MODE_, true, true, false); \
-        } else if (a.rec) LAUNCH_R(NX_, NU_, MODE_, false, true, false);                    \
-        else LAUNCH_R(NX_, NU_, MODE_, false, false, true);                                 \
-    }
-#define CALL(NX_, NU_)                                                                      \
-    {                                                                                       \
-        constexpr int TPW = kWave / (NX_ + NU_);                                            \
-        const int grid = (a.B + TPW - 1) / TPW;                                             \
-        if (a.solve_mode == ISLS_SOLVE_CHOL) LAUNCH_M(NX_, NU_, ISLS_SOLVE_CHOL)            \
-        else LAUNCH_M(NX_, NU_, ISLS_SOLVE_INV)                                             \
+    const GainForm form = {with_ff, a.rec != nullptr, a.Qux != nullptr, LIN_NONE, false, false};
+#define CALL(NX_, NU_)                                                                                      \
+    {                                                                                                       \
+        const int grid = (a.B + kWave / (NX_ + NU_) - 1) / (kWave / (NX_ + NU_));                           \
+        if (a.solve_mode == ISLS_SOLVE_CHOL) launch_gain_form<T, NX_, NU_, ISLS_SOLVE_CHOL, true>(form, grid, s, p); \
+        else launch_gain_form<T, NX_, NU_, ISLS_SOLVE_INV, true>(form, grid, s, p);                         \
     }
     ISLS_DISPATCH_DIMS(a.n, a.m, CALL)
 #undef CALL
-#undef LAUNCH_M
-#undef LAUNCH_R
     return check_launch();
 }
 template int launch_gain_reg<double>(const isls_gain_args &, hipStream_t, const isls_ff_args *, const isls_reg_args &);

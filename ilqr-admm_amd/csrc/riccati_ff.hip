@@ -20,7 +20,7 @@
 // cuts the horizon into segments that recurse concurrently from v_in = 0, ff_stitch_kernel chains the true
 // segment inputs through the transfer matrices and adds G_t v_in to k_t, and ff_prepare_kernel produces those
 // operators once per gain pass by pushing the n unit vectors through the homogeneous recursion.
-#include "isls_common.hpp"
+#include "riccati_shared.hpp"
 
 namespace isls {
 
@@ -244,29 +244,14 @@ __global__ __launch_bounds__(64, OCC) void riccati_ff_kernel(FfP<T> p)
             slot_sync();                                           // (b) qu visible; every lane has read v
 
             // k_t = -Quu^{-1} qu  (every lane), then v_i for x-lanes
-            T qu[NU], kt[NU];
+            T qu[NU], kt[NU], fac[NU][NU];
 #pragma unroll
-            for (int r = 0; r < NU; ++r) qu[r] = rec[QU_OFF + r];
-            if (p.mode == ISLS_SOLVE_CHOL) {
-                T U[NU][NU], rd[NU], x[NU];
+            for (int r = 0; r < NU; ++r) {
+                qu[r] = rec[QU_OFF + r];
 #pragma unroll
-                for (int r = 0; r < NU; ++r) {
-#pragma unroll
-                    for (int c = 0; c < NU; ++c) U[r][c] = rec[FAC_OFF + r * NU + c];
-                    rd[r] = U[r][r];
-                }
-                chol_solve<NU>(U, rd, qu, x);
-#pragma unroll
-                for (int r = 0; r < NU; ++r) kt[r] = -x[r];
-            } else {
-#pragma unroll
-                for (int r = 0; r < NU; ++r) {
-                    T acc = T(0);
-#pragma unroll
-                    for (int c = 0; c < NU; ++c) acc += rec[FAC_OFF + r * NU + c] * qu[c];
-                    kt[r] = -acc;
-                }
+                for (int c = 0; c < NU; ++c) fac[r][c] = rec[FAC_OFF + r * NU + c];
             }
+            k_from_factor<NU>(p.mode, fac, qu, kt);
             // v_i = qx_i + (K'qu)_i + (K'Quu k)_i + (Qux'k)_i ; u-lanes evaluate the same expression on their
             // (clamped) column and throw it away: no divergence
             const int ic = xl ? i : 0;
@@ -316,13 +301,11 @@ int launch_ff(const isls_ff_args &a, hipStream_t s, bool shared, const int32_t *
     if ((gate && !shared) || (gate != nullptr) != (K_fill != nullptr)) return ISLS_ERR_ARG;
     if (!dims_supported(a.n, a.m)) return launch_ff_generic<T>(a, s);          // generic.hip
     if ((a._pad > 1 || a.Qr_term) && !a.rec) return ISLS_ERR_UNSUPPORTED;     // feedback columns in one launch, terminal weight block: record path only
+    const bool segmented = ff_seg_enabled(a.seg) && a.N > 2;
+    if (segmented && !ff_seg_ok(a.seg, a.N)) return ISLS_ERR_ARG;
     if (a.rec) {                                               // packed records of the gain pass: riccati_ffrec.hip
-        const bool sg = ff_seg_enabled(a.seg) && a.N > 2;
-        if (sg && (a.seg.nseg > 16 || !a.seg.Psi || !a.seg.v || (int64_t)a.seg.nseg * a.seg.seg_len < a.N - 1 ||
-                   (int64_t)(a.seg.nseg - 1) * a.seg.seg_len >= a.N - 1))
-            return ISLS_ERR_ARG;
         const int rc = launch_ff_record<T>(a, s, shared, gate, K_fill);
-        if (rc != ISLS_OK || !sg) return rc;
+        if (rc != ISLS_OK || !segmented) return rc;
         return launch_ff_stitch<T>(a, s);
     }
     FfP<T> p;
@@ -333,13 +316,9 @@ int launch_ff(const isls_ff_args &a, hipStream_t s, bool shared, const int32_t *
     p.zx = (const T *)a.zx; p.lx = (const T *)a.lx; p.zu = (const T *)a.zu; p.lu = (const T *)a.lu;
     p.K = (const T *)a.K; p.Quu = (const T *)a.Quu; p.fac = (const T *)a.fac; p.Qux = (const T *)a.Qux;
     p.k = (T *)a.k; p.active = a.active;
-    const bool segmented = ff_seg_enabled(a.seg) && a.N > 2;
     p.nseg = segmented ? a.seg.nseg : 1;
     p.seg_len = segmented ? a.seg.seg_len : (a.N > 1 ? a.N - 1 : 1);
     p.vseg = segmented ? (T *)a.seg.v : nullptr;
-    if (segmented && (a.seg.nseg > 16 || !a.seg.Psi || !a.seg.v || (int64_t)a.seg.nseg * a.seg.seg_len < a.N - 1 ||
-                      (int64_t)(a.seg.nseg - 1) * a.seg.seg_len >= a.N - 1))
-        return ISLS_ERR_ARG;
     // weights that do not depend on the time step (or are absent) are loaded once per lane instead of once per step
     const bool rowc = (!a.Qr.p || a.Qr.st == 0) && (!a.Rr.p || a.Rr.st == 0);
 #define CALL(NX_, NU_)                                                                                 \

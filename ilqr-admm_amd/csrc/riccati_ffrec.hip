@@ -13,7 +13,7 @@
 //
 // Structure (slots, register ring, unconditional staging with dump words, padded dead steps, time-parallel segments via
 // blockIdx.y) is that of riccati_ff.hip; see there for the reasoning.
-#include "isls_common.hpp"
+#include "riccati_shared.hpp"
 
 namespace isls {
 
@@ -207,29 +207,14 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec_kernel(FfRecP<T> p)
             vcur = live ? vnew : vcur;
             rec[xl ? V_OFF + i : DUMP_OFF] = vcur;                 // read again only after the next (a)
             // k_t = -Quu^{-1} qu from the cached factor (every lane; u-lane r keeps entry r)
-            T qu[NU], kt[NU];
+            T qu[NU], kt[NU], fac[NU][NU];
 #pragma unroll
-            for (int r = 0; r < NU; ++r) qu[r] = rec[QU_OFF + r];
-            if (p.mode == ISLS_SOLVE_CHOL) {
-                T U[NU][NU], rd[NU], x[NU];
+            for (int r = 0; r < NU; ++r) {
+                qu[r] = rec[QU_OFF + r];
 #pragma unroll
-                for (int r = 0; r < NU; ++r) {
-#pragma unroll
-                    for (int c = 0; c < NU; ++c) U[r][c] = rec[FAC_OFF + r * NU + c];
-                    rd[r] = U[r][r];
-                }
-                chol_solve<NU>(U, rd, qu, x);
-#pragma unroll
-                for (int r = 0; r < NU; ++r) kt[r] = -x[r];
-            } else {
-#pragma unroll
-                for (int r = 0; r < NU; ++r) {
-                    T a2 = T(0);
-#pragma unroll
-                    for (int c = 0; c < NU; ++c) a2 += rec[FAC_OFF + r * NU + c] * qu[c];
-                    kt[r] = -a2;
-                }
+                for (int c = 0; c < NU; ++c) fac[r][c] = rec[FAC_OFF + r * NU + c];
             }
+            k_from_factor<NU>(p.mode, fac, qu, kt);
             T kv = kt[0];
 #pragma unroll
             for (int r = 1; r < NU; ++r) kv = (iu == r) ? kt[r] : kv;
@@ -264,10 +249,10 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec_kernel(FfRecP<T> p)
 //             fac):  (A'v)_0 = v_0, (A'v)_1 = v_1, (A'v)_2 = a02 v_0 + a12 v_1 + v_2, (A'v)_3 = a03 v_0 + a13 v_1 + a23 v_2 + v_3,
 //             B'v = (b20 v_2, dt v_3)
 // -- the same products as the dense form in another association (results equal up to rounding, same tolerance against the oracle).
-// SH (launch_ff's `shared`, LIN_DI): the batch has ONE set of records, in slot 0 of block 0 (riccati.hip); every slot of every
+// SH (launch_ff's `shared`, LIN_DI): the batch has ONE set of records, in slot 0 of block 0 (riccati_gain_kernel.hpp); every slot of every
 // wavefront stages that record.  The table is N lean records (22 KB at N = 100, n = 6, m = 3) that every wavefront of the launch
 // reads again: plain loads, so that it stays in the caches, where the per-trajectory records stream through with `nt`.
-// FU (SH only; launch_ff_record's `gate`): the pass stands in for the v / k recursion INSIDE the gain pass (riccati.hip, FF) on a
+// FU (SH only; launch_ff_record's `gate`): the pass stands in for the v / k recursion INSIDE the gain pass (riccati_gain_kernel.hpp, FF) on a
 // call whose gain launch returned at once because the gain memo's table is still valid (gain_memo.hpp).  Every wavefront returns
 // at the top unless *gate is set, and v, qu and k are evaluated with that recursion's sums, term by term in its order:
 //     qu_r = cu_r + sum_k [A B][k, n + r] v_k,     v_i = (cx_i + sum_k Phi[k, i] v_k) + sum_r K[r, i] cu_r,     Phi[:, i] = A[:, i] + b K[., i]
@@ -279,8 +264,6 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec_kernel(FfRecP<T> p)
 // unconditional like every memory instruction of the loop: the pairs of a slot without an active trajectory go where the first
 // active slot's go (the records are the batch's one set: same words to the same address), so an inactive trajectory's K stays
 // untouched.  The K broadcast launch this replaces took 11.8 us behind the pass's 42.0 us at B = 4096, N = 100.
-constexpr int LIN_NONE = 0, LIN_DI = 1, LIN_ARM3R = 2, LIN_CAR = 3;
-
 template <typename T, int NX, int NU, int D, int OCC, int MODE, int LIN = LIN_NONE, bool SH = false, bool FU = false>
 __global__ __launch_bounds__(64, OCC) void riccati_ffrec2_kernel(FfRecP<T> p)
 {
@@ -380,18 +363,14 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec2_kernel(FfRecP<T> p)
     const T sown = LIN == LIN_ARM3R ? ((xl && i < 6) ? T(1) : T(0)) : T(1);
     const T cv = LIN == LIN_DI ? ((xl && i >= NU) ? la : T(0)) : ((xl && i >= 3 && i < 6) ? ldt : T(0));
     const T cj = LIN == LIN_ARM3R ? ((xl && i < 3) ? T(1) : ((xl && i < 6) ? ldt : T(0))) : T(0);
-    // FU form: the lane's column of [A B], zeros included (riccati.hip's colc)
+    // FU form: the lane's column of [A B], zeros included
     T colc[NX];
 #pragma unroll
     for (int k = 0; k < NX; ++k) colc[k] = T(0);
     if constexpr (FU) {
         T c1, c2;
         int r1, r2;
-        if (xl && i < NU) { c1 = T(1); r1 = i; c2 = T(0); r2 = i; }
-        else if (xl) { c1 = la; r1 = i - NU; c2 = T(1); r2 = i; }
-        else { c1 = lb0; r1 = iu; c2 = lb1; r2 = NU + iu; }
-#pragma unroll
-        for (int k = 0; k < NX; ++k) colc[k] = (k == r1) ? c1 : ((k == r2) ? c2 : T(0));
+        di_column<NX, NU>(xl, i, iu, la, lb0, lb1, c1, r1, c2, r2, colc);
     }
 
     struct Stage {
@@ -424,16 +403,7 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec2_kernel(FfRecP<T> p)
     constexpr int KU = NU * NX / 2, JK = FU ? (TPW * KU + kWave - 1) / kWave : 0, JKA = JK > 0 ? JK : 1;
     int kso[JKA];
     int64_t kgo[JKA];
-#pragma unroll
-    for (int j = 0; j < JK; ++j) {
-        const int e = lane + kWave * j;
-        const bool in = e < TPW * KU;                           // lanes past the last piece repeat piece 0 of the first active slot
-        const int sl = in ? e / KU : bsh - bx * TPW, pc = in ? e - (e / KU) * KU : 0;
-        const int bk = bx * TPW + sl;
-        const bool ok = bk < p.B && (p.active == nullptr || p.active[bk] != 0);
-        kso[j] = sl * SLOT + K_OFF + 2 * pc;
-        kgo[j] = (int64_t)(ok ? bk : bsh) * N * (NU * NX) + 2 * pc;
-    }
+    k_piece_plan<JK, KU, 2, NU * NX>(lane, bx, TPW, SLOT, K_OFF, bsh - bx * TPW, bsh, p.B, p.active, N, kso, kgo);
     if constexpr (FU) {                                        // K[N-1] = 0
 #pragma unroll
         for (int j = 0; j < JK; ++j) st_stream(reinterpret_cast<V2 *>(p.Kfill + kgo[j] + (int64_t)(N - 1) * (NU * NX)), V2{T(0), T(0)});
@@ -446,11 +416,11 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec2_kernel(FfRecP<T> p)
         fetch(N - 1, term);
         rec[d_dst] = dmask * (hmask * term.hv - (term.zv - term.lv));
         slot_sync();
-        T sacc = T(0);
         const T *qT = (p.Qr_term && xl) ? p.Qr_term + (int64_t)bb * p.Qr.sb + i * NX : nullptr;   // the terminal step's own weight row
+        T rowT[NX], dT[NX];
 #pragma unroll
-        for (int j = 0; j < NX; ++j) sacc = ff_mad<FU>(qT ? T(2) * qT[j] : qrow[j], rrec[D_OFF + j], sacc);
-        const T cterm = c0m * term.c0 + sacc;                  // u-lanes: unused
+        for (int j = 0; j < NX; ++j) { rowT[j] = qT ? T(2) * qT[j] : qrow[j]; dT[j] = rrec[D_OFF + j]; }
+        const T cterm = ff_cost_grad<NX, FU>(c0m * term.c0, rowT, dT);   // u-lanes: unused
         vcur = (last && xl) ? cterm : T(0);
         rec[o_dst] = xl ? vcur : T(0);                         // v, and qu = 0: the first k the loop emits is k[N-1] = 0 (last segment)
         slot_sync();
@@ -519,6 +489,8 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec2_kernel(FfRecP<T> p)
             // cu (every lane), c_i, the lane's column of [Phi | B] against v
             T cu[NU];
 #pragma unroll
+            // (ff_cost_grad's sum, written out: through the helper the scheduler orders this batch so that the stand-alone
+            // structured pass takes 50.0 instead of 45.5 us at B = 4096, N = 100, fp64 -- DESIGN section 5)
             for (int r = 0; r < NU; ++r) {
                 T sacc = T(0);
 #pragma unroll
@@ -535,30 +507,14 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec2_kernel(FfRecP<T> p)
             for (int r = 0; r < NU; ++r) ci = (!xl && iu == r) ? cu[r] : ci;
             T qi, vnew;
             if constexpr (!LEAN) {
-                T acc = T(0);
-#pragma unroll
-                for (int k = 0; k < NX; ++k) acc += col[k] * vv[k];
-                qi = ci + acc;                                 // x-lanes: cx_i + (Phi'v)_i; u-lanes: qu_r
-                T kcu = T(0);
-#pragma unroll
-                for (int r = 0; r < NU; ++r) kcu += kcol[r] * cu[r];
-                vnew = qi + kcu;
+                qi = ff_qu<NX, false>(ci, col, vv);            // x-lanes: cx_i + (Phi'v)_i; u-lanes: qu_r
+                vnew = qi + ff_dot<NU, false>(kcol, cu);
             } else if constexpr (FU) {
-                T acc = T(0), acc2 = T(0), kcu = T(0), phc[NX];
+                T phc[NX];
 #pragma unroll
-                for (int k = 0; k < NX; ++k) acc = ff_mad(colc[k], vv[k], acc);
-#pragma unroll
-                for (int k = 0; k < NX; ++k) {
-                    T ph = colc[k];
-                    ph = ff_mad(k < NU ? lb0 : lb1, kcol[k % NU], ph);   // row k of B has one entry
-                    phc[k] = ph;
-                }
-#pragma unroll
-                for (int k = 0; k < NX; ++k) acc2 = ff_mad(phc[k], vv[k], acc2);
-#pragma unroll
-                for (int r = 0; r < NU; ++r) kcu = ff_mad(kcol[r], cu[r], kcu);
-                qi = ci + acc;                                 // u-lanes: qu_r
-                vnew = (ci + acc2) + kcu;                      // x-lanes: v_i
+                for (int k = 0; k < NX; ++k) phc[k] = di_phi<NU>(k, colc[k], lb0, lb1, kcol);
+                qi = ff_qu<NX, true>(ci, colc, vv);            // u-lanes: qu_r
+                vnew = ff_vi<NX, NU, true>(ci, phc, vv, kcol, cu);   // x-lanes: v_i
             } else {
                 T w[NU], jvo = T(0);                           // w = B'v; jvo = (J'v_ee)_o of the lane's own o
                 if constexpr (LIN == LIN_DI) {
@@ -593,22 +549,7 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec2_kernel(FfRecP<T> p)
             vcur = live ? vnew : vcur;
             // k of the previous step from its cached factor and qu (this step's hand-off delivered qu)
             T kt[NU];
-            if constexpr (MODE == ISLS_SOLVE_CHOL) {
-                T rd[NU], x[NU];
-#pragma unroll
-                for (int r = 0; r < NU; ++r) rd[r] = fac_h[r][r];
-                chol_solve_mad<NU, FU>(fac_h, rd, qup, x);
-#pragma unroll
-                for (int r = 0; r < NU; ++r) kt[r] = FU ? -x[r] : T(0) - x[r];     // -x, and +0 for the k[N-1] = 0 the first iteration emits
-            } else {
-#pragma unroll
-                for (int r = 0; r < NU; ++r) {
-                    T a2 = T(0);
-#pragma unroll
-                    for (int c = 0; c < NU; ++c) a2 = ff_mad<FU>(fac_h[r][c], qup[c], a2);
-                    kt[r] = FU ? -a2 : T(0) - a2;
-                }
-            }
+            k_from_factor<NU, FU, !FU>(MODE, fac_h, qup, kt);      // 0 - x: +0 for the k[N-1] = 0 the first iteration emits (FU: below)
             T kv = kt[0];
 #pragma unroll
             for (int r = 1; r < NU; ++r) kv = (ku == r) ? kt[r] : kv;
@@ -635,22 +576,7 @@ __global__ __launch_bounds__(64, OCC) void riccati_ffrec2_kernel(FfRecP<T> p)
         T qup[NU], kt[NU];
 #pragma unroll
         for (int r = 0; r < NU; ++r) qup[r] = rrec[QU_OFF + r];
-        if constexpr (MODE == ISLS_SOLVE_CHOL) {
-            T rd[NU], x[NU];
-#pragma unroll
-            for (int r = 0; r < NU; ++r) rd[r] = fac_h[r][r];
-            chol_solve_mad<NU, FU>(fac_h, rd, qup, x);
-#pragma unroll
-            for (int r = 0; r < NU; ++r) kt[r] = -x[r];
-        } else {
-#pragma unroll
-            for (int r = 0; r < NU; ++r) {
-                T a2 = T(0);
-#pragma unroll
-                for (int c = 0; c < NU; ++c) a2 = ff_mad<FU>(fac_h[r][c], qup[c], a2);
-                kt[r] = -a2;
-            }
-        }
+        k_from_factor<NU, FU>(MODE, fac_h, qup, kt);
         T kv = kt[0];
 #pragma unroll
         for (int r = 1; r < NU; ++r) kv = (ku == r) ? kt[r] : kv;
@@ -719,16 +645,13 @@ int launch_ff_record(const isls_ff_args &a, hipStream_t s, bool shared, const in
     // only the one-hand-off kernel reads -- time-varying weights or the time-parallel form (its operators come from the dense
     // records) are ISLS_ERR_UNSUPPORTED, not a fall-back
     int lin = LIN_NONE;
-    if (a.lin_on) {
-        if (a.lin_model == ISLS_MODEL_DI) { if (a.n != 2 * a.m) return ISLS_ERR_ARG; lin = LIN_DI; }
-        else if (a.lin_model == ISLS_MODEL_ARM3R) { if (a.n != 9 || a.m != 3) return ISLS_ERR_ARG; lin = LIN_ARM3R; }
-        else if (a.lin_model == ISLS_MODEL_CAR) { if (a.n != 4 || a.m != 2) return ISLS_ERR_ARG; lin = LIN_CAR; }
-        else return ISLS_ERR_UNSUPPORTED;
+    if (const int rc = lin_form(a.lin_on, a.lin_model, a.n, a.m, &lin); rc != ISLS_OK) return rc;
+    if (lin != LIN_NONE) {
         if (!a.lin_par) return ISLS_ERR_ARG;
         if (!rowc || segmented) return ISLS_ERR_UNSUPPORTED;
     }
     if (shared && (lin != LIN_DI || a.lin_par_sb != 0)) return ISLS_ERR_ARG;   // one set of records: the form that writes them
-    // the stand-in for the recursion inside the gain pass: what gain_ff_rides (riccati.hip) lets that pass take on
+    // the stand-in for the recursion inside the gain pass: what gain_ff_rides (riccati_gain_kernel.hpp) lets that pass take on
     if (gate && (!shared || a.Qr_term || p.ncol > 1 || !K_fill)) return ISLS_ERR_ARG;
     p.gate = gate; p.Kfill = (T *)K_fill;
     p.lin_par = (const T *)a.lin_par; p.lin_par_sb = a.lin_par_sb;

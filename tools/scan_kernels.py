@@ -3,6 +3,9 @@
 and workgroup size of every gfx950 kernel, read from the code objects inside the library's HIP fat binary.
 
     python tools/scan_kernels.py [--lib path] [--filter substring] [--scratch-only]
+    python tools/scan_kernels.py [--lib path] --against OTHER.so [--isa]      what a change to the sources did to the kernels:
+                                 kernels in one library only, kernels whose registers / scratch / LDS differ and, with --isa,
+                                 kernels whose disassembly differs (exit status 1 if any is listed)
 
 Flags the two things that silently halve a kernel: scratch memory in use (register spills) and a register count just
 past an occupancy step (512 / 256 / 168 / 128 registers per lane = 1 / 2 / 3 / 4 wavefronts per SIMD).
@@ -19,6 +22,7 @@ import msgpack
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEFAULT_LIB = os.path.join(ROOT, "ilqr-admm_amd", "csrc", "libisls_hip.so")
 OBJCOPY = "/opt/rocm/lib/llvm/bin/llvm-objcopy"
+OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 
 
@@ -63,14 +67,17 @@ def _metadata(elf):
     return None
 
 
-def kernel_table(path=DEFAULT_LIB):
-    """{demangled-ish kernel symbol: dict(vgpr, agpr, sgpr, scratch, lds, wg)} for every gfx950 kernel of the library."""
+def _fatbin(path):
     with tempfile.TemporaryDirectory() as td:
         fb, dummy = os.path.join(td, "fat.bin"), os.path.join(td, "copy.so")
         subprocess.run([OBJCOPY, f"--dump-section=.hip_fatbin={fb}", path, dummy], check=True, capture_output=True)
-        fat = open(fb, "rb").read()
+        return open(fb, "rb").read()
+
+
+def kernel_table(path=DEFAULT_LIB):
+    """{demangled-ish kernel symbol: dict(vgpr, agpr, sgpr, scratch, lds, wg)} for every gfx950 kernel of the library."""
     out = {}
-    for elf in _code_objects(fat):
+    for elf in _code_objects(_fatbin(path)):
         md = _metadata(elf)
         for k in (md or {}).get("amdhsa.kernels", []):
             out[k[".name"]] = dict(vgpr=k.get(".vgpr_count", 0), agpr=k.get(".agpr_count", 0), sgpr=k.get(".sgpr_count", 0),
@@ -87,12 +94,66 @@ def demangle(names):
         return list(names)
 
 
+def kernel_isa(path=DEFAULT_LIB):
+    """{kernel symbol: instruction text} of every gfx950 kernel of the library: each code object disassembled with the ROCm
+    llvm-objdump -d and split by symbol; addresses and encodings (the comment column) are dropped."""
+    kernels = set(kernel_table(path))
+    out = {}
+    with tempfile.TemporaryDirectory() as td:
+        for n, elf in enumerate(_code_objects(_fatbin(path))):
+            co = os.path.join(td, f"{n}.co")
+            open(co, "wb").write(elf)
+            text = subprocess.run([OBJDUMP, "-d", co], check=True, capture_output=True, text=True).stdout
+            sym = None
+            for line in text.split("\n"):
+                if line.endswith(">:") and "<" in line:
+                    sym = line[line.index("<") + 1:-2]
+                    sym = sym if sym in kernels else None
+                    if sym:
+                        out[sym] = []
+                elif sym and line.strip():
+                    out[sym].append(line.split("//")[0].strip())
+    return {k: "\n".join(v) for k, v in out.items()}
+
+
+def compare(lib, other, isa, flt):
+    """What differs between the kernels of two builds of the library; returns the number of kernels listed."""
+    fields = ("vgpr", "agpr", "sgpr", "scratch", "lds", "spill")
+    ta, tb = kernel_table(lib), kernel_table(other)
+    nice = dict(zip(sorted(set(ta) | set(tb)), demangle(sorted(set(ta) | set(tb)))))
+    short = lambda n: nice[n].replace("void isls::", "").split("(")[0]
+    keep = lambda n: not flt or flt in short(n)
+    figures = lambda k: " ".join(f"{f} {k[f]}" for f in fields)
+    listed = 0
+    for n in sorted(set(ta) ^ set(tb)):
+        if keep(n):
+            print(f"only in {lib if n in ta else other}: {short(n)}")
+            listed += 1
+    both = [n for n in sorted(set(ta) & set(tb)) if keep(n)]
+    ia, ib = (kernel_isa(lib), kernel_isa(other)) if isa else ({}, {})
+    for n in both:
+        res = any(ta[n][f] != tb[n][f] for f in fields)
+        txt = isa and ia.get(n) != ib.get(n)
+        if res or txt:
+            what = " and ".join(w for w, on in (("resources", res), ("instruction text", txt)) if on)
+            lines = f" ({ia[n].count(chr(10)) + 1} / {ib[n].count(chr(10)) + 1} instructions)" if txt else ""
+            print(f"{what} differ: {short(n)}{lines}\n    {lib}: {figures(ta[n])}\n    {other}: {figures(tb[n])}")
+            listed += 1
+    print(f"{len(ta)} kernels in {lib}, {len(tb)} in {other}; {len(both)} compared by resources"
+          f"{' and instruction text' if isa else ''}; {listed} listed")
+    return listed
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lib", default=DEFAULT_LIB)
     ap.add_argument("--filter", default="")
     ap.add_argument("--scratch-only", action="store_true")
+    ap.add_argument("--against", metavar="OTHER.so", help="list the kernels that differ between --lib and this library")
+    ap.add_argument("--isa", action="store_true", help="with --against: compare the disassembly of every kernel as well")
     a = ap.parse_args()
+    if a.against:
+        sys.exit(1 if compare(a.lib, a.against, a.isa, a.filter) else 0)
     tab = kernel_table(a.lib)
     names = sorted(tab)
     nice = dict(zip(names, demangle(names)))
