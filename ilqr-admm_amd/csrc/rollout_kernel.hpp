@@ -69,6 +69,7 @@ struct RoP {
     View<T> fa_xlo, fa_xhi, fa_ulo, fa_uhi;
     int32_t *fa_active, *fa_iters;
     int64_t cpar_sb;               // a user cost's parameters: 0 = shared, else one row of that many words per trajectory
+                                   // (a user cost's table [N][NTAB] travels in ztab / ztab_sb, which such a cost does not use otherwise)
     // where K_t is read: trajectory b's K_0 at K + b * K_sb, a step further K_st words on.  The K array: N m n and m n; the
     // batch's one set of lean records (launch_rollout's shared_rec): 0 and the words between two steps of a record slot
     int64_t K_sb;
@@ -79,6 +80,11 @@ struct RoP {
 // A run-time compiled program that carries a user cost defines ISLS_USER_COST_NPAR before it includes this header and
 // specialises RoCost<T, NX, NU, true> (user_cost.hpp): the stage cost then replaces the via-point, pseudo-Huber and u_std terms
 // of the search.  The library's own build takes the primary template: no state, no code.
+// A user cost with a per-step table (NTAB words per step, isls_user_cost_create_tab) gets the row of step t the way the step's
+// other operands arrive: the slot's lanes fetch its words D steps ahead -- single words, one per lane and load, a ring of its own
+// beside the pair ring, so the load plan and with it the (JM, OCC) variant set stay the built-in family's --, drop them into a
+// double-buffered side record behind the model's LDS words ahead of the step's slot_sync(), and `stage` reads them back as
+// broadcasts.  Every load stays inside the row it belongs to (lanes without a word repeat word 0 and write the dump word).
 #ifdef ISLS_USER_COST_NPAR
 constexpr bool kRoUserCost = true;
 #else
@@ -86,9 +92,14 @@ constexpr bool kRoUserCost = false;
 #endif
 template <typename T, int NX, int NU, bool ON>
 struct RoCost {
+    static constexpr int NTAB = 0;
     __device__ __forceinline__ void load(const T *) {}
-    __device__ __forceinline__ T stage(const T (&)[NX], const T (&)[NU], int, int) const { return T(0); }
+    __device__ __forceinline__ T stage(const T (&)[NX], const T (&)[NU], const T *, int, int) const { return T(0); }
 };
+// one side record of a table row: its words padded to an even count, and two dump words
+__host__ __device__ constexpr int ro_tab_rec(int ntab) { return ntab > 0 ? ntab + (ntab & 1) + 2 : 0; }
+// the slot's model words with a table cost: the model's own (even), then the two side records
+__host__ __device__ constexpr int ro_mdl_words(int mdlw, int ntab) { return ntab > 0 ? mdlw + (mdlw & 1) + 2 * ro_tab_rec(ntab) : mdlw; }
 
 // ---- built-in forward models -------------------------------------------------
 // sin_cos: isls_common.hpp
@@ -484,7 +495,10 @@ __global__ __launch_bounds__(64, OCC) void rollout_kernel(RoP<T> p)
     const int L = p.L, N = p.N, NSEG = p.nseg, S = p.seg_len;
     const int GL = L > 8 ? L : 8, TPW = p.tpw;
     const bool stage_on = p.stage_on != 0;
-    constexpr int MDLW = Model<T, NX, NU, MODEL>::LDS_WORDS;
+    constexpr int NTAB = RoCost<T, NX, NU, kRoUserCost>::NTAB, TABP = ro_tab_rec(NTAB);   // a user cost's table row, its side record
+    constexpr int MDLW = ro_mdl_words(Model<T, NX, NU, MODEL>::LDS_WORDS, NTAB);
+    // single-word loads per lane and step that cover the row in the narrowest slot of the occupancy class (16 lanes / 8 lanes)
+    constexpr int TL = NTAB > 0 ? (NTAB + (OCC == 2 ? 16 : 8) - 1) / (OCC == 2 ? 16 : 8) : 1;
     const int SLOT = LY::slot_elems(L, GL, NSEG, N, stage_on, MDLW);
     const int lane = threadIdx.x;
     // lanes beyond TPW*GL join the last slot as extra idle candidate lanes (c >= GL): they help nobody and
@@ -500,6 +514,7 @@ __global__ __launch_bounds__(64, OCC) void rollout_kernel(RoP<T> p)
     T *slot = lds + s * SLOT;
     T *c_aug = slot, *c_pln = c_aug + GL, *mdl = c_pln + GL;
     T *recs = static_cast<T *>(__builtin_assume_aligned(mdl + LY::mdl_elems(MDLW), W == 2 ? 2 * sizeof(T) : sizeof(T)));
+    T *const tabrec = recs - 2 * TABP;                         // the table row's side records [2][TABP], right below the records
     T *ck = recs + 2 * RECP;
     T *stage = recs;                                           // winner trajectory: x over the dead records + checkpoints,
     const int uoff = p.u_off;                                  // u behind them (recorded during the search)
@@ -539,6 +554,13 @@ __global__ __launch_bounds__(64, OCC) void rollout_kernel(RoP<T> p)
             mb0 = hb ? T(1) : T(0);
         }
     });
+    // the table row: load j of a lane fetches word c + GL * j of it; lanes past its end repeat word 0 and store nothing
+    const char *pt[TL];
+    if constexpr (NTAB > 0) {
+        const T *trow = p.ztab + (int64_t)bb * p.ztab_sb;      // row 0 of the trajectory's table (RoP::ztab: the table of a user cost)
+#pragma unroll
+        for (int j = 0; j < TL; ++j) pt[j] = reinterpret_cast<const char *>(trow + ((c < GL && c + GL * j < NTAB) ? c + GL * j : 0));
+    }
     // both records start as zeros (absent operands are never written); time-invariant AL weights go in once
     for (int e = c; e < 2 * RECP; e += GL) recs[e] = T(0);
     slot_sync();
@@ -609,6 +631,8 @@ __global__ __launch_bounds__(64, OCC) void rollout_kernel(RoP<T> p)
         // the fetches walk t = 0, 1, 2, ..., so a pointer advances by its stride after every fetch until it sits on step
         // N-1 (the tail's padding fetches repeat that step).
         Vec ra[D][JM], rb[D];
+        T rt[D][TL];                                           // the table row's ring (NTAB > 0)
+        constexpr int64_t stpt = (int64_t)NTAB * (int64_t)sizeof(T);
         const char *ca[JM], *cb;
 #pragma unroll
         for (int j = 0; j < JM; ++j) ca[j] = reinterpret_cast<const char *>(pa[j]);
@@ -620,11 +644,19 @@ __global__ __launch_bounds__(64, OCC) void rollout_kernel(RoP<T> p)
 #pragma unroll
             for (int j = 0; j < JM; ++j) ra[d][j] = ISLS_RO_LD(ca[j]);
             rb[d] = ISLS_RO_LD(cb);
+            if constexpr (NTAB > 0) {
+#pragma unroll
+                for (int j = 0; j < TL; ++j) rt[d][j] = *reinterpret_cast<const T *>(pt[j]);
+            }
             const int64_t adv = tf < N - 1 ? 1 : 0;
             tf += (int)adv;
 #pragma unroll
             for (int j = 0; j < JM; ++j) ca[j] += adv * stp[j];
             cb += adv * stpb;
+            if constexpr (NTAB > 0) {
+#pragma unroll
+                for (int j = 0; j < TL; ++j) pt[j] += adv * stpt;
+            }
             __builtin_amdgcn_sched_barrier(0);                  // keep the issue order = consumption order (vmcnt is in-order)
         }
         T *ckc = ck + (c < L ? c : L) * NSEG * NX;             // this candidate's checkpoints (row L = dump)
@@ -645,20 +677,33 @@ __global__ __launch_bounds__(64, OCC) void rollout_kernel(RoP<T> p)
             T *wj = rec + dst[j];                                                                                           \
             _Pragma("unroll") for (int h = 0; h < W; ++h) wj[h] = ra[d][j].v[h];                                            \
         }                                                                                                                   \
+        if constexpr (NTAB > 0) {                             /* the table row of step t into its side record */            \
+            _Pragma("unroll") for (int j = 0; j < TL; ++j)                                                                  \
+                if (c < GL && c + GL * j < NTAB) tabrec[d * TABP + c + GL * j] = rt[d][j];                                  \
+        }                                                                                                                   \
         slot_sync();                                          /* record(t) visible to the slot */                           \
         if (!TAILF || t + D < N) {                            /* refill this ring entry with step t + D (the tail skips */  \
             _Pragma("unroll") for (int j = 0; j < JM; ++j)    /* fetches nobody consumes: the wave would wait for them)  */  \
                 ra[d][j] = ISLS_RO_LD(ca[j]);                                                                               \
             rb[d] = ISLS_RO_LD(cb);                                                                                         \
+            if constexpr (NTAB > 0) {                                                                                       \
+                _Pragma("unroll") for (int j = 0; j < TL; ++j) rt[d][j] = *reinterpret_cast<const T *>(pt[j]);              \
+            }                                                                                                               \
             if (TAILF) {                                                                                                    \
                 const int64_t adv = tf < N - 1 ? 1 : 0;                                                                     \
                 tf += (int)adv;                                                                                             \
                 _Pragma("unroll") for (int j = 0; j < JM; ++j) ca[j] += adv * stp[j];                                       \
                 cb += adv * stpb;                                                                                           \
+                if constexpr (NTAB > 0) {                                                                                   \
+                    _Pragma("unroll") for (int j = 0; j < TL; ++j) pt[j] += adv * stpt;                                     \
+                }                                                                                                           \
             } else {                                                                                                        \
                 ++tf;                                                                                                       \
                 _Pragma("unroll") for (int j = 0; j < JM; ++j) ca[j] += stp[j];                                             \
                 cb += stpb;                                                                                                 \
+                if constexpr (NTAB > 0) {                                                                                   \
+                    _Pragma("unroll") for (int j = 0; j < TL; ++j) pt[j] += stpt;                                           \
+                }                                                                                                           \
             }                                                                                                               \
         }                                                                                                                   \
         if (t == next_ck && live) {                           /* uniform: state of every candidate at a segment start */    \
@@ -689,7 +734,7 @@ __global__ __launch_bounds__(64, OCC) void rollout_kernel(RoP<T> p)
         T cst1 = cst, cu1 = cu, ag1 = ag;                                                                                   \
         bool nz = UC ? false : (use_mask ? t == next_q : live); /* (x-z)'Q(x-z), skipped where Q_t == 0 (uniform test) */   \
         if (!UC && use_mask && nz) next_q = ro_next_bit(qm0, qm1, qm2, qm3, t + 1);                                         \
-        if constexpr (UC) cst1 += ucost.stage(x, u, t, N);    /* a user cost: the one term, cu stays 0 */                   \
+        if constexpr (UC) cst1 += ucost.stage(x, u, tabrec + d * TABP, t, N); /* a user cost: the one term, cu stays 0 */   \
         if (kHasPH && phuber) {                               /* sum_i cu_i u_i^2 + cx_i ph(x_i,px_i) (+ final term) */     \
             nz = false;                                                                                                     \
             _Pragma("unroll") for (int j = 0; j < NX; ++j)                                                                  \
@@ -1011,11 +1056,12 @@ __host__ __device__ constexpr int ro_pick_jm(int occ, int jm)
 // Launch plan of one (n, m) rollout: geometry of the winner replay, LDS budget, load-slot count, occupancy.  It depends on the
 // model only through its LDS words (MDLW), so a user model (no LDS words) gets the plan of the nonlinear built-ins of its
 // dimensions, decision for decision.  Fills p (tpw, seg_lanes, seg_len, nseg, stage_on, u_off; fa_on off when the stage does
-// not fit) and `out`.
-template <typename T, int NX, int NU, int MDLW>
-int plan_rollout(RoP<T> &p, const isls_rollout_args &a, bool want_fused, bool *stage_ok, RoLaunch &out)
+// not fit) and `out`.  A user cost's table enters the same way: its two side records lie behind the model's words.
+template <typename T, int NX, int NU, int MDLW0>
+int plan_rollout(RoP<T> &p, const isls_rollout_args &a, bool want_fused, bool *stage_ok, RoLaunch &out, int ntab = 0)
 {
     using LY = RoLayout<NX, NU>;
+    const int MDLW = ro_mdl_words(MDLW0, ntab);                // ntab: the words per step of a user cost's table (its side records)
     const int GL = a.L > 8 ? a.L : 8;
     int TPW = kWave / GL;
     // two waves per SIMD where a batch of 4096 launches more waves than SIMDs (slots of >= 16 lanes), the whole register
@@ -1187,6 +1233,8 @@ struct UserExpP {
     View<T> Qr, Rr;
     T *Cxx, *Cuu, *Cux, *c0x, *c0u;   // Cxx, Cuu, Cux nullable
     const int32_t *active;
+    const T *tab;                  // the cost's table: step t of trajectory b at tab + b * tab_sb + t * NTAB (a cost without one: unused)
+    int64_t tab_sb;
 };
 
 #ifndef __HIPCC_RTC__

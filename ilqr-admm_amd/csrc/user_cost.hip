@@ -19,19 +19,20 @@ int prepare(int id, int n, int m, hipStream_t s, const std::vector<hipFunction_t
 }  // namespace
 
 template <typename T>
-static int user_cost_value(int32_t id, int32_t R, int32_t N, const void *par, int64_t par_sb, const void *x, const void *u, void *cost,
-                           const int32_t *active, hipStream_t s)
+static int user_cost_value(int32_t id, int32_t R, int32_t N, const void *par, int64_t par_sb, const void *tab, int64_t tab_sb,
+                           const void *x, const void *u, void *cost, const int32_t *active, hipStream_t s)
 {
     if (R < 0 || N < 1 || !par || !cost || par_sb < 0) return ISLS_ERR_ARG;
     int n, m;
     int rc = urtc::dims(urtc::KIND_COST, id, &n, &m);
+    if (rc == ISLS_OK) rc = urtc::check_table(id, N, tab, tab_sb, -1);   // (a cost with a table through the entry without one: NULL)
     if (rc != ISLS_OK || R == 0) return rc;
     const std::vector<hipFunction_t> *fns;
     if ((rc = prepare<T>(id, n, m, s, &fns)) != ISLS_OK) return rc;
     int R_ = R, N_ = N;
-    const T *par_ = (const T *)par, *x_ = (const T *)x, *u_ = (const T *)u;
+    const T *par_ = (const T *)par, *x_ = (const T *)x, *u_ = (const T *)u, *tab_ = (const T *)tab;
     T *cost_ = (T *)cost;
-    void *args[] = {&R_, &N_, &par_, &par_sb, &x_, &u_, &cost_, &active};
+    void *args[] = {&R_, &N_, &par_, &par_sb, &x_, &u_, &cost_, &active, &tab_, &tab_sb};
     return urtc::launch((*fns)[FN_VAL], (R + 63) / 64, 0, s, args);
 }
 
@@ -41,9 +42,10 @@ int launch_expand_user_cost(const isls_expand_args &a, void *Cux, hipStream_t s)
 {
     if (a.B < 0 || a.N < 1 || !a.c0x || !a.c0u || !a.cost_par || a.cost_par_sb < 0) return ISLS_ERR_ARG;
     if (a.B == 0) return ISLS_OK;
-    const std::vector<hipFunction_t> *fns;
-    int rc = prepare<T>(a.cost_model, a.n, a.m, s, &fns);
+    int rc = urtc::check_table(a.cost_model, a.N, a.ztab, a.ztab_sb, a.nvia);   // the table: ztab, ztab_sb, nvia (isls_hip.h)
     if (rc != ISLS_OK) return rc;
+    const std::vector<hipFunction_t> *fns;
+    if ((rc = prepare<T>(a.cost_model, a.n, a.m, s, &fns)) != ISLS_OK) return rc;
     const int K = a.n + a.m, NP = K * (K + 1) / 2, steps = NP <= kWave ? kWave / NP : 4;   // user_expand_kernel's S
     UserExpP<T> p;
     p.B = a.B; p.N = a.N; p.nbt = (a.N + steps - 1) / steps;
@@ -52,11 +54,12 @@ int launch_expand_user_cost(const isls_expand_args &a, void *Cux, hipStream_t s)
     p.Qr = View<T>(a.Qr); p.Rr = View<T>(a.Rr);
     p.Cxx = (T *)a.Cxx; p.Cuu = (T *)a.Cuu; p.Cux = (T *)Cux; p.c0x = (T *)a.c0x; p.c0u = (T *)a.c0u;
     p.active = a.active;
+    p.tab = (const T *)a.ztab; p.tab_sb = a.ztab_sb;          // read by a cost with a table only
     const int64_t grid = (int64_t)a.B * p.nbt;
     if (grid > 0x7fffffff) return ISLS_ERR_UNSUPPORTED;
     void *args[] = {&p};
     if ((rc = urtc::launch((*fns)[FN_EXP], (int)grid, 0, s, args)) != ISLS_OK || !a.cost) return rc;
-    return user_cost_value<T>(a.cost_model, a.B, a.N, a.cost_par, a.cost_par_sb, a.xhat, a.uhat, a.cost, a.active, s);
+    return user_cost_value<T>(a.cost_model, a.B, a.N, a.cost_par, a.cost_par_sb, a.ztab, a.ztab_sb, a.xhat, a.uhat, a.cost, a.active, s);
 }
 template int launch_expand_user_cost<double>(const isls_expand_args &, void *, hipStream_t);
 template int launch_expand_user_cost<float>(const isls_expand_args &, void *, hipStream_t);
@@ -69,8 +72,15 @@ using namespace isls;
 
 ISLS_API int isls_user_cost_create(const char *source, int32_t n, int32_t m, int32_t n_par, int32_t *id)
 {
-    return urtc::create(urtc::KIND_COST, source, n, m, n_par, id);
+    return urtc::create(urtc::KIND_COST, source, n, m, n_par, 0, id);
 }
+
+ISLS_API int isls_user_cost_create_tab(const char *source, int32_t n, int32_t m, int32_t n_par, int32_t n_tab, int32_t *id)
+{
+    return urtc::create(urtc::KIND_COST, source, n, m, n_par, n_tab, id);
+}
+
+ISLS_API int isls_user_cost_n_tab(int32_t id) { return urtc::n_tab(id); }
 
 ISLS_API int64_t isls_user_cost_log(int32_t id, char *buf, int64_t len) { return urtc::copy_log(urtc::KIND_COST, id, buf, len); }
 
@@ -88,12 +98,22 @@ ISLS_API int isls_user_cost_load(int32_t id, int32_t model, int32_t dtype)
 ISLS_API int isls_user_cost_value_f64(int32_t id, int32_t R, int32_t N, const void *par, int64_t par_sb, const void *x, const void *u,
                                       void *cost, void *stream)
 {
-    return user_cost_value<double>(id, R, N, par, par_sb, x, u, cost, nullptr, (hipStream_t)stream);
+    return user_cost_value<double>(id, R, N, par, par_sb, nullptr, 0, x, u, cost, nullptr, (hipStream_t)stream);
 }
 ISLS_API int isls_user_cost_value_f32(int32_t id, int32_t R, int32_t N, const void *par, int64_t par_sb, const void *x, const void *u,
                                       void *cost, void *stream)
 {
-    return user_cost_value<float>(id, R, N, par, par_sb, x, u, cost, nullptr, (hipStream_t)stream);
+    return user_cost_value<float>(id, R, N, par, par_sb, nullptr, 0, x, u, cost, nullptr, (hipStream_t)stream);
+}
+ISLS_API int isls_user_cost_value_tab_f64(int32_t id, int32_t R, int32_t N, const void *par, int64_t par_sb, const void *tab, int64_t tab_sb,
+                                          const void *x, const void *u, void *cost, void *stream)
+{
+    return user_cost_value<double>(id, R, N, par, par_sb, tab, tab_sb, x, u, cost, nullptr, (hipStream_t)stream);
+}
+ISLS_API int isls_user_cost_value_tab_f32(int32_t id, int32_t R, int32_t N, const void *par, int64_t par_sb, const void *tab, int64_t tab_sb,
+                                          const void *x, const void *u, void *cost, void *stream)
+{
+    return user_cost_value<float>(id, R, N, par, par_sb, tab, tab_sb, x, u, cost, nullptr, (hipStream_t)stream);
 }
 
 ISLS_API int isls_user_cost_expand_f64(const isls_expand_args *a, void *Cux, void *stream)

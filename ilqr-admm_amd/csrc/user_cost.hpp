@@ -4,14 +4,21 @@
 //     [namespace isls_user { <a user model's step<S, P>> }   #define ISLS_USER_NPAR <P>]      -- with a models.Custom
 //     namespace isls_user_cost { <the user's stage<S, P>> }
 //     #define ISLS_USER_COST_NPAR <P>
+//     [#define ISLS_USER_COST_NTAB <W>]                                                       -- a cost with a per-step table
 //     #include "user_cost.hpp"
 // and its name expressions instantiate, for one (cost, model, dtype): every (JM, OCC) variant of rollout_kernel that the launch
 // plan of a built-in model of the same dimensions can pick -- the built-ins' template as it is, with RoCost<..., true> below as
 // its stage cost --, user_expand_kernel and user_cost_value_kernel.
+// With ISLS_USER_COST_NTAB the user's stage takes the W words of step t as `const P *row` behind `par` (plain P: nothing is
+// differentiated with respect to them); a source of the other form than its registration says does not compile.
 #pragma once
 
 #ifndef ISLS_USER_COST_NPAR
 #error "ISLS_USER_COST_NPAR: the parameter count of the user cost"
+#endif
+
+#ifndef ISLS_USER_COST_NTAB
+#define ISLS_USER_COST_NTAB 0
 #endif
 
 #ifdef ISLS_USER_NPAR
@@ -32,14 +39,27 @@ __device__ __forceinline__ void user_cost_par(const T *p, T (&par)[kUserCostParW
     for (int i = 0; i < kUserCostParWords; ++i) par[i] = i < ISLS_USER_COST_NPAR ? p[i] : T(0);
 }
 
-// the stage cost of the line search: parameters in registers (no LDS words, so the launch plan is the built-ins')
+// the user's stage in the form its registration names: with the row of step t, or without
+template <typename S, typename T>
+__device__ __forceinline__ S user_stage(const S *x, const S *u, const T *par, const T *row, int t, int N)
+{
+#if ISLS_USER_COST_NTAB > 0
+    return ::isls_user_cost::stage<S, T>(x, u, par, row, t, N);
+#else
+    return ::isls_user_cost::stage<S, T>(x, u, par, t, N);
+#endif
+}
+
+// the stage cost of the line search: parameters in registers (no LDS words, so the launch plan is the built-ins'); the row of a
+// table cost comes from the step's side record in LDS (rollout_kernel.hpp)
 template <typename T, int NX, int NU>
 struct RoCost<T, NX, NU, true> {
+    static constexpr int NTAB = ISLS_USER_COST_NTAB;
     T par[kUserCostParWords];
     __device__ __forceinline__ void load(const T *p) { user_cost_par(p, par); }
-    __device__ __forceinline__ T stage(const T (&x)[NX], const T (&u)[NU], int t, int N) const
+    __device__ __forceinline__ T stage(const T (&x)[NX], const T (&u)[NU], const T *row, int t, int N) const
     {
-        return ::isls_user_cost::stage<T, T>(x, u, par, t, N);
+        return user_stage<T, T>(x, u, par, row, t, N);
     }
 };
 
@@ -63,6 +83,7 @@ __global__ __launch_bounds__(64) void user_expand_kernel(UserExpP<T> p)
     const int64_t bN = (int64_t)b * N;
     T par[kUserCostParWords];
     user_cost_par(p.par + (int64_t)b * p.par_sb, par);
+    const T *const tab = ISLS_USER_COST_NTAB > 0 ? p.tab + (int64_t)b * p.tab_sb : nullptr;   // row t: a plain global read
     using D = ad::Dual2<T>;
 #pragma unroll 1
     for (int w = threadIdx.x; w < S * NP; w += kWave) {
@@ -79,7 +100,7 @@ __global__ __launch_bounds__(64) void user_expand_kernel(UserExpP<T> p)
 #pragma unroll
         for (int e = 0; e < NU; ++e)
             u[e] = D(p.uhat ? p.uhat[(bN + t) * NU + e] : T(0), NX + e == i ? T(1) : T(0), NX + e == j ? T(1) : T(0), T(0));
-        const D c = ::isls_user_cost::stage<D, T>(x, u, par, t, N);
+        const D c = user_stage<D, T>(x, u, par, tab + (int64_t)t * ISLS_USER_COST_NTAB, t, N);
         if (i == j) tg[ts * K + i] = c.a;
         if (j < NX) {                                          // i <= j < NX
             const T *Q = p.Qr.p ? p.Qr.at(b, t) : nullptr;
@@ -116,15 +137,17 @@ __global__ __launch_bounds__(64) void user_expand_kernel(UserExpP<T> p)
 }
 
 // cost[r] = sum_t stage(x[r,t], u[r,t], par, t, N) for R trajectories, one lane each, summed in the order of the line search
-// (isls_user_cost_value_*, and the nominal cost of an expansion); par [P] shared (par_sb = 0) or one row per trajectory
+// (isls_user_cost_value_*, and the nominal cost of an expansion); par [P] shared (par_sb = 0) or one row per trajectory; tab: the
+// table of a cost that has one, [N][NTAB] shared (tab_sb = 0) or per trajectory
 template <typename T, int NX, int NU>
 __global__ __launch_bounds__(64) void user_cost_value_kernel(int R, int N, const T *par, int64_t par_sb, const T *x, const T *u, T *cost,
-                                                             const int32_t *active)
+                                                             const int32_t *active, const T *tab, int64_t tab_sb)
 {
     const int r = blockIdx.x * kWave + threadIdx.x;
     if (r >= R || (active && active[r] == 0)) return;
     RoCost<T, NX, NU, true> c;
     c.load(par + (int64_t)r * par_sb);
+    const T *const trow = ISLS_USER_COST_NTAB > 0 ? tab + (int64_t)r * tab_sb : nullptr;
     T sum = T(0);
     for (int t = 0; t < N; ++t) {
         T xr[NX], ur[NU];
@@ -132,7 +155,7 @@ __global__ __launch_bounds__(64) void user_cost_value_kernel(int R, int N, const
         for (int i = 0; i < NX; ++i) xr[i] = x ? x[((int64_t)r * N + t) * NX + i] : T(0);
 #pragma unroll
         for (int i = 0; i < NU; ++i) ur[i] = u ? u[((int64_t)r * N + t) * NU + i] : T(0);
-        sum += c.stage(xr, ur, t, N);
+        sum += c.stage(xr, ur, trow + (int64_t)t * ISLS_USER_COST_NTAB, t, N);
     }
     cost[r] = sum;
 }

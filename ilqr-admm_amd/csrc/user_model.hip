@@ -93,7 +93,7 @@ using namespace isls;
 
 ISLS_API int isls_user_model_create(const char *source, int32_t n, int32_t m, int32_t n_par, int32_t *id)
 {
-    return urtc::create(urtc::KIND_MODEL, source, n, m, n_par, id);
+    return urtc::create(urtc::KIND_MODEL, source, n, m, n_par, 0, id);
 }
 
 ISLS_API int64_t isls_user_model_log(int32_t id, char *buf, int64_t len) { return urtc::copy_log(urtc::KIND_MODEL, id, buf, len); }

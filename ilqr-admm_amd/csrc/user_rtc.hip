@@ -207,7 +207,7 @@ int load_program(Program &pg, const std::vector<hipFunction_t> **out, hipStream_
 // ---- the registry and the program cache (both under g_mu) --------------------------------------------------------------------
 struct Source {
     std::string source;
-    int n, m, npar;
+    int n, m, npar, ntab;                                    // ntab: words per step of a cost's table (0: none)
     std::string log;
 };
 
@@ -270,6 +270,7 @@ int program(int model, int cost, int dtype, Program **out)
                     "isls::mc_closed_loop_kernel<" + T + ", " + dims + ", " + tmodel + ">"};
     pg.ro0 = (int)pg.names.size();
     pg.mdlw = mdlw;
+    pg.ntab = uc ? uc->ntab : 0;
     pg.ro.clear();
     if (model != kNone) {
 #define ISLS_URTC_VARIANTS_(NX_, NU_) if (n == NX_ && m == NU_) ro_variants<NX_, NU_>(pg.ro);
@@ -282,6 +283,7 @@ int program(int model, int cost, int dtype, Program **out)
     std::string src = uc ? "#include \"user_cost_ad.hpp\"\n" : "#include \"user_model_ad.hpp\"\n";
     if (um) src += wrap_source("isls_user", "user_model", um->source) + "#define ISLS_USER_NPAR " + std::to_string(um->npar) + "\n";
     if (uc) src += wrap_source("isls_user_cost", "user_cost", uc->source) + "#define ISLS_USER_COST_NPAR " + std::to_string(uc->npar) + "\n";
+    if (uc && uc->ntab > 0) src += "#define ISLS_USER_COST_NTAB " + std::to_string(uc->ntab) + "\n";
     src += uc ? "#include \"user_cost.hpp\"\n" : "#include \"user_model.hpp\"\n";
     return compile_program(src, uc ? "user_cost.hip" : "user_model.hip", pg, (uc ? uc : um)->log);
 }
@@ -291,12 +293,13 @@ bool dtype_ok(int dtype) { return dtype == ISLS_DTYPE_F64 || dtype == ISLS_DTYPE
 }  // namespace
 
 // ---- what user_model.hip and user_cost.hip build their entry points and launches from ------------------------------------------
-int create(Kind kind, const char *source, int n, int m, int n_par, int32_t *id)
+int create(Kind kind, const char *source, int n, int m, int n_par, int n_tab, int32_t *id)
 {
     if (!source || !id) return ISLS_ERR_ARG;
     if (!dims_supported(n, m) || n_par < 0 || n_par > ISLS_USER_MAX_PAR) return ISLS_ERR_UNSUPPORTED;
+    if (n_tab < 0 || n_tab > ISLS_USER_MAX_TAB || (kind == KIND_MODEL && n_tab != 0)) return ISLS_ERR_UNSUPPORTED;
     auto src = std::make_unique<Source>();
-    src->source = source; src->n = n; src->m = m; src->npar = n_par;
+    src->source = source; src->n = n; src->m = m; src->npar = n_par; src->ntab = n_tab;
     if (refused_source(src->source)) return ISLS_ERR_ARG;     // plain arithmetic: no hand-written ISA through this door
     std::lock_guard<std::mutex> lk(g_mu);
     *id = (kind == KIND_MODEL ? ISLS_MODEL_USER_BASE : ISLS_COST_USER_BASE) + (int32_t)g_src[kind].size();
@@ -352,6 +355,21 @@ int dims(Kind kind, int id, int *n, int *m)
     return ISLS_OK;
 }
 
+int n_tab(int cost)
+{
+    std::lock_guard<std::mutex> lk(g_mu);
+    const Source *src = find(KIND_COST, cost);
+    return src ? src->ntab : ISLS_ERR_ARG;
+}
+
+int check_table(int cost, int N, const void *tab, int64_t tab_sb, int nvia)
+{
+    const int W = n_tab(cost);
+    if (W <= 0) return W < 0 ? ISLS_ERR_ARG : ISLS_OK;
+    const bool ok = tab != nullptr && (tab_sb == 0 || tab_sb == (int64_t)N * W) && (nvia < 0 || nvia == W);
+    return ok ? ISLS_OK : ISLS_ERR_ARG;
+}
+
 int prepare(int model, int cost, int dtype, int n, int m, hipStream_t s, const std::vector<hipFunction_t> **fns, const Program **out)
 {
     std::lock_guard<std::mutex> lk(g_mu);
@@ -390,16 +408,19 @@ int launch_rollout_user(RoP<T> &p, const isls_rollout_args &a, hipStream_t s, bo
     if (ucost && (!a.cost_par || a.cost_par_sb < 0)) return ISLS_ERR_ARG;
     const urtc::Program *pg;
     const std::vector<hipFunction_t> *fns;
-    int rc = urtc::prepare(a.model, ucost ? a.cost_model : urtc::kNone, urtc::dtype_of<T>(), a.n, a.m, s, &fns, &pg);
+    int rc = ucost ? urtc::check_table(a.cost_model, a.N, a.ztab, a.ztab_sb, a.nvia) : ISLS_OK;   // the table: ztab, ztab_sb, nvia
+    if (rc != ISLS_OK) return rc;
+    rc = urtc::prepare(a.model, ucost ? a.cost_model : urtc::kNone, urtc::dtype_of<T>(), a.n, a.m, s, &fns, &pg);
     if (rc != ISLS_OK) return rc;
     if (ucost) p.cpar_sb = a.cost_par_sb;
     RoLaunch pl;
     rc = ISLS_ERR_UNSUPPORTED;
-    // the model enters the plan through its LDS words only (a dense LTI model's [A B]; none for the others and for user models)
+    // the model enters the plan through its LDS words only (a dense LTI model's [A B]; none for the others and for user models),
+    // a cost's table through the side records of its row behind them
 #define ISLS_URTC_PLAN_(NX_, NU_)                                                                              \
     if (a.n == NX_ && a.m == NU_)                                                                              \
-        rc = pg->mdlw ? plan_rollout<T, NX_, NU_, NX_ * (NX_ + NU_)>(p, a, want_fused, nullptr, pl)            \
-                      : plan_rollout<T, NX_, NU_, 0>(p, a, want_fused, nullptr, pl);
+        rc = pg->mdlw ? plan_rollout<T, NX_, NU_, NX_ * (NX_ + NU_)>(p, a, want_fused, nullptr, pl, pg->ntab)  \
+                      : plan_rollout<T, NX_, NU_, 0>(p, a, want_fused, nullptr, pl, pg->ntab);
     ISLS_FOR_EACH_DIMS(ISLS_URTC_PLAN_)
 #undef ISLS_URTC_PLAN_
     if (rc != ISLS_OK) return rc;

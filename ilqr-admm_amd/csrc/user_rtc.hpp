@@ -23,19 +23,25 @@ struct Program {                                             // one key: a model
     std::vector<char> code;
     std::vector<std::string> names, lowered;                 // name expressions and their mangled names
     int ro0 = 0, mdlw = 0;                                   // index of the first rollout variant; LDS words of the model (plan_rollout)
+    int ntab = 0;                                            // words per step of the cost's table (its side records enter the plan too)
     std::vector<std::pair<int, int>> ro;                     // (JM, OCC) of the rollout variants: names[ro0 + i]
     std::map<int, std::pair<hipModule_t, std::vector<hipFunction_t>>> dev;   // device -> module, functions
 };
 
 // isls_user_{model,cost}_create: register `source` (an id is assigned even when the compile fails) and compile its own program
-// (the model's, or the cost's expansion and value) for fp64
-int create(Kind kind, const char *source, int n, int m, int n_par, int32_t *id);
+// (the model's, or the cost's expansion and value) for fp64; n_tab: words per step of a cost's table (0: none, and for a model)
+int create(Kind kind, const char *source, int n, int m, int n_par, int n_tab, int32_t *id);
 // isls_user_*_log / _code / _load: the compiler's messages for a source so far; the code object of a key, compiled on first use;
 // the same loaded onto the current device
 int64_t copy_log(Kind kind, int id, char *buf, int64_t len);
 int copy_code(int model, int cost, int dtype, void *buf, int64_t *len);
 int load(int model, int cost, int dtype);
 int dims(Kind kind, int id, int *n, int *m);                 // ISLS_ERR_ARG: no such id
+int n_tab(int cost);                                         // words per step of the cost's table (0: none); ISLS_ERR_ARG: no such id
+// A launch's table fields against the cost's registration, before anything is compiled, loaded or launched (no GPU needed): a
+// cost with a table of W words needs tab != NULL, tab_sb == 0 or N * W, and nvia == W (nvia < 0: not given); the fields of a cost
+// without a table are ignored.  ISLS_ERR_ARG otherwise, and for an id nobody registered.
+int check_table(int cost, int N, const void *tab, int64_t tab_sb, int nvia);
 // The functions (index: pg.names) of the key's program for a launch of dims (n, m) on the current device: compiled and loaded on
 // first use -- never inside a capture of stream `s`.  (kNone, cost) asks for the expansion and the value, which every program
 // of the cost holds: one that is on this device already serves, the cost's own program is compiled only when there is none.

@@ -24,6 +24,7 @@ REG_AFTER_GAIN, REG_AFTER_LS = 0, 1             # isls_reg_update_args.mode
 SOLVE_CHOL, SOLVE_INV = 0, 1
 MODEL_LTI, MODEL_ARM3R, MODEL_CAR, MODEL_DI, MODEL_TASSA = 0, 1, 2, 3, 4
 MODEL_USER_BASE, USER_MAX_PAR = 1024, 16      # ids of user models (isls_user_model_create), parameters per model at most
+USER_MAX_TAB = 16                              # words per step of a user cost's table (isls_user_cost_create_tab), at most
 DTYPE_F64, DTYPE_F32 = 0, 1
 COST_VIA, COST_PHUBER = 0, 1
 COST_USER_BASE = 1024                          # ids of user costs (isls_user_cost_create)
@@ -242,12 +243,13 @@ class AdvanceArgs(C.Structure):
 EXPORTED = [f"isls_{k}_{s}" for s in ("f64", "f32") for k in
             ("riccati_gain", "riccati_ff", "riccati_gain_ff", "riccati_ff_prepare", "rollout_ls", "admm_update", "project_rows", "sls_admm", "sls_closed_loop", "columns_rollout", "columns_admm", "dense_closed_loop", "mc_closed_loop", "cov_closed_loop", "sls_controller", "expand_quadratic", "linearize",
              "accept_step", "reduce_convergence", "reduce_convergence_table", "ilqr_admm_outer", "outer_advance", "columns_iteration",
-             "user_model_step", "user_cost_value", "user_cost_expand", "riccati_gain_reg", "reg_update")] + \
+             "user_model_step", "user_cost_value", "user_cost_value_tab", "user_cost_expand", "riccati_gain_reg", "reg_update")] + \
            ["isls_ff_segments", "isls_ff_record_elems", "isls_sls_controller_work_elems", "isls_mc_work_elems", "isls_version", "isls_dims_supported", "isls_dims_generic", "isls_error_string", "isls_timing_create",
             "isls_timing_destroy", "isls_timing_reset", "isls_timing_pause", "isls_timing_read_ms",
             "isls_gain_memo_stats", "isls_gain_memo_clear",
             "isls_user_model_create", "isls_user_model_log", "isls_user_model_code", "isls_user_model_load",
-            "isls_user_cost_create", "isls_user_cost_log", "isls_user_cost_code", "isls_user_cost_load"]
+            "isls_user_cost_create", "isls_user_cost_log", "isls_user_cost_code", "isls_user_cost_load",
+            "isls_user_cost_create_tab", "isls_user_cost_n_tab"]
 
 
 SET_BOX, SET_SOC_UNIT, SET_SQUARE, SET_LINEAR, SET_QUADRATIC, SET_SHELL, SET_MULTILINEAR = 1, 2, 3, 4, 5, 6, 7
@@ -295,6 +297,8 @@ def load_hip_library(path=None):
     lib.isls_user_model_code.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int64)]
     lib.isls_user_model_load.argtypes = [C.c_int32, C.c_int32]
     lib.isls_user_cost_create.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
+    lib.isls_user_cost_create_tab.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
+    lib.isls_user_cost_n_tab.argtypes = [C.c_int32]
     lib.isls_user_cost_log.restype = C.c_int64
     lib.isls_user_cost_log.argtypes = [C.c_int32, C.c_char_p, C.c_int64]
     lib.isls_user_cost_code.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int64)]
@@ -372,12 +376,13 @@ class _UserKind:
         self._fn("log")(C.c_int32(uid), buf, len(buf))
         return buf.value.decode(errors="replace")
 
-    def create(self, source, n, m, n_par):
-        key = (str(source), int(n), int(m), int(n_par))
+    def create(self, source, n, m, n_par, n_tab=0):
+        """n_tab > 0 (costs only): a cost with a per-step table of that many words; the key of one without is what it was"""
+        key = (str(source), int(n), int(m), int(n_par)) + ((int(n_tab),) if n_tab else ())
         if key in self.ids:
             return self.ids[key]
         uid = C.c_int32(-1)
-        rc = self._fn("create")(key[0].encode(), key[1], key[2], key[3], C.byref(uid))
+        rc = self._fn("create_tab" if n_tab else "create")(key[0].encode(), *key[1:], C.byref(uid))
         if rc == ERR_COMPILE:
             raise IslsError(f"user {self.noun}: compile failed\n{self.log(uid.value) if uid.value >= self.base else ''}")
         if rc != OK:
@@ -421,10 +426,19 @@ def user_model_load(model_id, dtype=np.float64):
     _USER_MODEL.load(model_id, dtype=dtype)
 
 
-def user_cost_create(source, n, m, n_par):
+def user_cost_create(source, n, m, n_par, n_tab=0):
     """Register a user cost and compile its expansion and value for gfx950 (fp64; the line-search kernels are compiled per model
-    it is used with); the same (source, n, m, n_par) is registered once per process.  IslsError carries the compile log."""
-    return _USER_COST.create(source, n, m, n_par)
+    it is used with); the same (source, n, m, n_par, n_tab) is registered once per process.  n_tab > 0: the cost reads a table
+    of that many words per step (isls_user_cost_create_tab; the six-argument `stage`).  IslsError carries the compile log."""
+    return _USER_COST.create(source, n, m, n_par, n_tab)
+
+
+def user_cost_n_tab(cost_id):
+    """Words per step of the cost's table (0: a cost without one)."""
+    rc = library().isls_user_cost_n_tab(C.c_int32(cost_id))
+    if rc < 0:
+        raise IslsError(f"isls_user_cost_n_tab -> {rc}: {library().isls_error_string(rc).decode()}")
+    return rc
 
 
 def user_cost_code(cost_id, model=-1, dtype=np.float64):
@@ -444,6 +458,20 @@ def _cost_par(cost_model, cost_par, B):
             raise ValueError("a user cost needs its parameters (cost_par)")
         return _par(cost_par, B, "cost_par")
     return _ptr(cost_par), 0
+
+
+def _cost_tab(a, cost_model, cost_tab):
+    """A user cost's table [N, W] or [B, N, W] into the fields such a cost ignores otherwise (include/isls_hip.h): ztab, ztab_sb
+    (0 or N W), nvia = W"""
+    if cost_tab is None:
+        return
+    if int(cost_model) < COST_USER_BASE:
+        raise ValueError("cost_tab: the per-step table of a user cost")
+    if cost_tab.ndim not in (2, 3):
+        raise ValueError(f"cost_tab: [N, W] or [B, N, W], got shape {tuple(cost_tab.shape)}")
+    W = int(cost_tab.shape[-1])
+    a.ztab, a.ztab_sb = _tab(cost_tab, a.B, (a.N, W), "cost_tab")
+    a.nvia = W
 
 
 # ------------------------------------------------------------------------------------------------
@@ -676,7 +704,7 @@ class Kernels:
     def rollout_args(model, model_par, K, k, xhat, uhat, alphas, Qtab, ztab, seq, u_std, x_out, u_out,
                      best=None, cost_new=None, cost_all=None, x0=None, wq=None, wr=None, zx=None, lx=None,
                      zu=None, lu=None, cost_cur=None, flags=0, status=None, active=None, q_nonzero=None,
-                     cost_model=COST_VIA, cost_par=None):
+                     cost_model=COST_VIA, cost_par=None, cost_tab=None):
         B, N, m, n = K.shape
         L = int(alphas.shape[0])
         nvia = int(Qtab.shape[-3])
@@ -710,6 +738,7 @@ class Kernels:
         a.status, a.active = _ptr(status), _ptr(active)
         a.cost_model = int(cost_model)
         a.cost_par, a.cost_par_sb = _cost_par(cost_model, cost_par, B)
+        _cost_tab(a, cost_model, cost_tab)
         return a
 
     @staticmethod
@@ -980,7 +1009,8 @@ class Kernels:
 
     @staticmethod
     def expand_args(Qtab, ztab, seq, u_std, c0x, c0u, xhat=None, uhat=None, Cxx=None, Cuu=None,
-                    Qr=None, Rr=None, cost=None, active=None, cost_model=COST_VIA, cost_par=None, q_nonzero=None):
+                    Qr=None, Rr=None, cost=None, active=None, cost_model=COST_VIA, cost_par=None, q_nonzero=None,
+                    cost_tab=None):
         B, N, n = c0x.shape
         m = c0u.shape[2]
         nvia = int(Qtab.shape[-3])
@@ -995,6 +1025,7 @@ class Kernels:
         a.cost, a.active = _ptr(_dense(cost, (B,), "cost")), _ptr(active)
         a.cost_model, a.q_nonzero = int(cost_model), _ptr(q_nonzero)
         a.cost_par, a.cost_par_sb = _cost_par(cost_model, cost_par, B)
+        _cost_tab(a, cost_model, cost_tab)
         return a
 
     def linearize(self, *args, stream=None, **kw):
@@ -1048,11 +1079,17 @@ class Kernels:
         return self._invoke("user_model_step", _sfx(xn), C.c_int32(model_id), C.c_int32(R), C.c_void_p(ptr), C.c_int64(sb),
                             C.c_void_p(_ptr(x)), C.c_void_p(_ptr(u)), C.c_void_p(_ptr(xn)), stream=stream)
 
-    def user_cost_value(self, cost_id, par, x, u, cost, stream=None):
-        """isls_user_cost_value: cost [R] = sum_t stage(x [R,N,n], u [R,N,m]) with par [P] (shared) or [R,P]."""
+    def user_cost_value(self, cost_id, par, x, u, cost, stream=None, tab=None):
+        """isls_user_cost_value: cost [R] = sum_t stage(x [R,N,n], u [R,N,m]) with par [P] (shared) or [R,P]; a cost with a table
+        (isls_user_cost_value_tab): tab [N,W] (shared) or [R,N,W]."""
         R, N, n = x.shape
         _dense(u, (R, N, u.shape[2]), "u"), _dense(cost, (R,), "cost")
         ptr, sb = _par(par, R, "par")
+        if tab is not None:
+            tptr, tsb = _tab(tab, R, (N, int(tab.shape[-1])), "tab")
+            return self._invoke("user_cost_value_tab", _sfx(cost), C.c_int32(cost_id), C.c_int32(R), C.c_int32(N), C.c_void_p(ptr),
+                                C.c_int64(sb), C.c_void_p(tptr), C.c_int64(tsb), C.c_void_p(_ptr(x)), C.c_void_p(_ptr(u)),
+                                C.c_void_p(_ptr(cost)), stream=stream)
         return self._invoke("user_cost_value", _sfx(cost), C.c_int32(cost_id), C.c_int32(R), C.c_int32(N), C.c_void_p(ptr), C.c_int64(sb),
                             C.c_void_p(_ptr(x)), C.c_void_p(_ptr(u)), C.c_void_p(_ptr(cost)), stream=stream)
 

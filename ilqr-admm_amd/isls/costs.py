@@ -67,10 +67,34 @@ class Custom(UserSource):
     `models.Custom`: the library compiles it at run time for gfx950 (hiprtc) into the rollout kernel of that model and into an
     expansion on hyper-dual numbers -- gradient and full Hessian, x-u cross terms included, come from `stage` itself, so
     `get_Cs=None` is all `solve` / `ilqr_admm` need.  `params` is [P] (shared) or [B, P] (one row per trajectory), P <= 16.
-    Only the (x_dim, u_dim) pairs with the row-per-lane kernels are served (`isls._capi.supported_dims()`)."""
+    Only the (x_dim, u_dim) pairs with the row-per-lane kernels are served (`isls._capi.supported_dims()`).
 
-    def __init__(self, x_dim, u_dim, params, source):
-        self.cost_model = self._register("cost", capi.user_cost_create, x_dim, u_dim, params, source)
+    Per-step data (a reference to track, weights that change along the horizon, a moving obstacle): `table` is [N, W] (shared by
+    the batch) or [B, N, W] (one per trajectory), 1 <= W <= 16, and `source` then defines the six-argument form
+
+        template <typename S, typename P>
+        __device__ S stage(const S *x, const S *u, const P *par, const P *row, int t, int N);
+
+    `row` the W words of step t: plain P, never differentiated.  `set_table` replaces the values (same shape) between two calls
+    of a solver -- a receding-horizon window: no compile, and the engines holding the cost copy the new values into the device
+    table they already have."""
+
+    def __init__(self, x_dim, u_dim, params, source, table=None):
+        self.cost_model = self._register("cost", capi.user_cost_create, x_dim, u_dim, params, source, table=table)
+
+    @property
+    def table(self):
+        """The host copy of the per-step table ([N, W] or [B, N W]; None: a cost without one)."""
+        return self._table
+
+    def set_table(self, table):
+        """New values for the table, of the shape it has: the next call of a solver on any iSLS holding this cost uses them."""
+        if self._table is None:
+            raise ValueError("set_table: this cost was built without a table")
+        table = np.array(table, dtype=np.float64, order="C")
+        if table.shape != self._table.shape:
+            raise ValueError(f"set_table: the table is {self._table.shape}, got {table.shape} (a new shape is a new costs.Custom)")
+        self._table, self._table_version = table, self._table_version + 1
 
     def code(self, model=None, dtype=np.float64):
         """The gfx950 code object of the cost for dtype: with `model` (an isls.models object or a model id) every kernel of the
@@ -86,16 +110,19 @@ class Custom(UserSource):
         lead = np.broadcast_shapes(x.shape[:-2], u.shape[:-2])
         N = x.shape[-2]
         R = int(np.prod(lead)) if lead else 1
+        if self._table is not None and self._table.shape[-2] != N:
+            raise ValueError(f"the cost's table has {self._table.shape[-2]} steps, x has {N}")
         torch, kern, dev, (par, xs, us) = self._on_device(R, "{0} trajectories x, u, got {1}",
                                                            np.broadcast_to(x, lead + (N, self.x_dim)).reshape(R, N, self.x_dim),
                                                            np.broadcast_to(u, lead + (N, self.u_dim)).reshape(R, N, self.u_dim))
+        self._tab_dev = None if self._table is None else torch.as_tensor(self._table, device=dev)
         return torch, kern, lead, R, N, xs, us, par, dev
 
     def __call__(self, x, u):
         """x [..., N, n], u [..., N, m] -> cost [...] (numpy, fp64), evaluated on the device."""
         torch, kern, lead, R, N, xs, us, par, dev = self._batch(x, u)
         cost = torch.empty(R, dtype=torch.float64, device=dev)
-        kern.user_cost_value(self.cost_model, par, xs, us, cost, stream=torch.cuda.current_stream().cuda_stream)
+        kern.user_cost_value(self.cost_model, par, xs, us, cost, stream=torch.cuda.current_stream().cuda_stream, tab=self._tab_dev)
         c = cost.cpu().numpy().reshape(lead)
         return float(c) if lead == () else c
 
@@ -109,7 +136,7 @@ class Custom(UserSource):
         Cxx, Cuu, Cux, c0x, c0u = z(R, N, n, n), z(R, N, m, m), z(R, N, m, n), z(R, N, n), z(R, N, m)
         zero = z(1, n, n)
         exp = capi.Kernels.expand_args(zero, zero[0, :1], torch.zeros(N, dtype=torch.int32, device=dev), 0.0, c0x, c0u, xhat=xs, uhat=us,
-                                       Cxx=Cxx, Cuu=Cuu, cost_model=self.cost_model, cost_par=par)
+                                       Cxx=Cxx, Cuu=Cuu, cost_model=self.cost_model, cost_par=par, cost_tab=self._tab_dev)
         kern.user_cost_expand(exp, Cux, "f64", stream=torch.cuda.current_stream().cuda_stream)
         cs = torch.cat([c0x, c0u], dim=-1).cpu().numpy()
         Cs = torch.cat([torch.cat([Cxx, Cux.transpose(-1, -2)], dim=-1), torch.cat([Cux, Cuu], dim=-1)], dim=-2).cpu().numpy()

@@ -110,6 +110,7 @@ class Engine:
         self.Qtab = self.ztab = self.seq = self.q_nonzero = None
         self.u_std = 0.0
         self.cost_model, self.cost_par = capi.COST_VIA, None
+        self.cost_tab = None                                  # a user cost's per-step table [N, W] / [B, N, W] (set_cost_model)
         self.allow_shared_hessian = True                      # front ends that write Cxx / Cuu themselves switch it off
         self.Qr = self.Rr = self.wq = self.wr = self.Qr_ff = self.Qr_term = None      # ADMM weights: set_weights()
         self._w_invariant, self._w_terminal = True, False
@@ -218,14 +219,27 @@ class Engine:
         qnz = (self.Qtab.reshape(-1, self.Qtab.shape[-3], self.n * self.n) != 0).any(-1).any(0).cpu().numpy()
         self.q_nonzero = torch.as_tensor(qnz[seq].astype(np.int32), device=self.device)
         self.u_std = float(u_std)
-        self.cost_model, self.cost_par = capi.COST_VIA, None
+        self.cost_model, self.cost_par, self.cost_tab = capi.COST_VIA, None, None
         self._outer_args = None
         self._hess_dirty = True
 
-    def set_cost_model(self, cost_model, par):
+    def set_cost_model(self, cost_model, par, table=None):
         """Non-quadratic cost of the line search and of the expansion: built in (ISLS_COST_PHUBER: [cu, cx, px, cf, pf]) or a
-        user cost (costs.Custom.cost_model; par [P] shared or [B, P] per trajectory)."""
-        self.cost_model, self.cost_par = int(cost_model), self._t(np.ascontiguousarray(par))
+        user cost (costs.Custom.cost_model; par [P] shared or [B, P] per trajectory; table: the [N, W] or [B, N, W] per-step
+        table of a cost registered with one)."""
+        par = np.ascontiguousarray(par)
+        if int(cost_model) >= capi.COST_USER_BASE:
+            W =capi.user_cost_n_tab(cost_model)
+            if (table is None) != (W == 0):
+                raise ValueError(f"cost {cost_model} " + (f"reads a table of {W} words per step: table=" if W else "has no table"))
+            if table is not None:
+                table = np.ascontiguousarray(table)
+                if table.ndim not in (2, 3) or table.shape[-2:] != (self.N, W) or (table.ndim == 3 and table.shape[0] != self.B):
+                    raise ValueError(f"the cost's table: [{self.N}, {W}] or [{self.B}, {self.N}, {W}], got {table.shape}")
+        elif table is not None:
+            raise ValueError("table: a user cost's (costs.Custom)")
+        self.cost_model, self.cost_par = int(cost_model), self._t(par)
+        self.cost_tab = None if table is None else self._t(table)
         if self.user_cost:
             if self.Cux is None:
                 self.Cux = torch.zeros(self.B, self.N, self.m, self.n, dtype=self.dtype, device=self.device)
@@ -236,6 +250,14 @@ class Engine:
         self.q_nonzero = torch.zeros(self.N, dtype=torch.int32, device=self.device)
         self.u_std = 0.0
         self._outer_args = self._advance_args = None
+
+    def update_cost_table(self, table):
+        """New values for the user cost's table, copied INTO the device tensor the engine holds: the argument blocks cached over
+        it (and the raw pointer inside them) stay valid; nothing is compiled, allocated on the device or marshalled again."""
+        if self.cost_tab is None or tuple(np.shape(table)) != tuple(self.cost_tab.shape):
+            raise ValueError(f"update_cost_table: the table is {None if self.cost_tab is None else tuple(self.cost_tab.shape)}, "
+                             f"got {tuple(np.shape(table))}")
+        self.cost_tab.copy_(torch.as_tensor(np.ascontiguousarray(table), dtype=self.dtype))
 
     def set_nominal(self, x_nom, u_nom):
         """nominal_values setter (isls/isls_base.py:80-85): stores the nominal and evaluates its cost."""
@@ -397,7 +419,7 @@ class Engine:
         return capi.Kernels.expand_args(self.Qtab, self.ztab, self.seq, self.u_std, self.c0x, self.c0u, xhat=self.xhat, uhat=self.uhat,
                                         Cxx=self.Cxx if with_hessian else None, Cuu=self.Cuu if with_hessian else None,
                                         Qr=self.Qr, Rr=self.Rr, cost=cost, active=active, cost_model=self.cost_model,
-                                        cost_par=self.cost_par, q_nonzero=self.q_nonzero)
+                                        cost_par=self.cost_par, q_nonzero=self.q_nonzero, cost_tab=self.cost_tab)
 
     def expand(self, with_hessian=True):
         if self.user_cost:                                     # user_expand_kernel: gradient and full Hessian, Cux included
@@ -451,7 +473,7 @@ class Engine:
                                          cost_new=self.cost_new, cost_all=cost_all, wq=self.wq, wr=self.wr, zx=self.zx,
                                          lx=self.lx, zu=self.zu, lu=self.lu, cost_cur=self.cost, flags=flags,
                                          status=self.status, active=active, q_nonzero=self.q_nonzero,
-                                         cost_model=self.cost_model, cost_par=self.cost_par)
+                                         cost_model=self.cost_model, cost_par=self.cost_par, cost_tab=self.cost_tab)
 
     def _admm_block(self, tol_abs, tol_rel, active):
         return capi.Kernels.admm_args(self.xx, self.xu, self.res, zx=self.zx, lx=self.lx, zu=self.zu, lu=self.lu,

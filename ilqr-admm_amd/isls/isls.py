@@ -83,13 +83,28 @@ class iSLS(Base):
         self._cost_function = function
         if hasattr(function, "cost_model"):
             self._host_cost = False
-            self.engine.set_cost_model(function.cost_model, function.params())
+            table = getattr(function, "table", None)           # costs.Custom(table=): per-step data of the user's stage
+            if table is None:
+                self.engine.set_cost_model(function.cost_model, function.params())
+            else:
+                self.engine.set_cost_model(function.cost_model, function.params(), table=table)
+                self._table_version = function._table_version
         elif callable(function):
             # the reference's `cost_function(x[L,N,n], u[L,N,m]) -> [L]` (isls.py:360): evaluated on the host for every
             # candidate of the line search; its expansion comes from the caller's get_Cs
             self._host_cost = True
         else:
             raise TypeError("cost_function must be None, an isls.costs object or a callable cost(x, u)")
+
+    def _sync_cost_table(self):
+        """costs.Custom.set_table since this object last looked: the new values go INTO the engine's device table (no compile, no
+        allocation, cached argument blocks stay valid) and the nominal's cost is evaluated again with them."""
+        f = self._cost_function
+        if self._host_cost or getattr(f, "table", None) is None or f._table_version == self._table_version:
+            return
+        self.engine.update_cost_table(f.table)
+        self._table_version = f._table_version
+        self.engine.evaluate_cost()
 
     @property
     def AB(self):
@@ -120,6 +135,7 @@ class iSLS(Base):
     @nominal_values.setter
     def nominal_values(self, value):
         e = self.engine
+        self._sync_cost_table()
         if e.Qtab is None:                                      # no via-point cost (a callable cost only): a zero table
             e.set_quadratic_cost(np.zeros((1, self.x_dim)), np.zeros((1, self.x_dim, self.x_dim)), np.zeros(self.N, dtype=np.int32), 0.0)
         e.set_nominal(self._batched(value[0], 2), self._batched(value[1], 2))
@@ -154,6 +170,7 @@ class iSLS(Base):
 
     @property
     def cost(self):
+        self._sync_cost_table()
         c = self.engine.cost.detach().cpu().numpy()
         return float(c[0]) if self.batch == 1 else c
 
@@ -223,6 +240,7 @@ class iSLS(Base):
 
     def _expand(self, Cts=None, cts=None):
         e = self.engine
+        self._sync_cost_table()
         if Cts is None:
             if not e.user_cost:                                 # (a user cost's expansion writes Cux)
                 e.Cux = None
@@ -340,6 +358,7 @@ class iSLS(Base):
         if regularization is not None and method == 'batch':
             raise capi.IslsError("solve(method='batch') does not serve a regularisation (its column passes have no such term); use method='dp'")
         self._set_regularization(regularization)
+        self._sync_cost_table()
         e = self.engine
         e.outer_active.fill_(1)
         prev = np.atleast_1d(np.array(self.cost, dtype=np.float64)).copy()
@@ -410,6 +429,7 @@ class iSLS(Base):
         stop rules |dcost| < 1e-3 / oscillation < 1e-3.  Returns the residual log of the last outer iteration."""
         if self._host_cost and get_Cs is None:
             raise ValueError("a callable cost_function needs get_Cs (its gradient / Hessian along the nominal)")
+        self._sync_cost_table()
         max_iter = k_max if k_max is not None else max_iter
         L = max_line_search if max_line_search is not None else max_line_search_iter
         tol = threshold if threshold is not None else tol
@@ -656,7 +676,7 @@ class iSLS(Base):
         for l in range(ub.shape[1]):
             e.kern.rollout_ls(e.model, e.model_par, zero_K, e._t(np.ascontiguousarray(ub[:, l])), e.xhat, zero_u, one, e.Qtab, e.ztab,
                               e.seq, e.u_std, e.xx, e.xu, x0=x0, q_nonzero=e.q_nonzero, cost_model=e.cost_model, cost_par=e.cost_par,
-                              stream=torch.cuda.current_stream().cuda_stream)
+                              cost_tab=e.cost_tab, stream=torch.cuda.current_stream().cuda_stream)
             xs.append(e.xx.cpu().numpy())
         x = np.stack(xs, axis=1)
         return (x[0] if self.batch == 1 else x), u

@@ -171,8 +171,17 @@ class UserSource:
     """What models.Custom and costs.Custom share: the validation and registration of a run-time compiled source (`noun`: model |
     cost) and the way their host-side evaluations put numpy arrays on the device."""
 
-    def _register(self, noun, create, x_dim, u_dim, params, source):
+    _table = None                                            # a cost's per-step table (costs.Custom(table=)): [N, W] or [B, N, W]
+
+    def _register(self, noun, create, x_dim, u_dim, params, source, table=None):
         self.x_dim, self.u_dim = int(x_dim), int(u_dim)
+        if table is not None:
+            table = np.array(table, dtype=np.float64, order="C")
+            if table.ndim not in (2, 3) or table.shape[-1] < 1:
+                raise ValueError("table: [N, W] or [B, N, W] with W >= 1")
+            if table.shape[-1] > capi.USER_MAX_TAB:
+                raise capi.IslsError(f"a user {noun}'s table holds at most {capi.USER_MAX_TAB} words per step, got {table.shape[-1]}")
+            self._table, self._table_version = table, 0
         self._params = np.atleast_1d(np.asarray(params, dtype=np.float64))
         if self._params.ndim > 2:
             raise ValueError("params: [P] or [B, P]")
@@ -185,6 +194,8 @@ class UserSource:
         if re.search(r"\b(asm|__asm|__asm__)\b", source) or "__builtin_amdgcn" in source:
             raise capi.IslsError(f"a user {noun} is plain arithmetic: `asm` and `__builtin_amdgcn_*` are not accepted")
         self.source = source
+        if table is not None:
+            return create(source, self.x_dim, self.u_dim, P, table.shape[-1])
         return create(source, self.x_dim, self.u_dim, P)
 
     def params(self):
@@ -198,6 +209,9 @@ class UserSource:
         par = self._params
         if par.ndim == 2 and par.shape[0] != rows:
             raise ValueError(f"per-trajectory params [{par.shape[0]}, P] need " + need.format(par.shape[0], rows))
+        tab = self._table
+        if tab is not None and tab.ndim == 3 and tab.shape[0] != rows:
+            raise ValueError(f"a per-trajectory table [{tab.shape[0]}, N, W] needs " + need.format(tab.shape[0], rows))
         dev = torch.device("cuda", torch.cuda.current_device())
         self._load(np.float64)
         return torch, kernels(), dev, [torch.as_tensor(np.array(a, dtype=np.float64, order="C"), device=dev) for a in (par,) + arrays]

@@ -75,6 +75,7 @@ extern "C" {
  * model_par_sb = n_par).  Fast (n, m) pairs only (isls_dims_supported), cost model ISLS_COST_VIA; no model hint (lin_on). */
 #define ISLS_MODEL_USER_BASE 1024
 #define ISLS_USER_MAX_PAR 16        /* parameters of a user model, at most                                             */
+#define ISLS_USER_MAX_TAB 16        /* words per step of a user cost's table, at most (isls_user_cost_create_tab)      */
 #define ISLS_DTYPE_F64 0
 #define ISLS_DTYPE_F32 1
 
@@ -91,7 +92,15 @@ extern "C" {
  * trajectory with cost_par_sb = n_par); Qtab / ztab / seq / u_std are then ignored.  isls_expand_quadratic_* serves such an id
  * for the gradients and the nominal cost only (Cxx == Cuu == NULL); the full expansion, with Cux, is isls_user_cost_expand_*.
  * isls_outer_advance_* refuses such an id in `exp` (ISLS_ERR_UNSUPPORTED): run it with exp.c0x == NULL and the user expansion
- * behind it on the same stream, with active = accept.outer_active.  No generic (n, m), no model hint (lin_on). */
+ * behind it on the same stream, with active = accept.outer_active.  No generic (n, m), no model hint (lin_on).
+ * A cost registered with a per-step table of W words (isls_user_cost_create_tab: a reference to track, weights or an obstacle
+ * that change along the horizon) takes the table in three of the fields it ignores otherwise, in isls_rollout_args and in
+ * isls_expand_args alike, stateless like cost_par:
+ *   ztab    = the table, [N, W] or [B, N, W] (row t: the W words `stage` gets as `row` at step t);
+ *   ztab_sb = 0 (shared by the batch) or N * W (one table per trajectory);
+ *   nvia    = W.
+ * ISLS_ERR_ARG, before anything is launched: ztab == NULL, nvia != W, any other ztab_sb.  The values may change between two
+ * launches (a receding-horizon window): nothing is compiled or bound for them. */
 #define ISLS_COST_USER_BASE 1024
 
 /* rollout flags */
@@ -823,6 +832,13 @@ int isls_user_model_step_f32(int32_t id, int32_t R, const void *par, int64_t par
  * (ISLS_ERR_COMPILE; its log stays readable).  ISLS_ERR_UNSUPPORTED: (n, m) not a fast pair, n_par outside
  * [0, ISLS_USER_MAX_PAR]; ISLS_ERR_ARG: a source with `asm` or `__builtin_amdgcn`.  Needs no GPU. */
 int isls_user_cost_create(const char *source, int32_t n, int32_t m, int32_t n_par, int32_t *id);
+/* The same for a cost with a per-step table of n_tab words: `source` then defines the six-argument form
+ *   template <typename S, typename P> __device__ S stage(const S *x, const S *u, const P *par, const P *row, int t, int N);
+ * (`row`: the n_tab words of step t, plain P).  n_tab = 0 is isls_user_cost_create; a source of the other form than n_tab says is
+ * a compile error.  ISLS_ERR_UNSUPPORTED: n_tab outside [0, ISLS_USER_MAX_TAB]. */
+int isls_user_cost_create_tab(const char *source, int32_t n, int32_t m, int32_t n_par, int32_t n_tab, int32_t *id);
+/* Words per step of the cost's table (0: a cost without one), or ISLS_ERR_ARG for an id nobody registered. */
+int isls_user_cost_n_tab(int32_t id);
 /* The compile log of the cost's programs (as isls_user_model_log). */
 int64_t isls_user_cost_log(int32_t id, char *buf, int64_t len);
 /* The gfx950 code object of the cost with `model` (a built-in model of the cost's (n, m), a user model of them, or -1: the
@@ -836,6 +852,12 @@ int isls_user_cost_value_f64(int32_t id, int32_t R, int32_t N, const void *par, 
                              void *cost, void *stream);
 int isls_user_cost_value_f32(int32_t id, int32_t R, int32_t N, const void *par, int64_t par_sb, const void *x, const void *u,
                              void *cost, void *stream);
+/* The same for a cost with a table: tab [N,n_tab] (tab_sb = 0) or [R,N,n_tab] (tab_sb = N * n_tab); ISLS_ERR_ARG for tab == NULL
+ * or another tab_sb, before any launch.  (isls_user_cost_value_* on a cost with a table: ISLS_ERR_ARG.) */
+int isls_user_cost_value_tab_f64(int32_t id, int32_t R, int32_t N, const void *par, int64_t par_sb, const void *tab, int64_t tab_sb,
+                                 const void *x, const void *u, void *cost, void *stream);
+int isls_user_cost_value_tab_f32(int32_t id, int32_t R, int32_t N, const void *par, int64_t par_sb, const void *tab, int64_t tab_sb,
+                                 const void *x, const void *u, void *cost, void *stream);
 /* The expansion of a user cost about the nominal, in the layouts and with the `active` semantics of isls_expand_quadratic_*:
  *   c0x, c0u = gradient ; Cxx = H_xx + 2 Qr ; Cuu = H_uu + 2 Rr ; Cux [B,N,m,n] = H_ux ; cost[b] (nullable) = the nominal's cost.
  * Cxx, Cuu, Cux nullable (skipped).  a->cost_model is the cost's id; Qtab, ztab, seq, u_std, q_nonzero are ignored. */

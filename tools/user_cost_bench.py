@@ -2,7 +2,7 @@
 """Built-in PseudoHuber against the same cost written as an isls.costs.Custom source, on the Tassa parking problem (N = 100,
 L = 20, J = 5, control box) at B = 4096.
 
-    python tools/user_cost_bench.py [--batch 4096] [--reps 20] [--rounds 5]
+    python tools/user_cost_bench.py [--batch 4096] [--reps 20] [--rounds 5] [--legs phuber,arm,table,host]
 
 Two engines on the same problem, the forms alternating over the rounds (medians; spread = max - min over the rounds):
 * one rollout launch (the line search of the ADMM iteration, same gains and ADMM targets on both sides);
@@ -12,6 +12,10 @@ Two engines on the same problem, the forms alternating over the rounds (medians;
 * the 3R arm (9, 3) at L = 40 candidates, built-in via-point cost against its Custom restatement, one rollout launch with the
   prediction reset before each (every winner is replayed): the two-waves-per-SIMD kernels, whose replay keeps three operand
   sets in flight with a user cost and four without;
+* a tracking cost (tests/table_costs.py) in three forms on the Tassa shapes, one rollout launch and one expansion launch each:
+  a constant reference folded into `params` (what a cost without a table can hold), the same reference as a shared [N, W]
+  table, and as a [B, N, W] table -- what the row's way through the line search (fetched two steps ahead, staged in LDS) and
+  the expansion's global reads of it cost;
 * the run-time compile of the Custom source (fresh source: registration with the expansion, then the program with the Tassa
   rollout kernels) and one `solve` iteration of the host slow path (the cost as numpy callables + get_Cs) at a small batch.
 Prints the numbers and one JSON line."""
@@ -29,6 +33,7 @@ for p in (os.path.join(ROOT, "ilqr-admm_amd"), ROOT, os.path.join(ROOT, "tests")
     if p not in sys.path:
         sys.path.insert(0, p)
 
+import table_costs as tc  # noqa: E402
 import user_costs as uc  # noqa: E402
 
 
@@ -95,6 +100,33 @@ def arm_section(a, out, N=100, L=40):
               f"({replayed[i]} of {a.batch} winners replayed)")
 
 
+def table_section(a, out, g, mdl, x, u):
+    from isls import costs
+    N, B = int(g["N"]), a.batch
+    row = np.array([0.5, -0.5, 0.3, 1.0, 1.0, 1.2, 0.8, 0.6])   # z (4), diag Q (4): the same reference at every step
+    u_std = 0.01
+    forms = {"params": costs.Custom(4, 2, np.concatenate([[u_std], row]), tc.params_source(4, 2, row)),
+             "table_shared": costs.Custom(4, 2, [u_std], tc.tracking_source(4, 2), table=np.tile(row, (N, 1))),
+             "table_batch": costs.Custom(4, 2, [u_std], tc.tracking_source(4, 2), table=np.tile(row, (B, N, 1)))}
+    engines = {}
+    for k, c in forms.items():
+        e = make(g, mdl, c, x, u, False).engine
+        e.gain(active=e.admm_active); e.feedforward(active=e.admm_active)
+        engines[k] = e
+    costs0 = [e.cost.cpu().numpy() for e in engines.values()]
+    assert all(np.allclose(c, costs0[0], rtol=1e-12) for c in costs0)   # the three forms are the same cost
+    for what, fn in (("rollout", lambda e: e.rollout(20, active=e.admm_active)), ("expand", lambda e: e.expand())):
+        runs = {k: [] for k in engines}
+        for e in engines.values():
+            timed(lambda: fn(e), 3)
+        for _ in range(a.rounds):
+            for k, e in engines.items():
+                runs[k].append(timed(lambda: fn(e), a.reps))
+        for k, r in runs.items():
+            out[f"tracking_{what}_{k}_us"] = [float(np.median(r)), float(max(r) - min(r))]
+            print(f"tracking {what:8s} {k:13s} median {np.median(r):9.1f} us  spread {max(r) - min(r):7.1f}")
+
+
 def timed(fn, reps):
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record()
@@ -110,9 +142,23 @@ def main():
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--legs", default="phuber,arm,table,host", help="comma-separated: phuber, arm, table, host")
     a = ap.parse_args()
+    legs = set(a.legs.split(","))
     from isls import costs
     g, mdl, x, u = problem(a.batch)
+    out = {"batch": a.batch}
+    if "table" in legs:
+        table_section(a, out, g, mdl, x, u)
+    if "arm" in legs:
+        arm_section(a, out)
+    if "phuber" in legs:
+        phuber_section(a, out, g, mdl, x, u, "host" in legs)
+    print(json.dumps(out))
+
+
+def phuber_section(a, out, g, mdl, x, u, host):
+    from isls import costs
     t0 = time.time()
     src = uc.phuber_source(4, 2, g["par_px"], g["par_pf"]) + f"// {time.time()}\n"      # a fresh source: nothing cached
     cu = costs.Custom(4, 2, uc.phuber_params(g["par_cu"], g["par_cx"], g["par_cf"]), src)
@@ -135,7 +181,6 @@ def main():
     forms = {"rollout": (lambda: eb.rollout(20, active=eb.admm_active), lambda: ec.rollout(20, active=ec.admm_active)),
              "expand": (eb.expand, ec.expand),
              "outer": (lambda: step(eb), lambda: step(ec), lambda: step_adv(ea))}
-    out = {}
     for name in ("rollout", "expand", "outer"):
         fns = forms[name]
         for f in fns:
@@ -147,7 +192,10 @@ def main():
         for i, label in enumerate(("builtin", "custom", "custom_advance")[:len(fns)]):
             out[f"{name}_{label}_us"] = [float(np.median(runs[i])), float(max(runs[i]) - min(runs[i]))]
             print(f"{name:8s} {label:15s} median {np.median(runs[i]):9.1f} us  spread {max(runs[i]) - min(runs[i]):7.1f}")
-    arm_section(a, out)
+    out.update(compile_create_s=t_create, compile_pair_s=t_pair)
+    print(f"compile: registration + expansion {t_create:.2f} s, program with the Tassa rollout kernels {t_pair:.2f} s")
+    if not host:
+        return
     # host slow path for contrast: the same cost as numpy callables, one solve iteration at B = 4
     from isls import iSLS
     hs = iSLS(4, 2, int(g["N"]), batch=4)
@@ -158,10 +206,8 @@ def main():
     t0 = time.time()
     hs.solve(get_Cs=ph.get_Cs, max_iter=1, max_line_search_iter=20)
     torch.cuda.synchronize()
-    out.update(host_solve_iter_s_B4=time.time() - t0, compile_create_s=t_create, compile_pair_s=t_pair, batch=a.batch)
-    print(f"compile: registration + expansion {t_create:.2f} s, program with the Tassa rollout kernels {t_pair:.2f} s; "
-          f"host slow path, one solve iteration at B = 4: {out['host_solve_iter_s_B4']:.3f} s")
-    print(json.dumps(out))
+    out.update(host_solve_iter_s_B4=time.time() - t0)
+    print(f"host slow path, one solve iteration at B = 4: {out['host_solve_iter_s_B4']:.3f} s")
 
 
 if __name__ == "__main__":
