@@ -1,14 +1,14 @@
 // user_model.hip -- user-written forward models: the launches of a model's own kernels -- linearisation, dense closed loop,
 // row-wise step (the device side is user_model.hpp) -- and the isls_user_model_* entry points.  Registry, run-time compilation,
 // module loading and the line search are user_rtc.hip's: a model's program is the key (model, no cost) there.
-#include "monte_carlo.hpp"
+#include "mpc.hpp"
 #include "user_rtc.hpp"
 
 namespace isls {
 
 namespace {
 
-enum Fn { FN_LIN = 0, FN_LOOP, FN_STEP, FN_MC };             // the order of the key's name expressions (user_rtc.hip)
+enum Fn { FN_LIN = 0, FN_LOOP, FN_STEP, FN_MC, FN_MPC };           // the order of the key's name expressions (user_rtc.hip)
 
 // the functions of model `id` for a launch of dims (n, m)
 template <typename T>
@@ -68,6 +68,21 @@ int launch_mc_closed_loop_user(const McP<T> &p0, int model, int grid, int lanes,
 }
 template int launch_mc_closed_loop_user<double>(const McP<double> &, int, int, int, size_t, hipStream_t);
 template int launch_mc_closed_loop_user<float>(const McP<float> &, int, int, int, size_t, hipStream_t);
+
+template <typename T>
+int launch_mpc_step_user(const MpcP<T> &p0, int model, int grid, size_t smem, hipStream_t s)
+{
+    const std::vector<hipFunction_t> *fns;
+    const int rc = prepare<T>(model, p0.n, p0.m, s, &fns);
+    if (rc != ISLS_OK) return rc;
+    MpcP<T> p = p0;
+    void *args[] = {&p};
+    if (grid <= 0) return ISLS_OK;
+    return hipModuleLaunchKernel((*fns)[FN_MPC], grid, 1, 1, kWave, 1, 1, (unsigned)smem, s, args, nullptr) == hipSuccess ? ISLS_OK
+                                                                                                                       : ISLS_ERR_LAUNCH;
+}
+template int launch_mpc_step_user<double>(const MpcP<double> &, int, int, size_t, hipStream_t);
+template int launch_mpc_step_user<float>(const MpcP<float> &, int, int, size_t, hipStream_t);
 
 template <typename T>
 static int user_step(int32_t id, int32_t R, const void *par, int64_t par_sb, const void *x, const void *u, void *xn, hipStream_t s)

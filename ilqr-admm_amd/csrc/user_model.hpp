@@ -6,11 +6,12 @@
 //     #include "user_model.hpp"
 // and its name expressions instantiate, for one (n, m, dtype): every (JM, OCC) variant of rollout_kernel that the launch plan
 // of a built-in model of the same dimensions can pick, user_linearize_kernel, dense_closed_loop_kernel, user_step_kernel and
-// mc_closed_loop_kernel (monte_carlo.hpp).
+// mc_closed_loop_kernel (monte_carlo.hpp) and mpc_step_kernel (mpc.hpp).
 // The rollout kernel is the built-ins' template as it is: only Model<T, NX, NU, ISLS_MODEL_USER> below is new.
 #pragma once
 
 #include "monte_carlo.hpp"
+#include "mpc.hpp"
 #include "rollout_kernel.hpp"
 #include "user_model_ad.hpp"
 

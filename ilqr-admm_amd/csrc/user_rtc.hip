@@ -245,7 +245,7 @@ bool builtin_family(int n, int m, int model, int *mdlw)
 }
 
 // The program of (model, cost, dtype), compiled on first use: its text, its file name and its name expressions in order --
-// lin, loop, step, Monte-Carlo loop, rollouts for a model alone; exp, val, rollouts (none without a model) for a cost.  The
+// lin, loop, step, Monte-Carlo loop, control step, rollouts for a model alone; exp, val, rollouts (none without a model) for a cost.  The
 // compiler's messages go to the cost's log, to the model's when there is no cost.  ISLS_ERR_ARG: no such source, or a model and
 // a cost of different dimensions; ISLS_ERR_UNSUPPORTED: a built-in model with no family for the cost's dimensions.
 int program(int model, int cost, int dtype, Program **out)
@@ -267,7 +267,8 @@ int program(int model, int cost, int dtype, Program **out)
         pg.names = {"isls::user_linearize_kernel<" + T + ", " + dims + ">",
                     "isls::dense_closed_loop_kernel<" + T + ", " + dims + ", " + tmodel + ">",
                     "isls::user_step_kernel<" + T + ", " + dims + ">",
-                    "isls::mc_closed_loop_kernel<" + T + ", " + dims + ", " + tmodel + ">"};
+                    "isls::mc_closed_loop_kernel<" + T + ", " + dims + ", " + tmodel + ">",
+                    "isls::mpc_step_kernel<" + T + ", " + dims + ", " + tmodel + ">"};
     pg.ro0 = (int)pg.names.size();
     pg.mdlw = mdlw;
     pg.ntab = uc ? uc->ntab : 0;

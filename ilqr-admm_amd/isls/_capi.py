@@ -193,6 +193,18 @@ class McLoopArgs(C.Structure):
                 ("work", C.c_void_p), ("work_elems", C.c_int64)]
 
 
+class MpcStepArgs(C.Structure):
+    """isls_mpc_step_args: one control step of a receding-horizon loop, in place (Engine.mpc_step, iSLS.mpc)"""
+    _fields_ = [("B", C.c_int32), ("N", C.c_int32), ("n", C.c_int32), ("m", C.c_int32), ("model", C.c_int32), ("W", C.c_int32),
+                ("model_par", C.c_void_p), ("par_sb", C.c_int64), ("plant_par", C.c_void_p), ("plant_sb", C.c_int64),
+                ("xhat", C.c_void_p), ("uhat", C.c_void_p), ("K", C.c_void_p), ("zx", C.c_void_p), ("zu", C.c_void_p),
+                ("tab", C.c_void_p), ("tab_sb", C.c_int64), ("tab_next", C.c_void_p), ("tab_next_sb", C.c_int64),
+                ("u_lo", C.c_void_p), ("u_hi", C.c_void_p), ("w", C.c_void_p), ("noise_std", C.c_void_p), ("seed", C.c_uint64),
+                ("problem0", C.c_int32), ("step", C.c_int32),
+                ("x_meas_out", C.c_void_p), ("u_out", C.c_void_p), ("x_next_out", C.c_void_p),
+                ("x_meas_sb", C.c_int64), ("u_out_sb", C.c_int64), ("x_next_sb", C.c_int64)]
+
+
 class CovArgs(C.Structure):
     """isls_cov_args: mean and covariance of the linearised closed loop of a batch of stage-local controllers (isls/covariance.py)"""
     _fields_ = [("P", C.c_int32), ("N", C.c_int32), ("n", C.c_int32), ("m", C.c_int32),
@@ -241,7 +253,7 @@ class AdvanceArgs(C.Structure):
 
 # names every build of the library must export (checked by tests/test_capi_host.py)
 EXPORTED = [f"isls_{k}_{s}" for s in ("f64", "f32") for k in
-            ("riccati_gain", "riccati_ff", "riccati_gain_ff", "riccati_ff_prepare", "rollout_ls", "admm_update", "project_rows", "sls_admm", "sls_closed_loop", "columns_rollout", "columns_admm", "dense_closed_loop", "mc_closed_loop", "cov_closed_loop", "sls_controller", "expand_quadratic", "linearize",
+            ("riccati_gain", "riccati_ff", "riccati_gain_ff", "riccati_ff_prepare", "rollout_ls", "admm_update", "project_rows", "sls_admm", "sls_closed_loop", "columns_rollout", "columns_admm", "dense_closed_loop", "mc_closed_loop", "mpc_step", "cov_closed_loop", "sls_controller", "expand_quadratic", "linearize",
              "accept_step", "reduce_convergence", "reduce_convergence_table", "ilqr_admm_outer", "outer_advance", "columns_iteration",
              "user_model_step", "user_cost_value", "user_cost_value_tab", "user_cost_expand", "riccati_gain_reg", "reg_update")] + \
            ["isls_ff_segments", "isls_ff_record_elems", "isls_sls_controller_work_elems", "isls_mc_work_elems", "isls_version", "isls_dims_supported", "isls_dims_generic", "isls_error_string", "isls_timing_create",
@@ -973,6 +985,53 @@ class Kernels:
     def mc_closed_loop(self, a, sfx, stream=None):
         """isls_mc_closed_loop on a filled McLoopArgs (isls/montecarlo.py builds it)"""
         return self._call("mc_closed_loop", sfx, a, stream)
+
+    @staticmethod
+    def _out_col(t, B, d, name):
+        """(ptr, batch stride) of an output of isls_mpc_step: [B, d], or a column [:, s] of a [B, T, d] log (unit stride over d)"""
+        if t is None:
+            return None, 0
+        st = _estrides(t)
+        if tuple(t.shape) != (B, d) or (d != 1 and st[1] != 1):
+            raise ValueError(f"{name}: [{B}, {d}] with contiguous rows, got shape {tuple(t.shape)} strides {st}")
+        return _ptr(t), int(st[0]) if B > 1 else d
+
+    @staticmethod
+    def mpc_step_args(model, model_par, xhat, uhat, K=None, zx=None, zu=None, plant_par=None, tab=None, tab_next=None,
+                      u_lo=None, u_hi=None, w=None, noise_std=None, seed=0, problem0=0, step=0,
+                      x_meas_out=None, u_out=None, x_next_out=None):
+        """isls_mpc_step_args over the caller's arrays: xhat [B,N,n], uhat [B,N,m], K [B,N,m,n], zx, zu (in/out); tab [N,W] or
+        [B,N,W] with tab_next [W] / [B,W]; the outputs [B,.] or columns of [B,T,.] logs."""
+        B, N, n = xhat.shape
+        m = uhat.shape[2]
+        a = MpcStepArgs(B=B, N=N, n=n, m=m, model=int(model), seed=int(seed), problem0=int(problem0), step=int(step))
+        a.model_par, a.par_sb = _par(model_par, B, "model_par")
+        if plant_par is not None:
+            a.plant_par, a.plant_sb = _par(plant_par, B, "plant_par")
+        a.xhat, a.uhat = _ptr(_dense(xhat, (B, N, n), "xhat")), _ptr(_dense(uhat, (B, N, m), "uhat"))
+        a.K = _ptr(_dense(K, (B, N, m, n), "K"))
+        a.zx, a.zu = _ptr(_dense(zx, (B, N, n), "zx")), _ptr(_dense(zu, (B, N, m), "zu"))
+        if tab is not None:
+            if tab.ndim not in (2, 3):
+                raise ValueError(f"tab: [N, W] or [B, N, W], got shape {tuple(tab.shape)}")
+            a.W = int(tab.shape[-1])
+            a.tab, a.tab_sb = _tab(tab, B, (N, a.W), "tab")
+            if tab_next is not None:
+                a.tab_next, a.tab_next_sb = _tab(tab_next, B, (a.W,), "tab_next")
+                if (a.tab_sb == 0) != (a.tab_next_sb == 0):
+                    raise ValueError("tab_next: shared with a shared table, per trajectory with a per-trajectory one")
+        elif tab_next is not None:
+            raise ValueError("tab_next without tab")
+        a.u_lo, a.u_hi = _ptr(_dense(u_lo, (m,), "u_lo")), _ptr(_dense(u_hi, (m,), "u_hi"))
+        a.w, a.noise_std = _ptr(_dense(w, (B, n), "w")), _ptr(_dense(noise_std, (n,), "noise_std"))
+        a.x_meas_out, a.x_meas_sb = Kernels._out_col(x_meas_out, B, n, "x_meas_out")
+        a.u_out, a.u_out_sb = Kernels._out_col(u_out, B, m, "u_out")
+        a.x_next_out, a.x_next_sb = Kernels._out_col(x_next_out, B, n, "x_next_out")
+        return a
+
+    def mpc_step(self, model, model_par, xhat, uhat, stream=None, **kw):
+        """isls_mpc_step: the first control through the plant, the plan moved up by one step in place, re-rolled from x+"""
+        return self._call("mpc_step", _sfx(xhat), self.mpc_step_args(model, model_par, xhat, uhat, **kw), stream)
 
     def cov_closed_loop(self, a, sfx, stream=None):
         """isls_cov_closed_loop on a filled CovArgs (isls/covariance.py builds it)"""

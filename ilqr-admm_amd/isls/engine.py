@@ -263,12 +263,36 @@ class Engine:
         """nominal_values setter (isls/isls_base.py:80-85): stores the nominal and evaluates its cost."""
         self.xhat.copy_(self._t(x_nom).expand(self.B, self.N, self.n))
         self.uhat.copy_(self._t(u_nom).expand(self.B, self.N, self.m))
+        self.nominal_rewritten()
+
+    def nominal_rewritten(self):
+        """The nominal on the device was rewritten (set_nominal, mpc_step): its cost, a cost log of that one entry, every
+        trajectory iterating again with a clean status.  Device work only, nothing is read back."""
         self.evaluate_cost()
         self.cost_hist.zero_()
         self.cost_hist[:, 0] = self.cost                  # cost_log = [initial cost]
         self.hist_len.fill_(1)
         self.outer_active.fill_(1)
         self.status.zero_()
+
+    def mpc_step(self, plant_par=None, u_lo=None, u_hi=None, w=None, noise_std=None, seed=0, step=0, feedback=True,
+                 shift_z=True, tab_next=None, x_meas_out=None, u_out=None, x_next_out=None):
+        """One control step of a receding-horizon loop on the engine's own buffers (isls_mpc_step_*, csrc/mpc.hpp): the first
+        control of every plan through the plant (the model with `plant_par`; None: the model's own), then xhat, uhat, K (feedback
+        only: else the plan is re-rolled open loop and K stays), zx, zu (shift_z) and the user cost's table move up by one step and the plan
+        is rolled out again from the measured state; then nominal_rewritten().  Everything is written INTO the tensors the engine
+        holds -- the contract of update_cost_table: cached argument blocks stay valid -- and nothing is read back.  A
+        linearisation along the old nominal is stale afterwards; a state-independent model keeps its one linearisation."""
+        if self.model is None:
+            raise capi.IslsError("Engine.mpc_step needs a device model (set_model)")
+        self.kern.mpc_step(self.model, self.model_par, self.xhat, self.uhat, K=self.K if feedback else None,
+                           zx=self.zx if shift_z else None, zu=self.zu if shift_z else None,
+                           plant_par=plant_par, tab=self.cost_tab, tab_next=tab_next, u_lo=u_lo, u_hi=u_hi, w=w,
+                           noise_std=noise_std, seed=seed, step=step, x_meas_out=x_meas_out, u_out=u_out, x_next_out=x_next_out,
+                           stream=_stream_ptr())
+        if self._ab_src == LINEARIZED:                         # A, Bm belong to the nominal that has just left
+            self._ab_src = None
+        self.nominal_rewritten()
 
     def set_weights(self, Qr, Rr):
         """ADMM weights Qr [n,n] / [1|N,n,n] / [B,N,n,n], Rr likewise (or None) and what the passes take from them: the line

@@ -23,9 +23,18 @@ from . import _capi as capi
 from . import hostpath
 from .admm import ADMM
 from .base import ALPHAS, Base
+from .engine import STATIC
 from .models import Model
 from .projections import Box, ConvexSets
 from .robust import isls_admm as _isls_admm
+
+
+class MpcResult:
+    """What iSLS.mpc returns: x [B, T+1, n] measured states, u [B, T, m] applied controls, and per control step the cost,
+    status bits and executed ADMM iterations [B, T] of the plan the control was taken from (numpy)."""
+
+    def __init__(self, x, u, cost, status, admm_iters):
+        self.x, self.u, self.cost, self.status, self.admm_iters = x, u, cost, status, admm_iters
 
 
 class iSLS(Base):
@@ -469,6 +478,122 @@ class iSLS(Base):
         # `self.admm_iters` tells how many are real per trajectory
         self.admm_iters = e.admm_iters.cpu().numpy()
         return logs[:int(self.admm_iters[0])] if self.batch == 1 and not host_proj else logs
+
+    # ---- receding-horizon control of the whole batch ----------------------------------------------------------------------
+    def mpc(self, steps, iters=1, project_x=False, project_u=False, rho_x=None, rho_u=None, alpha=1, max_admm_iter=5,
+            max_line_search_iter=20, tol=1e-3, plant_params=None, noise_scale=0.0, w=None, seed=0, feedback=True,
+            warm_start_z=False, clip_u=None, table_future=None, regularization=None):
+        """Model-predictive control of every trajectory of the batch for `steps` control steps, with no host round trip per step.
+        Per control step s: `iters` outer iterations of ilqr_admm's device route about the current plan (same stop rules per
+        trajectory, tol_cost = tol_osc = 1e-3, same gain / feed-forward / line-search settings), then one launch
+        (Engine.mpc_step, isls_mpc_step_*) applies the first control to the plant, moves the plan -- nominal, gains, the user
+        cost's table -- up by one step with its last row held and rolls it out again from the measured state.  The next step's
+        ADMM starts as a fresh ilqr_admm call would: z = 0, lambda = 0; warm_start_z=True keeps the moved z.
+        The plant is the forward model with `plant_params` ([P] or [batch, P]; None: the model's own parameters) plus a
+        disturbance: none, explicit w [batch, steps, n], or noise_scale (a number or [n]) o z drawn on the device with `seed`
+        (the normals of monte_carlo at (seed, trajectory, sample 0, step)).  feedback=True: the moved gains K correct the plan for
+        the measured state, False: the moved controls are rolled out open loop.  clip_u=(lo, hi) (numbers or [m]) clips the
+        APPLIED control only.  table_future [steps, W] or [batch, steps, W] (a costs.Custom(table=) cost): row s enters the
+        window as its last row after step s; without it the last row is held.  The via-point cost of set_cost_variables is
+        horizon-relative: it is reused unchanged in every window (a via point at step t stays t steps ahead of the plant).
+        Returns an MpcResult: x [batch, steps+1, n] (the measured states, x[:, 0] the first), u [batch, steps, m] (the applied
+        controls), cost, status, admm_iters [batch, steps] (of the plan each step was taken from).  They are read once, after
+        the last step; then, with no regularisation, LinAlgError("Quu not positive definite") if any status row has
+        ISLS_ST_NOT_PD.  x_nom, u_nom, K, k hold the last plan afterwards: covariance() and monte_carlo() work on it."""
+        e = self.engine
+        if self._host_ls or e.model is None:
+            raise capi.IslsError("mpc runs on the device: set forward_model to an isls.models descriptor (models.Custom for a model of "
+                                 "your own) and cost_function to an isls.costs object (costs.Custom for a cost of your own), not "
+                                 "Python callables; a host-driven loop can use ilqr_admm and the nominal_values setter")
+        if regularization is not None:
+            raise capi.IslsError("mpc does not serve regularization=: its retry loop reads a counter on the host at every gain pass; "
+                                 "use ilqr_admm(regularization=) in a loop of your own")
+        T_, iters, B, N, n, m = int(steps), int(iters), self.batch, self.N, self.x_dim, self.u_dim
+        if T_ < 1 or iters < 1:
+            raise ValueError("mpc: steps >= 1 and iters >= 1")
+        self._sync_cost_table()
+        if table_future is not None and e.cost_tab is None:
+            raise capi.IslsError("table_future is the future of a costs.Custom(table=) cost's table: set such a cost_function, or move "
+                                 "the via points of set_cost_variables yourself")
+        if w is not None and noise_scale is not None and np.any(np.asarray(noise_scale) != 0):
+            raise ValueError("mpc: explicit w or noise_scale, not both")
+        plant = None
+        if plant_params is not None:
+            pp = np.ascontiguousarray(plant_params, dtype=np.float64)
+            P_ = e.model_par.shape[-1]
+            if pp.ndim not in (1, 2) or pp.shape[-1] != P_ or (pp.ndim == 2 and pp.shape[0] != B):
+                raise capi.IslsError(f"plant_params: [{P_}] for every trajectory or [{B}, {P_}] (one row per trajectory), got "
+                                     f"{pp.shape}")
+            plant = e._t(pp)
+        px, pu, host_proj = self._setup_admm(project_x, project_u, rho_x, rho_u, alpha)
+        if host_proj:
+            raise capi.IslsError("mpc runs on the device: project_x / project_u must be Box or ConvexSets, not Python callables; a "
+                                 "host-driven loop can use ilqr_admm and the nominal_values setter")
+        self._set_regularization(None)
+        if e.Qtab is None:                                      # no via-point cost: a zero table (the nominal_values setter's rule)
+            e.set_quadratic_cost(np.zeros((1, n)), np.zeros((1, n, n)), np.zeros(N, dtype=np.int32), 0.0)
+
+        def vec(v, d):
+            return None if v is None else e._t(np.broadcast_to(np.asarray(v, dtype=np.float64), (d,)).copy())
+        u_lo, u_hi = (None, None) if clip_u is None else (vec(clip_u[0], m), vec(clip_u[1], m))
+        noise_std = vec(noise_scale, n) if (w is None and noise_scale is not None and np.any(np.asarray(noise_scale) != 0)) else None
+        if w is not None:                                       # [steps, batch, n]: a step's rows are one dense block
+            w = e._t(w)
+            if tuple(w.shape) != (B, T_, n):
+                raise ValueError(f"w: [{B}, {T_}, {n}], got {tuple(w.shape)}")
+            w = w.permute(1, 0, 2).contiguous()
+        if table_future is not None:
+            W, per_traj = int(e.cost_tab.shape[-1]), e.cost_tab.ndim == 3
+            tf = e._t(table_future)
+            if tuple(tf.shape) not in ((T_, W), (B, T_, W)) or (tf.ndim == 3 and not per_traj):
+                raise ValueError(f"table_future: [{T_}, {W}]" + (f" or [{B}, {T_}, {W}]" if per_traj else " (the table is shared)") +
+                                 f", got {tuple(tf.shape)}")
+            if per_traj:
+                tf = (tf if tf.ndim == 3 else tf.unsqueeze(0).expand(B, T_, W)).permute(1, 0, 2).contiguous()
+            table_future = tf
+        L, J = int(max_line_search_iter), int(max_admm_iter)
+        z = lambda *s_, dt=e.dtype: torch.zeros(*s_, dtype=dt, device=e.device)   # noqa: E731
+        x_log, u_log, cost_log = z(B, T_ + 1, n), z(B, T_, m), z(B, T_)
+        st_log, it_log = z(B, T_, dt=torch.int32), z(B, T_, dt=torch.int32)
+        logbuf = z(J, B, 2)
+        e.outer_active.fill_(1)
+        e._outer_args, fused = None, False
+        for s in range(T_):                                    # nothing below reads the device
+            for it in range(iters):
+                if it == 0 or not fused:
+                    if e._ab_src != STATIC or self._user_AB:    # a state-independent model keeps its one linearisation
+                        self._linearize(None)
+                    self._expand_regularised(None)
+                if e._outer_args is None:
+                    e.build_outer(L, J, tol_abs=tol, tol_rel=tol, log=logbuf)
+                    # between two outer iterations of a step, Engine.advance where it serves the cost's Hessians
+                    fused = e.user_cost or e._shared_hessian()
+                e.run_outer()
+                if it == iters - 1:
+                    it_log[:, s].copy_(e.admm_iters)
+                    e.accept_x_step(tol_cost=1e-3, tol_osc=1e-3)
+                elif fused:
+                    e.advance(tol_cost=1e-3, tol_osc=1e-3)
+                else:
+                    e.accept_x_step(tol_cost=1e-3, tol_osc=1e-3)
+            cost_log[:, s].copy_(e.cost)
+            st_log[:, s].copy_(e.status)
+            e.mpc_step(plant_par=plant, u_lo=u_lo, u_hi=u_hi, w=None if w is None else w[s], noise_std=noise_std, seed=seed, step=s,
+                       feedback=feedback, shift_z=warm_start_z, tab_next=None if table_future is None else table_future[s],
+                       x_meas_out=x_log[:, s], u_out=u_log[:, s], x_next_out=x_log[:, s + 1])
+            if not warm_start_z:
+                for zz in (e.zx, e.zu):
+                    if zz is not None:
+                        zz.zero_()
+        f = self._cost_function
+        if getattr(f, "table", None) is not None:               # the cost object follows the window the engine holds now
+            f._table = e.cost_tab.cpu().numpy().astype(np.float64)
+        r = MpcResult(x_log.cpu().numpy(), u_log.cpu().numpy(), cost_log.cpu().numpy(), st_log.cpu().numpy(), it_log.cpu().numpy())
+        self.admm_iters = r.admm_iters[:, -1].copy()
+        self.cost_log.append(self.cost)
+        if (r.status & capi.ST_NOT_PD).any():
+            raise np.linalg.LinAlgError("Quu not positive definite")
+        return r
 
     def _setup_admm(self, project_x, project_u, rho_x, rho_u, alpha):
         """project_x / project_u of an ilqr_admm call -> the engine's ADMM state (weights, boxes or device sets, z / lambda

@@ -930,6 +930,60 @@ int isls_mc_closed_loop_f64(const isls_mc_loop_args *a, void *stream);
 int isls_mc_closed_loop_f32(const isls_mc_loop_args *a, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * One control step of a receding-horizon (model-predictive) loop for a batch of B plans, in one launch and in place: the first
+ * control of every plan goes through the plant, the plan moves up by one step with its last row held, and it is rolled out again
+ * from the measured state.  It restates, on the device, what a host loop does with the nominal_values setter
+ * (isls/isls_base.py:80-85: the shifted plan becomes the nominal) around a closed-loop step in the reference's order
+ * (isls/isls_base.py:59-75: the control first, then the step, then the noise), as isls_mc_closed_loop_* does.  Per trajectory b:
+ *   1. x_m = xhat[b,0] ;  u_a = min(max(uhat[b,0], u_lo), u_hi) ;  x+ = f(x_m, u_a; plant_par_b) + w_b
+ *      w_b: none, w [B,n] (explicit), or noise_std o z with the normals z of csrc/philox.hpp at (seed, problem0 + b, sample 0,
+ *      step, coordinate) -- the draws of isls_mc_closed_loop_* at the same counters; the _f32 entry rounds std * z once.
+ *   2. for a in xhat, uhat, K, zx, zu:  a~[t] = a[t+1] (t < N-1), a~[N-1] = a[N-1];  the table likewise, its last row tab_next
+ *      where that is given.  A shared table (tab_sb == 0) is moved once per launch, not once per trajectory.
+ *   3. x_0 = x+ ;  t = 0 .. N-1:  u_t = (K~_t (x_t - x~_t)) + u~_t  (K NULL: u_t = u~_t) ;  t < N-1:  x_{t+1} = f(x_t, u_t; model_par_b)
+ *      Every sum runs over j ascending from 0, every multiply-add of it is one fused operation.
+ *   4. xhat <- x, uhat <- u, K <- K~, zx <- zx~, zu <- zu~, the table, and the outputs x_meas_out = x_m, u_out = u_a, x_next_out = x+.
+ *   N == 1: nothing moves (row 0 is the held row): x_0 = x+, u_0 = (K_0 (x+ - xhat_0)) + uhat_0.
+ * All pointers are device pointers; `_sb` are batch strides in elements, 0 = shared.  model / model_par / par_sb as in
+ * isls_mc_loop_args (the solver's model: the families of csrc/families.def at their own dimensions, ISLS_MODEL_LTI at any
+ * n <= 16, m <= 8, user-model ids); plant_par / plant_sb: the same model with the plant's parameters (NULL: model_par).
+ * In/out: xhat [B,N,n], uhat [B,N,m]; K [B,N,m,n] (nullable: open-loop re-roll); zx [B,N,n], zu [B,N,m] (each nullable: not
+ * moved); tab [N,W] (tab_sb = 0) or [B,N,W] (tab_sb = N W), nullable, with tab_next [W] / [B,W] (tab_next_sb = 0 / W; nullable:
+ * the last row is held).  u_lo, u_hi [m] (each nullable: that side is free) clip the APPLIED control only.
+ * Outputs, each nullable: x_meas_out [B,n], u_out [B,m], x_next_out [B,n], each with a batch stride of its own (a caller points
+ * them at column s of its [B,T,.] logs).  Nothing else is written.
+ * ISLS_ERR_ARG before any launch: a NULL xhat / uhat / model_par, B < 0, N < 1, n outside [1,16], m outside [1,8], a negative
+ * stride, tab with W outside [1,16], w together with noise_std.  ISLS_ERR_UNSUPPORTED: a model without a kernel at (n, m).
+ * B == 0: ISLS_OK, nothing is launched.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct isls_mpc_step_args {
+    int32_t B, N, n, m;
+    int32_t model;
+    int32_t W;                      /* words per row of the table */
+    const void *model_par;
+    int64_t par_sb;
+    const void *plant_par;          /* nullable: model_par */
+    int64_t plant_sb;
+    void *xhat, *uhat;              /* [B,N,n], [B,N,m] */
+    void *K;                        /* [B,N,m,n] nullable */
+    void *zx, *zu;                  /* [B,N,n], [B,N,m] nullable */
+    void *tab;                      /* [.,N,W] nullable */
+    int64_t tab_sb;
+    const void *tab_next;           /* [.,W] nullable */
+    int64_t tab_next_sb;
+    const void *u_lo, *u_hi;        /* [m] nullable */
+    const void *w;                  /* [B,n] nullable */
+    const void *noise_std;          /* [n] nullable */
+    uint64_t seed;
+    int32_t problem0, step;         /* counter offset of this launch's first trajectory; the control step */
+    void *x_meas_out, *u_out, *x_next_out;
+    int64_t x_meas_sb, u_out_sb, x_next_sb;
+} isls_mpc_step_args;
+
+int isls_mpc_step_f64(const isls_mpc_step_args *a, void *stream);
+int isls_mpc_step_f32(const isls_mpc_step_args *a, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Closed-loop covariance of a batch of stage-local controllers: the analytic counterpart of isls_mc_closed_loop_*.  The
  * reference has no covariance code (it samples, or constrains phi_u S0 phi_u' in its SLS form); this is the first and second
  * moment of the LINEARISED closed loop x_{t+1} = f(x_t, u_t) + w_t, u_t = uhat_t + k_t + K_t (x_t - xhat_t) about a nominal
