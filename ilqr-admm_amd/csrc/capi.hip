@@ -175,6 +175,7 @@ ISLS_ENTRY(sls_admm, isls_sls_admm_args, launch_sls_admm, false)
 ISLS_ENTRY(dense_closed_loop, isls_dense_loop_args, launch_dense_closed_loop, false)
 ISLS_ENTRY(mc_closed_loop, isls_mc_loop_args, launch_mc_closed_loop, false)
 ISLS_ENTRY(mpc_step, isls_mpc_step_args, launch_mpc_step, false)
+ISLS_ENTRY(sample_nominal, isls_sample_args, launch_sample_nominal, false)
 ISLS_ENTRY(cov_closed_loop, isls_cov_args, launch_cov_closed_loop, false)
 ISLS_ENTRY(sls_controller, isls_sls_controller_args, launch_sls_controller, false)
 ISLS_ENTRY(columns_rollout, isls_columns_args, launch_columns_rollout, false)

@@ -26,6 +26,7 @@
 #else
 #include "rollout_kernel.hpp"
 #endif
+#include "sampling.hpp"
 #include "user_cost_ad.hpp"
 
 namespace isls {

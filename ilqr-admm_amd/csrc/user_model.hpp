@@ -13,6 +13,7 @@
 #include "monte_carlo.hpp"
 #include "mpc.hpp"
 #include "rollout_kernel.hpp"
+#include "sampling.hpp"
 #include "user_model_ad.hpp"
 
 #ifndef ISLS_USER_NPAR

@@ -205,6 +205,21 @@ class MpcStepArgs(C.Structure):
                 ("x_meas_sb", C.c_int64), ("u_out_sb", C.c_int64), ("x_next_sb", C.c_int64)]
 
 
+class SampleArgs(C.Structure):
+    """isls_sample_args: one sampling round about the nominal, in place (Engine.sample_round, iSLS.sample_nominal)"""
+    _fields_ = [("B", C.c_int32), ("N", C.c_int32), ("n", C.c_int32), ("m", C.c_int32), ("S", C.c_int32),
+                ("model", C.c_int32), ("cost_model", C.c_int32), ("nvia", C.c_int32),
+                ("model_par", C.c_void_p), ("model_par_sb", C.c_int64), ("cost_par", C.c_void_p), ("cost_par_sb", C.c_int64),
+                ("xhat", C.c_void_p), ("uhat", C.c_void_p),
+                ("Qtab", C.c_void_p), ("Qtab_sb", C.c_int64), ("ztab", C.c_void_p), ("ztab_sb", C.c_int64),
+                ("seq", C.c_void_p), ("u_std", C.c_double),
+                ("sigma", C.c_void_p), ("sigma_sb", C.c_int64), ("u_lo", C.c_void_p), ("u_hi", C.c_void_p),
+                ("temperature", C.c_double), ("seed", C.c_uint64), ("problem0", C.c_int32), ("phase", C.c_int32),
+                ("problem_ids", C.c_void_p), ("active", C.c_void_p), ("costs", C.c_void_p),
+                ("cost_before", C.c_void_p), ("cost_after", C.c_void_p), ("cost_best", C.c_void_p), ("ess", C.c_void_p),
+                ("took_best", C.c_void_p), ("stat_sb", C.c_int64)]
+
+
 class CovArgs(C.Structure):
     """isls_cov_args: mean and covariance of the linearised closed loop of a batch of stage-local controllers (isls/covariance.py)"""
     _fields_ = [("P", C.c_int32), ("N", C.c_int32), ("n", C.c_int32), ("m", C.c_int32),
@@ -253,7 +268,7 @@ class AdvanceArgs(C.Structure):
 
 # names every build of the library must export (checked by tests/test_capi_host.py)
 EXPORTED = [f"isls_{k}_{s}" for s in ("f64", "f32") for k in
-            ("riccati_gain", "riccati_ff", "riccati_gain_ff", "riccati_ff_prepare", "rollout_ls", "admm_update", "project_rows", "sls_admm", "sls_closed_loop", "columns_rollout", "columns_admm", "dense_closed_loop", "mc_closed_loop", "mpc_step", "cov_closed_loop", "sls_controller", "expand_quadratic", "linearize",
+            ("riccati_gain", "riccati_ff", "riccati_gain_ff", "riccati_ff_prepare", "rollout_ls", "admm_update", "project_rows", "sls_admm", "sls_closed_loop", "columns_rollout", "columns_admm", "dense_closed_loop", "mc_closed_loop", "mpc_step", "sample_nominal", "cov_closed_loop", "sls_controller", "expand_quadratic", "linearize",
              "accept_step", "reduce_convergence", "reduce_convergence_table", "ilqr_admm_outer", "outer_advance", "columns_iteration",
              "user_model_step", "user_cost_value", "user_cost_value_tab", "user_cost_expand", "riccati_gain_reg", "reg_update")] + \
            ["isls_ff_segments", "isls_ff_record_elems", "isls_sls_controller_work_elems", "isls_mc_work_elems", "isls_version", "isls_dims_supported", "isls_dims_generic", "isls_error_string", "isls_timing_create",
@@ -1032,6 +1047,55 @@ class Kernels:
     def mpc_step(self, model, model_par, xhat, uhat, stream=None, **kw):
         """isls_mpc_step: the first control through the plant, the plan moved up by one step in place, re-rolled from x+"""
         return self._call("mpc_step", _sfx(xhat), self.mpc_step_args(model, model_par, xhat, uhat, **kw), stream)
+
+    @staticmethod
+    def _stat_col(t, B, name):
+        """(ptr, batch stride) of a per-problem statistic of isls_sample_nominal: [B], or a column [:, r] of a [B, rounds] log"""
+        if t is None:
+            return None, 0
+        if tuple(t.shape) != (B,):
+            raise ValueError(f"{name}: [{B}], got shape {tuple(t.shape)}")
+        return _ptr(t), int(_estrides(t)[0]) if B > 1 else 1
+
+    @staticmethod
+    def sample_args(model, model_par, xhat, uhat, Qtab, ztab, seq, u_std, sigma, costs, cost_model=COST_VIA, cost_par=None,
+                    cost_tab=None, u_lo=None, u_hi=None, temperature=1.0, seed=0, problem0=0, active=None, cost_before=None,
+                    cost_after=None, cost_best=None, ess=None, took_best=None, problem_ids=None, phase=0):
+        """isls_sample_args over the caller's arrays: xhat [B,N,n], uhat [B,N,m] (in/out), sigma [m] or [B,m], costs [B,S]; the
+        statistics [B] or columns of [B, rounds] logs (one batch stride for all of them); problem_ids [B] int32: the draws'
+        problem counters; phase 1 / 2: the cost launch / the update launch alone."""
+        B, N, n = xhat.shape
+        m = uhat.shape[2]
+        nvia = int(Qtab.shape[-3])
+        a = SampleArgs(B=B, N=N, n=n, m=m, S=int(costs.shape[1]), model=int(model), cost_model=int(cost_model), nvia=nvia,
+                       u_std=float(u_std), temperature=float(temperature), seed=int(seed), problem0=int(problem0), phase=int(phase))
+        a.problem_ids = _ptr(_dense(problem_ids, (B,), "problem_ids"))
+        a.model_par, a.model_par_sb = _par(model_par, B, "model_par")
+        a.cost_par, a.cost_par_sb = _cost_par(cost_model, cost_par, B)
+        a.xhat, a.uhat = _ptr(_dense(xhat, (B, N, n), "xhat")), _ptr(_dense(uhat, (B, N, m), "uhat"))
+        a.Qtab, a.Qtab_sb = _tab(Qtab, B, (nvia, n, n), "Qtab")
+        a.ztab, a.ztab_sb = _tab(ztab, B, (nvia, n), "ztab")
+        a.seq = _ptr(seq)
+        _cost_tab(a, cost_model, cost_tab)
+        a.sigma, a.sigma_sb = _tab(sigma, B, (m,), "sigma")
+        a.u_lo, a.u_hi = _ptr(_dense(u_lo, (m,), "u_lo")), _ptr(_dense(u_hi, (m,), "u_hi"))
+        a.active = _ptr(active)
+        a.costs = _ptr(_dense(costs, (B, a.S), "costs"))
+        strides = set()
+        for name, t in (("cost_before", cost_before), ("cost_after", cost_after), ("cost_best", cost_best), ("ess", ess),
+                        ("took_best", took_best)):
+            ptr, sb = Kernels._stat_col(t, B, name)
+            setattr(a, name, ptr)
+            if t is not None:
+                strides.add(sb)
+        if len(strides) > 1:
+            raise ValueError("the statistics of isls_sample_nominal share one batch stride")
+        a.stat_sb = strides.pop() if strides else 1
+        return a
+
+    def sample_nominal(self, model, model_par, xhat, uhat, *args, stream=None, **kw):
+        """isls_sample_nominal: one sampling round about (xhat, uhat), in place"""
+        return self._call("sample_nominal", _sfx(xhat), self.sample_args(model, model_par, xhat, uhat, *args, **kw), stream)
 
     def cov_closed_loop(self, a, sfx, stream=None):
         """isls_cov_closed_loop on a filled CovArgs (isls/covariance.py builds it)"""

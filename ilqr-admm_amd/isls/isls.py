@@ -758,6 +758,36 @@ class iSLS(Base):
                               x0s=x0s, noise_scale=noise_scale, w=w, seed=seed, u_bounds=u_bounds, x_bounds=x_bounds, xhat=xhat,
                               uhat=uhat, problems=self.batch, return_trajectories=return_trajectories, **chunks)
 
+    def sample_nominal(self, samples=1024, sigma=0.5, temperature=1.0, rounds=1, seed=0, clip_u=None, return_costs=False):
+        """Sampling warm start of every problem's nominal on the device (isls/sampling.py, isls_sample_nominal_*): per round,
+        `samples` open-loop rollouts from xhat_0 with controls uhat + sigma o z (sample 0: uhat itself; z drawn on the device
+        with seed + round, the normals of monte_carlo at (seed, problem, sample, step); clip_u=(lo, hi), numbers or [m], clips
+        them), each costed with the problem's own cost -- what `cost` means: the via-point cost, costs.PseudoHuber, or a
+        costs.Custom with its table; a NaN counts as +inf.  The nominal moves to uhat + sum_s w_s (u_s - uhat) with
+        w_s ~ exp(-(S_s - S_min) / (temperature max(S_min, tiny))), or to the best sample where that mean does not cost less:
+        the nominal's cost never rises.  sigma: a number, [m] or [batch, m].  x_nom, u_nom are rewritten in place (x_nom[:, 0]
+        stays), then cost, cost_log, status and the masks as the nominal_values setter leaves them.  Returns a SampleResult:
+        cost_before, cost_after [batch], cost_best_sample, took_best, ess [batch, rounds] (+ costs [batch, samples] of the last
+        round with return_costs=True), read once at the end.  IslsError: a forward model or cost that is a Python callable, an
+        (x_dim, u_dim) outside the fast pairs, samples < 1, rounds < 1, temperature <= 0, a negative or non-finite sigma, lo > hi --
+        all before anything is launched -- and, after the rounds (the other problems have moved, cost_log has its entry), a nominal
+        whose own rollout has no finite cost: that problem is left as it is."""
+        from . import sampling
+        e = self.engine
+        if self._host_ls or e.model is None:
+            raise capi.IslsError("sample_nominal runs on the device: set forward_model to an isls.models descriptor (models.Custom for a "
+                                 "model of your own) and cost_function to an isls.costs object (costs.Custom for a cost of your "
+                                 "own), not Python callables")
+        sampling.check_args(self.batch, self.u_dim, samples, sigma, temperature, rounds, clip_u)
+        self._sync_cost_table()
+        if e.Qtab is None:                                      # no via-point cost: a zero table (the nominal_values setter's rule)
+            e.set_quadratic_cost(np.zeros((1, self.x_dim)), np.zeros((1, self.x_dim, self.x_dim)), np.zeros(self.N, dtype=np.int32), 0.0)
+        try:
+            return sampling.run(e, samples=samples, sigma=sigma, temperature=temperature, rounds=rounds, seed=seed, clip_u=clip_u,
+                                return_costs=return_costs)
+        finally:                                                # also when a nominal without a finite cost raises: the others moved
+            self.cost_log.append(self.cost)
+
     def covariance(self, K=None, k=None, x0=None, x0_std=None, x0_cov=None, noise_scale=0.0, noise_cov=None, u_bounds=None,
                    x_bounds=None, full=False):
         """Mean and covariance of every problem's closed loop, predicted without a sample (isls/covariance.py,

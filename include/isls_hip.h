@@ -984,6 +984,77 @@ int isls_mpc_step_f64(const isls_mpc_step_args *a, void *stream);
 int isls_mpc_step_f32(const isls_mpc_step_args *a, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * One sampling round about the nominal of a batch of B problems (a warm start of the MPPI kind: model-predictive path integral
+ * control), in two launches and in place.  The reference has no counterpart: its solvers refine the nominal they are handed
+ * (isls/isls.py:336-374) and end in the nearest local minimum.  Per problem b, with S samples:
+ *   1. eps[0,t,:] = 0 ;  s >= 1:  eps[s,t,:] = sigma_b o z,  z the normals of csrc/philox.hpp at (seed, problem0 + b, sample s,
+ *      step t, coordinate) -- the draws of isls_mc_closed_loop_* at the same counters; the _f32 entry rounds sigma * z once.
+ *   2. u[s,t] = min(max(uhat[b,t] + eps[s,t], u_lo), u_hi) ;  e[s,t] = u[s,t] - uhat[b,t] ;  x[s,0] = xhat[b,0],
+ *      x[s,t+1] = f(x[s,t], u[s,t]; model_par_b)  (open loop).
+ *   3. costs[b,s] = the cost of (x[s], u[s]) as isls_rollout_ls_* counts it for cost_model, by the same code: the via-point cost
+ *      sum_t (x_t-z_t)'Q_t(x_t-z_t) + u_std |u_t|^2, ISLS_COST_PHUBER (ISLS_MODEL_TASSA), or a user cost's sum of `stage` with its
+ *      table row; u_{N-1} is costed, no ADMM terms.  A NaN is written as +inf.  There is no q_nonzero hint here: the via-point
+ *      term is evaluated at every step, so a state that has overflowed to +-inf gives 0 * inf = NaN (hence +inf) also where
+ *      Q_t == 0, a step the line search's hint would skip.
+ *   4. Smin = min_s costs[b,s], smin its FIRST index ;  w_s = exp(-(costs[b,s] - Smin) / (temperature max(Smin, tiny))) / sum of
+ *      the same (tiny: the smallest normal number of the precision) ;  u_new[t] = uhat[b,t] + sum_s w_s e[s,t] ;  ess = 1 / sum w_s^2.
+ *   5. x_new = the rollout of u_new, c_new its cost.  c_new < Smin: (xhat, uhat)[b] <- (x_new, u_new), cost_after = c_new,
+ *      took_best = 0.  Otherwise (also c_new NaN): (xhat, uhat)[b] <- (x[smin], u[smin]), cost_after = Smin, took_best = 1.
+ *      So cost_after <= cost_before = costs[b,0], the cost of the nominal controls rolled out from xhat[b,0].
+ *   xhat[b,0] is never written.  costs[b,0] not finite: the problem is left as it is, cost_before = cost_after = costs[b,0],
+ *   cost_best = Smin, ess = 0, took_best = 0 (the caller decides; iSLS.sample_nominal raises).
+ * Minimum, arg-min and every sum over the samples are taken in a fixed order: the results are bitwise repeatable and do not depend
+ * on B or on the other problems of the launch.  The draws are never stored: step 4 generates them again.  problem_ids [B] gives
+ * every problem the counter of its own draws (a subset of a larger batch repeats that batch's numbers); phase splits the call
+ * into its two launches (1: steps 1-3, 2: steps 4-5 on the costs as they stand) for tools that time them apart.
+ * All pointers are device pointers; `_sb` are batch strides in elements, 0 = shared.  model / model_par / model_par_sb, cost_model /
+ * cost_par / cost_par_sb, Qtab / ztab / seq / u_std / nvia as in isls_rollout_args (a user cost's table in ztab / ztab_sb / nvia).
+ * The families of csrc/families.def, user models and user costs; fast (n, m) pairs only.
+ * In/out: xhat [B,N,n], uhat [B,N,m].  sigma [m] (sigma_sb = 0) or [B,m] (sigma_sb = m), >= 0.  u_lo, u_hi [m], each nullable (that
+ * side is free).  active [B] nullable: a problem with active[b] == 0 is skipped, nothing of it is read or written.
+ * Workspace and output: costs [B,S] (caller allocated).  Statistics, each nullable, element b at b * stat_sb (a caller points them
+ * at column r of its [B, rounds] logs): cost_before, cost_after, cost_best (= Smin), ess; took_best (int32).
+ * ISLS_ERR_ARG before any launch: a NULL xhat / uhat / model_par / sigma / costs, B < 0, N < 1, S < 1, n < 1, m < 1, a negative
+ * stride, phase outside [0,2], temperature not a positive finite number, a via-point cost without its tables, a user cost without cost_par or with
+ * table fields that do not fit its registration.  ISLS_ERR_UNSUPPORTED: (n, m) without the row-per-lane kernels, a model without
+ * a family at (n, m), ISLS_COST_PHUBER with another model than ISLS_MODEL_TASSA, N m words (plus a dense LTI model's) beyond the
+ * 48 KB of LDS the update keeps u_new in, B ceil(S / 64) >= 2^31.  B == 0: ISLS_OK, nothing is launched.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct isls_sample_args {
+    int32_t B, N, n, m, S;
+    int32_t model;
+    int32_t cost_model;
+    int32_t nvia;
+    const void *model_par;
+    int64_t model_par_sb;
+    const void *cost_par;
+    int64_t cost_par_sb;
+    void *xhat, *uhat;              /* [B,N,n], [B,N,m] */
+    const void *Qtab;               /* [.,nvia,n,n] */
+    int64_t Qtab_sb;
+    const void *ztab;               /* [.,nvia,n]; a user cost's table [.,N,W] */
+    int64_t ztab_sb;
+    const int32_t *seq;             /* [N] */
+    double u_std;
+    const void *sigma;              /* [.,m] */
+    int64_t sigma_sb;
+    const void *u_lo, *u_hi;        /* [m] nullable */
+    double temperature;
+    uint64_t seed;
+    int32_t problem0;               /* counter offset of this launch's first problem */
+    int32_t phase;                  /* 0: both launches; 1: the costs only; 2: the update only, on costs [B,S] as they stand */
+    const int32_t *problem_ids;     /* [B] nullable: the problem counter of each problem's draws (else problem0 + b) */
+    const int32_t *active;          /* [B] nullable */
+    void *costs;                    /* [B,S] */
+    void *cost_before, *cost_after, *cost_best, *ess;
+    int32_t *took_best;
+    int64_t stat_sb;
+} isls_sample_args;
+
+int isls_sample_nominal_f64(const isls_sample_args *a, void *stream);
+int isls_sample_nominal_f32(const isls_sample_args *a, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Closed-loop covariance of a batch of stage-local controllers: the analytic counterpart of isls_mc_closed_loop_*.  The
  * reference has no covariance code (it samples, or constrains phi_u S0 phi_u' in its SLS form); this is the first and second
  * moment of the LINEARISED closed loop x_{t+1} = f(x_t, u_t) + w_t, u_t = uhat_t + k_t + K_t (x_t - xhat_t) about a nominal
