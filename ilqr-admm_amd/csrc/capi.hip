@@ -194,6 +194,9 @@ ISLS_TYPED_PAIR(riccati_gain_ff, (const isls_gain_args *g, const isls_ff_args *f
 ISLS_TYPED_PAIR(riccati_gain_reg, (const isls_gain_args *g, const isls_ff_args *ff, const isls_reg_args *r, void *stream),
                 if (!g || !r) return ISLS_ERR_ARG;
                 return launch_gain_reg<T>(*g, (hipStream_t)stream, ff, *r);)
+ISLS_TYPED_PAIR(sample_nominal_fb, (const isls_sample_args *a, const void *K, int64_t K_sb, void *stream),
+                if (!a) return ISLS_ERR_ARG;
+                return launch_sample_nominal_fb<T>(*a, K, K_sb, (hipStream_t)stream);)
 ISLS_TYPED_PAIR(sls_closed_loop, (int32_t M, int32_t N, int32_t n, int32_t m, const void *A, const void *B, const void *K, const void *k,
                                   const void *x0, void *x_log, void *u_log, void *stream),
                 return launch_sls_closed_loop<T>(M, N, n, m, A, B, K, k, x0, x_log, u_log, (hipStream_t)stream);)

@@ -332,6 +332,7 @@ template <typename T> int launch_mc_closed_loop(const isls_mc_loop_args &a, hipS
 int64_t mc_work_elems(int32_t P, int32_t M, int32_t N, int32_t n, int32_t m, int32_t K_form);
 template <typename T> int launch_mpc_step(const isls_mpc_step_args &a, hipStream_t s);
 template <typename T> int launch_sample_nominal(const isls_sample_args &a, hipStream_t s);
+template <typename T> int launch_sample_nominal_fb(const isls_sample_args &a, const void *K, int64_t K_sb, hipStream_t s);
 template <typename T> int launch_sls_controller(const isls_sls_controller_args &a, hipStream_t s);
 int64_t sls_controller_work_elems(int32_t B, int32_t N, int32_t n);
 template <typename T> int launch_columns_rollout(const isls_columns_args &a, hipStream_t s);

@@ -394,11 +394,260 @@ __global__ __launch_bounds__(64) void sample_update_kernel(SampleP<T> p)
     }
 }
 
+// ---- the closed-loop round (isls_sample_nominal_fb_*): every sample's control is uhat_t + G_t (x_t - xhat_t) + eps_t ------------------
+// The same mapping, counters and cost code as above; what differs:
+//   * xa_t = xhat[b,t] (NX words) and G_t = K[b,t] (NU NX words) are read per step at wave-uniform addresses, like uhat_t: the gain
+//     table is never held in registers.
+//   * the update sums the DRAWN noise, d_t = sum_s w_s eps[s,t] (the realised deviation of a closed-loop sample depends on its state
+//     and could not be regenerated without its rollout; the draw can), kSmpTile steps per sweep as above.
+//   * both rollouts of the update need the anchor xa_t while the new states are produced: the new states [N][NX] and controls [N][NU]
+//     stay in LDS until the choice is made, xhat / uhat are read only until then and leave LDS in two contiguous sweeps.
+// These are kernels of their own with an argument block of their own: the open-loop kernels and SampleP<> are as they were.
+template <typename T>
+struct SampleFbP {
+    SampleP<T> p;
+    const T *K;                    // [.,N,m,n]
+    int64_t K_sb;                  // 0 (shared by the batch) or N m n
+};
+
+// eps = sigma o z(seed, problem, sample, step) (sample 0: eps = 0): the draw of SampleDraw<>::controls, unclipped
+template <typename T, int NU>
+__device__ __forceinline__ void smp_noise(const SampleDraw<T, NU> &draw, unsigned int sample, unsigned int step, T (&eps)[NU])
+{
+#pragma unroll
+    for (int g = 0; g < (NU + 3) / 4; ++g) {
+        double z[4];
+        philox::normal4(draw.seed, sample, draw.problem, step, (unsigned int)g, z);
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            const int r = 4 * g + h;
+            if (r < NU) eps[r] = sample == 0u ? T(0) : mc_scale(draw.sig[r], z[h]);
+        }
+    }
+}
+
+// v = base + G (x - xa): the product summed over the state index ascending, then added to base
+template <typename T, int NX, int NU>
+__device__ __forceinline__ void smp_feedback(const T (&base)[NU], const T *G, const T *xa, const T (&x)[NX], T (&v)[NU])
+{
+    T dx[NX];
+#pragma unroll
+    for (int j = 0; j < NX; ++j) dx[j] = x[j] - xa[j];
+#pragma unroll
+    for (int r = 0; r < NU; ++r) {
+        T acc = T(0);
+#pragma unroll
+        for (int j = 0; j < NX; ++j) acc += G[r * NX + j] * dx[j];
+        v[r] = base[r] + acc;
+    }
+}
+
+// u = clip(v + eps), the sum never contracted (the rule for drawn noise)
+template <typename T, int NU>
+__device__ __forceinline__ void smp_clip_add(const SampleDraw<T, NU> &draw, const T (&v)[NU], const T (&eps)[NU], T (&u)[NU])
+{
+#pragma unroll
+    for (int r = 0; r < NU; ++r) {
+        T w = mc_add(v[r], eps[r]);
+        w = w < draw.lo[r] ? draw.lo[r] : w;
+        w = w > draw.hi[r] ? draw.hi[r] : w;
+        u[r] = w;
+    }
+}
+
+template <typename T, int NX, int NU, int MODEL>
+__global__ __launch_bounds__(64) void sample_cost_fb_kernel(SampleFbP<T> q)
+{
+    extern __shared__ __align__(16) unsigned char smp_smem[];
+    const SampleP<T> &p = q.p;
+    const int lane = threadIdx.x, N = p.N;
+    const int b = blockIdx.x / p.chunks, ch = blockIdx.x - b * p.chunks;
+    if (p.active && p.active[b] == 0) return;                  // uniform
+    const int s = ch * kWave + lane;
+    Model<T, NX, NU, MODEL> mdl;
+    mdl.load(p.par + (int64_t)b * p.par_sb, reinterpret_cast<T *>(smp_smem), lane, kWave);
+    __syncthreads();
+    SampleDraw<T, NU> draw;
+    draw.load(p, b);
+    SampleCost<T, NX, NU, MODEL> cost;
+    cost.load(p, b);
+    cost.reset();
+    const T *xh = p.xhat + (int64_t)b * N * NX, *uhp = p.uhat + (int64_t)b * N * NU;
+    const T *G = q.K + (int64_t)b * q.K_sb;
+    T x[NX], xn[NX], u[NU], v[NU], eps[NU], uh[NU];
+#pragma unroll
+    for (int j = 0; j < NX; ++j) x[j] = xh[j];
+    for (int t = 0; t < N; ++t) {
+#pragma unroll
+        for (int r = 0; r < NU; ++r) uh[r] = uhp[(int64_t)t * NU + r];
+        smp_feedback<T, NX, NU>(uh, G + (int64_t)t * NU * NX, xh + (int64_t)t * NX, x, v);
+        smp_noise<T, NU>(draw, (unsigned int)s, (unsigned int)t, eps);
+        smp_clip_add<T, NU>(draw, v, eps, u);
+        cost.add(x, u, t, N);
+        if (t < N - 1) {
+            mdl.step(x, u, xn);
+#pragma unroll
+            for (int j = 0; j < NX; ++j) x[j] = xn[j];
+        }
+    }
+    const T c = cost.total();
+    if (s < p.S) p.costs[(int64_t)b * p.S + s] = c != c ? (T)__builtin_huge_val() : c;
+}
+
+// One closed-loop rollout from xa_0, costed; lane 0 leaves x_t in xbuf[t] and the realised, clipped u_t in ubuf[t].  REPLAY: sample
+// `sample` again, u_t = clip((ua_t + G_t (x_t - xa_t)) + eps_t) with the draws regenerated step by step (ubuf is written only);
+// else the candidate, u_t = clip(v_t + G_t (x_t - xa_t)) with v_t read from ubuf[t] before u_t goes there.
+template <typename T, int NX, int NU, int MODEL, bool REPLAY>
+__device__ __forceinline__ T smp_rollout_fb(const Model<T, NX, NU, MODEL> &mdl, SampleCost<T, NX, NU, MODEL> &cost, const SampleDraw<T, NU> &draw,
+                                            unsigned int sample, T *ubuf, T *xbuf, const T *xa, const T *ua, const T *G, int N, int lane)
+{
+    T x[NX], xn[NX], u[NU], v[NU], base[NU], eps[NU];
+#pragma unroll
+    for (int j = 0; j < NX; ++j) x[j] = xa[j];
+    cost.reset();
+    for (int t = 0; t < N; ++t) {
+#pragma unroll
+        for (int r = 0; r < NU; ++r) base[r] = REPLAY ? ua[(int64_t)t * NU + r] : ubuf[t * NU + r];
+        smp_feedback<T, NX, NU>(base, G + (int64_t)t * NU * NX, xa + (int64_t)t * NX, x, v);
+        if constexpr (REPLAY) {
+            smp_noise<T, NU>(draw, sample, (unsigned int)t, eps);
+        } else {
+#pragma unroll
+            for (int r = 0; r < NU; ++r) eps[r] = T(0);
+        }
+        smp_clip_add<T, NU>(draw, v, eps, u);
+        if (lane == 0) {
+#pragma unroll
+            for (int r = 0; r < NU; ++r) ubuf[t * NU + r] = u[r];
+#pragma unroll
+            for (int j = 0; j < NX; ++j) xbuf[t * NX + j] = x[j];
+        }
+        cost.add(x, u, t, N);
+        if (t < N - 1) {
+            mdl.step(x, u, xn);
+#pragma unroll
+            for (int j = 0; j < NX; ++j) x[j] = xn[j];
+        }
+    }
+    return cost.total();
+}
+
+template <typename T, int NX, int NU, int MODEL>
+__global__ __launch_bounds__(64) void sample_update_fb_kernel(SampleFbP<T> q)
+{
+    extern __shared__ __align__(16) unsigned char smp_smem[];
+    constexpr int MDLW = smp_mdl_words(Model<T, NX, NU, MODEL>::LDS_WORDS), TT = kSmpTile;
+    const SampleP<T> &p = q.p;
+    const int lane = threadIdx.x, N = p.N, S = p.S, b = blockIdx.x;
+    if (p.active && p.active[b] == 0) return;                  // uniform: the trajectory and its statistics stay as they are
+    T *ubuf = reinterpret_cast<T *>(smp_smem) + MDLW;          // [N][NU]
+    T *xbuf = ubuf + N * NU;                                   // [N][NX]
+    const T *cs = p.costs + (int64_t)b * S;
+    const T inf = (T)__builtin_huge_val();
+    const int64_t so = (int64_t)b * p.stat_sb;
+
+    // ---- minimum and first arg-min (as sample_update_kernel) -----------------------------------------------------------------------
+    T cmin = inf;
+    int imin = 0x7fffffff;
+    for (int s = lane; s < S; s += kWave) {
+        const T c = cs[s];
+        if (c < cmin) { cmin = c; imin = s; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const T oc = __shfl_xor(cmin, o, kWave);
+        const int oi = __shfl_xor(imin, o, kWave);
+        if (oc < cmin || (oc == cmin && oi < imin)) { cmin = oc; imin = oi; }
+    }
+    const T c0 = cs[0];
+    if (!(c0 < inf) || !(c0 > -inf)) {                         // the nominal's own rollout has no finite cost: nothing to start from
+        if (lane == 0) {
+            if (p.cost_before) p.cost_before[so] = c0;
+            if (p.cost_after) p.cost_after[so] = c0;
+            if (p.cost_best) p.cost_best[so] = cmin;
+            if (p.ess) p.ess[so] = T(0);
+            if (p.took_best) p.took_best[so] = 0;
+        }
+        return;
+    }
+
+    // ---- weights (as sample_update_kernel) -------------------------------------------------------------------------------------------
+    const T tiny = smp_tiny(T(0));
+    const T lam = p.temperature * (cmin > tiny ? cmin : tiny);
+    T wsum = T(0), w2 = T(0);
+    for (int s = lane; s < S; s += kWave) {
+        const T w = smp_weight(cs[s], cmin, lam);
+        wsum += w;
+        w2 += w * w;
+    }
+    wsum = wave_sum(wsum);
+    w2 = wave_sum(w2);
+
+    Model<T, NX, NU, MODEL> mdl;
+    mdl.load(p.par + (int64_t)b * p.par_sb, reinterpret_cast<T *>(smp_smem), lane, kWave);
+    SampleDraw<T, NU> draw;
+    draw.load(p, b);
+    SampleCost<T, NX, NU, MODEL> cost;
+    cost.load(p, b);
+    T *xh = p.xhat + (int64_t)b * N * NX, *uhp = p.uhat + (int64_t)b * N * NU;
+    const T *G = q.K + (int64_t)b * q.K_sb;
+
+    // ---- v_t = uhat_t + sum_s w_s eps_st, the draws regenerated ---------------------------------------------------------------------
+    for (int t0 = 0; t0 < N; t0 += TT) {
+        T acc[TT][NU];
+#pragma unroll
+        for (int tt = 0; tt < TT; ++tt) {
+#pragma unroll
+            for (int r = 0; r < NU; ++r) acc[tt][r] = T(0);
+        }
+        for (int s = lane; s < S; s += kWave) {
+            const T wn = smp_weight(cs[s], cmin, lam) / wsum;
+#pragma unroll
+            for (int tt = 0; tt < TT; ++tt) {
+                if (t0 + tt < N) {                             // uniform
+                    T eps[NU];
+                    smp_noise<T, NU>(draw, (unsigned int)s, (unsigned int)(t0 + tt), eps);
+#pragma unroll
+                    for (int r = 0; r < NU; ++r) acc[tt][r] += wn * eps[r];
+                }
+            }
+        }
+#pragma unroll
+        for (int tt = 0; tt < TT; ++tt) {
+#pragma unroll
+            for (int r = 0; r < NU; ++r) {
+                const T a = wave_sum(acc[tt][r]);
+                if (lane == 0 && t0 + tt < N) ubuf[(t0 + tt) * NU + r] = mc_add(uhp[(int64_t)(t0 + tt) * NU + r], a);
+            }
+        }
+    }
+    __syncthreads();
+
+    // ---- the candidate in closed loop; where it does not beat the best sample, that sample again -------------------------------------
+    const T cnew = smp_rollout_fb<T, NX, NU, MODEL, false>(mdl, cost, draw, 0u, ubuf, xbuf, xh, uhp, G, N, lane);
+    const bool take_best = !(cnew < cmin);
+    if (take_best) {                                           // uniform
+        __syncthreads();
+        smp_rollout_fb<T, NX, NU, MODEL, true>(mdl, cost, draw, (unsigned int)imin, ubuf, xbuf, xh, uhp, G, N, lane);
+    }
+    __syncthreads();
+    for (int e = lane; e < N * NU; e += kWave) uhp[e] = ubuf[e];
+    for (int e = NX + lane; e < N * NX; e += kWave) xh[e] = xbuf[e];   // xhat_0 is never written
+    if (lane == 0) {
+        if (p.cost_before) p.cost_before[so] = c0;
+        if (p.cost_after) p.cost_after[so] = take_best ? cmin : cnew;
+        if (p.cost_best) p.cost_best[so] = cmin;
+        if (p.ess) p.ess[so] = (wsum * wsum) / w2;
+        if (p.took_best) p.took_best[so] = take_best ? 1 : 0;
+    }
+}
+
 #ifndef __HIPCC_RTC__
-// the two launches of a user model and / or a user cost (user_rtc.hip), from the module of the (model, cost) pair
+// the two launches of a user model and / or a user cost (user_rtc.hip), from the module of the (model, cost) pair; K: the closed-loop
+// pair of kernels with these gains (nullptr: the open-loop pair)
 template <typename T>
 int launch_sample_user(const SampleP<T> &p, int model, int cost, int n, int m, size_t smem_cost, size_t smem_update, int phase,
-                       hipStream_t s);
+                       hipStream_t s, const T *K = nullptr, int64_t K_sb = 0);
 #endif
 
 }  // namespace isls

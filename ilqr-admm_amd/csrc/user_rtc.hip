@@ -246,7 +246,7 @@ bool builtin_family(int n, int m, int model, int *mdlw)
 
 // The program of (model, cost, dtype), compiled on first use: its text, its file name and its name expressions in order --
 // lin, loop, step, Monte-Carlo loop, control step, rollouts for a model alone; exp, val, rollouts (none without a model) for a cost;
-// behind them the two kernels of the sampling round where the key has a model.  The
+// behind them the four kernels of the sampling round (the open-loop pair, then the closed-loop pair) where the key has a model.  The
 // compiler's messages go to the cost's log, to the model's when there is no cost.  ISLS_ERR_ARG: no such source, or a model and
 // a cost of different dimensions; ISLS_ERR_UNSUPPORTED: a built-in model with no family for the cost's dimensions.
 int program(int model, int cost, int dtype, Program **out)
@@ -286,7 +286,9 @@ int program(int model, int cost, int dtype, Program **out)
     pg.smp0 = -1;
     if (model != kNone) {
         pg.smp0 = (int)pg.names.size();
-        for (const char *k : {"isls::sample_cost_kernel<", "isls::sample_update_kernel<"}) pg.names.push_back(k + T + ", " + dims + ", " + tmodel + ">");
+        // (the closed-loop pair of isls_sample_nominal_fb_* behind the open-loop one: smp0 + 2, smp0 + 3)
+        for (const char *k : {"isls::sample_cost_kernel<", "isls::sample_update_kernel<", "isls::sample_cost_fb_kernel<", "isls::sample_update_fb_kernel<"})
+            pg.names.push_back(k + T + ", " + dims + ", " + tmodel + ">");
     }
     std::string src = uc ? "#include \"user_cost_ad.hpp\"\n" : "#include \"user_model_ad.hpp\"\n";
     if (um) src += wrap_source("isls_user", "user_model", um->source) + "#define ISLS_USER_NPAR " + std::to_string(um->npar) + "\n";

@@ -24,7 +24,7 @@ struct Program {                                             // one key: a model
     std::vector<std::string> names, lowered;                 // name expressions and their mangled names
     int ro0 = 0, mdlw = 0;                                   // index of the first rollout variant; LDS words of the model (plan_rollout)
     int ntab = 0;                                            // words per step of the cost's table (its side records enter the plan too)
-    int smp0 = -1;                                           // index of sample_cost_kernel, sample_update_kernel behind it (a key with a model)
+    int smp0 = -1;                                           // index of sample_cost_kernel; sample_update_kernel and the two *_fb_kernel behind it (a key with a model)
     std::vector<std::pair<int, int>> ro;                     // (JM, OCC) of the rollout variants: names[ro0 + i]
     std::map<int, std::pair<hipModule_t, std::vector<hipFunction_t>>> dev;   // device -> module, functions
 };

@@ -268,7 +268,7 @@ class AdvanceArgs(C.Structure):
 
 # names every build of the library must export (checked by tests/test_capi_host.py)
 EXPORTED = [f"isls_{k}_{s}" for s in ("f64", "f32") for k in
-            ("riccati_gain", "riccati_ff", "riccati_gain_ff", "riccati_ff_prepare", "rollout_ls", "admm_update", "project_rows", "sls_admm", "sls_closed_loop", "columns_rollout", "columns_admm", "dense_closed_loop", "mc_closed_loop", "mpc_step", "sample_nominal", "cov_closed_loop", "sls_controller", "expand_quadratic", "linearize",
+            ("riccati_gain", "riccati_ff", "riccati_gain_ff", "riccati_ff_prepare", "rollout_ls", "admm_update", "project_rows", "sls_admm", "sls_closed_loop", "columns_rollout", "columns_admm", "dense_closed_loop", "mc_closed_loop", "mpc_step", "sample_nominal", "sample_nominal_fb", "cov_closed_loop", "sls_controller", "expand_quadratic", "linearize",
              "accept_step", "reduce_convergence", "reduce_convergence_table", "ilqr_admm_outer", "outer_advance", "columns_iteration",
              "user_model_step", "user_cost_value", "user_cost_value_tab", "user_cost_expand", "riccati_gain_reg", "reg_update")] + \
            ["isls_ff_segments", "isls_ff_record_elems", "isls_sls_controller_work_elems", "isls_mc_work_elems", "isls_version", "isls_dims_supported", "isls_dims_generic", "isls_error_string", "isls_timing_create",
@@ -1096,6 +1096,16 @@ class Kernels:
     def sample_nominal(self, model, model_par, xhat, uhat, *args, stream=None, **kw):
         """isls_sample_nominal: one sampling round about (xhat, uhat), in place"""
         return self._call("sample_nominal", _sfx(xhat), self.sample_args(model, model_par, xhat, uhat, *args, **kw), stream)
+
+    def sample_nominal_fb(self, model, model_par, xhat, uhat, *args, K, stream=None, **kw):
+        """isls_sample_nominal_fb: the round in closed loop about the gains K [N,m,n] (shared) or [B,N,m,n], in place"""
+        a = self.sample_args(model, model_par, xhat, uhat, *args, **kw)
+        if K is None:
+            raise ValueError("K: the gains [N, m, n] or [B, N, m, n]")
+        if K.dtype != xhat.dtype:
+            raise ValueError(f"K: dtype {xhat.dtype}, got {K.dtype}")
+        ptr, sb = _tab(K, a.B, (a.N, a.m, a.n), "K")
+        return self._invoke("sample_nominal_fb", _sfx(xhat), C.byref(a), C.c_void_p(ptr), C.c_int64(sb), stream=stream)
 
     def cov_closed_loop(self, a, sfx, stream=None):
         """isls_cov_closed_loop on a filled CovArgs (isls/covariance.py builds it)"""

@@ -11,6 +11,7 @@ contiguous stream (A: N*n*n, K: N*m*n, x: N*n ... elements) that a wavefront slo
 (Riccati) or forwards (rollout) with one-step-ahead prefetch; shared tables (LTI A/B, via-point Q, box
 bounds, rho weights) are passed with zero batch/time strides and stay cache-resident.
 """
+import functools
 import os
 
 import numpy as np
@@ -294,17 +295,19 @@ class Engine:
             self._ab_src = None
         self.nominal_rewritten()
 
-    def sample_round(self, sigma, costs, u_lo=None, u_hi=None, temperature=1.0, seed=0, active=None, **stats):
+    def sample_round(self, sigma, costs, u_lo=None, u_hi=None, temperature=1.0, seed=0, active=None, K=None, **stats):
         """One sampling round about the nominal on the engine's own buffers (isls_sample_nominal_*, csrc/sampling.hpp): costs
         [B, S] of S open-loop rollouts with controls drawn about uhat (sigma [m] or [B, m], clipped to u_lo / u_hi), then xhat,
         uhat <- their path-integral mean, or the best sample where that mean does not beat it.  Written INTO the tensors the engine
         holds, nothing is read back; `stats`: cost_before, cost_after, cost_best, ess, took_best [B] (or columns of [B, rounds]).
-        The caller ends a series of rounds with nominal_rewritten()."""
+        The caller ends a series of rounds with nominal_rewritten().  K [N, m, n] or [B, N, m, n] (a device tensor of the engine's
+        dtype): the round in closed loop about these gains (isls_sample_nominal_fb_*), controls uhat_t + K_t (x_t - xhat_t) + noise."""
         if self.model is None:
             raise capi.IslsError("Engine.sample_round needs a device model (set_model)")
-        self.kern.sample_nominal(self.model, self.model_par, self.xhat, self.uhat, self.Qtab, self.ztab, self.seq, self.u_std, sigma,
-                                 costs, cost_model=self.cost_model, cost_par=self.cost_par, cost_tab=self.cost_tab, u_lo=u_lo,
-                                 u_hi=u_hi, temperature=temperature, seed=seed, active=active, stream=_stream_ptr(), **stats)
+        fn = self.kern.sample_nominal if K is None else functools.partial(self.kern.sample_nominal_fb, K=K)
+        fn(self.model, self.model_par, self.xhat, self.uhat, self.Qtab, self.ztab, self.seq, self.u_std, sigma,
+           costs, cost_model=self.cost_model, cost_par=self.cost_par, cost_tab=self.cost_tab, u_lo=u_lo,
+           u_hi=u_hi, temperature=temperature, seed=seed, active=active, stream=_stream_ptr(), **stats)
         if self._ab_src == LINEARIZED:                         # A, Bm belong to the nominal that has just left
             self._ab_src = None
 

@@ -758,7 +758,24 @@ class iSLS(Base):
                               x0s=x0s, noise_scale=noise_scale, w=w, seed=seed, u_bounds=u_bounds, x_bounds=x_bounds, xhat=xhat,
                               uhat=uhat, problems=self.batch, return_trajectories=return_trajectories, **chunks)
 
-    def sample_nominal(self, samples=1024, sigma=0.5, temperature=1.0, rounds=1, seed=0, clip_u=None, return_costs=False):
+    def _sampling_gains(self):
+        """The gains of sample_nominal(feedback=True): the backward pass about the nominal as it stands on the device -- linearise,
+        expand, gain pass on the form that writes the K array (what backward_pass_DP runs) -- for every trajectory, with the
+        engine's regularisation if it has one.  A Quu that stays not positive definite raises as iterate_once_dp does."""
+        e = self.engine
+        e.outer_active.fill_(1)
+        e.status.zero_()
+        if not self._user_AB:
+            self._linearize(None)
+        self._expand()
+        e.gain()
+        st = e.status.cpu().numpy()
+        if (st & capi.ST_NOT_PD).any():
+            raise np.linalg.LinAlgError(f"Quu not positive definite for trajectories {np.nonzero(st & capi.ST_NOT_PD)[0].tolist()}")
+        return e.K
+
+    def sample_nominal(self, samples=1024, sigma=0.5, temperature=1.0, rounds=1, seed=0, clip_u=None, return_costs=False,
+                       feedback=None, regularization=_KEEP):
         """Sampling warm start of every problem's nominal on the device (isls/sampling.py, isls_sample_nominal_*): per round,
         `samples` open-loop rollouts from xhat_0 with controls uhat + sigma o z (sample 0: uhat itself; z drawn on the device
         with seed + round, the normals of monte_carlo at (seed, problem, sample, step); clip_u=(lo, hi), numbers or [m], clips
@@ -771,20 +788,39 @@ class iSLS(Base):
         round with return_costs=True), read once at the end.  IslsError: a forward model or cost that is a Python callable, an
         (x_dim, u_dim) outside the fast pairs, samples < 1, rounds < 1, temperature <= 0, a negative or non-finite sigma, lo > hi --
         all before anything is launched -- and, after the rounds (the other problems have moved, cost_log has its entry), a nominal
-        whose own rollout has no finite cost: that problem is left as it is."""
+        whose own rollout has no finite cost: that problem is left as it is.
+
+        feedback: the samples run in CLOSED LOOP about feedback gains (isls_sample_nominal_fb_*), u_s,t = clip((uhat_t +
+        K_t (x_s,t - xhat_t)) + eps_s,t) with the same draws eps as the open-loop round of that seed: noise injected at step t is
+        corrected at the steps behind it, which is what an unstable or strongly nonlinear plant needs.  The nominal moves to the
+        closed-loop rollout of uhat + sum_s w_s eps_s (the weighted DRAWN noise) or to the best sample, and what is stored are the
+        realised states and the realised, clipped controls: x_nom, u_nom are dynamically consistent and inside clip_u.
+        feedback=None or False: the open-loop rounds above.  feedback=an array [N, m, n] or [batch, N, m, n] (numpy or torch; a
+        torch tensor on the device is used in place): these gains in every round -- `q.sample_nominal(feedback=q.K)` after a solve;
+        a wrong shape or a non-finite entry raises IslsError before anything is launched.  feedback=True: before EVERY round the
+        backward pass about the current nominal (linearise, expand, gain pass: what backward_pass_DP runs) gives the gains, for
+        every trajectory; the engine's K is overwritten, k is stale afterwards, and the status is read once per round.
+        regularization (an `isls.Regularization` or None, as in `solve`; not given: the engine's setting stays) is the gain pass's:
+        it is read with feedback=True only, every other form runs no gain pass and leaves the engine's setting and mu alone;
+        without one, a Quu that is not positive definite raises np.linalg.LinAlgError as iterate_once_dp does -- in the first round
+        before anything is sampled."""
         from . import sampling
         e = self.engine
         if self._host_ls or e.model is None:
             raise capi.IslsError("sample_nominal runs on the device: set forward_model to an isls.models descriptor (models.Custom for a "
                                  "model of your own) and cost_function to an isls.costs object (costs.Custom for a cost of your "
                                  "own), not Python callables")
-        sampling.check_args(self.batch, self.u_dim, samples, sigma, temperature, rounds, clip_u)
+        sampling.check_args(self.batch, self.u_dim, samples, sigma, temperature, rounds, clip_u, feedback, self.N, self.x_dim)
+        if feedback is True:                                    # the only form that runs a gain pass: regularization= is its
+            if regularization is not iSLS._KEEP:
+                self._set_regularization(regularization)
+            feedback = self._sampling_gains
         self._sync_cost_table()
         if e.Qtab is None:                                      # no via-point cost: a zero table (the nominal_values setter's rule)
             e.set_quadratic_cost(np.zeros((1, self.x_dim)), np.zeros((1, self.x_dim, self.x_dim)), np.zeros(self.N, dtype=np.int32), 0.0)
         try:
             return sampling.run(e, samples=samples, sigma=sigma, temperature=temperature, rounds=rounds, seed=seed, clip_u=clip_u,
-                                return_costs=return_costs)
+                                return_costs=return_costs, feedback=feedback, feedback_checked=True)
         finally:                                                # also when a nominal without a finite cost raises: the others moved
             self.cost_log.append(self.cost)
 

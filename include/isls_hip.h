@@ -1054,6 +1054,31 @@ typedef struct isls_sample_args {
 int isls_sample_nominal_f64(const isls_sample_args *a, void *stream);
 int isls_sample_nominal_f32(const isls_sample_args *a, void *stream);
 
+/* The same round in CLOSED LOOP about feedback gains (iLQG-guided / tube MPPI): noise injected at step t is corrected at the steps
+ * behind it, so the samples stay near the nominal, where the model and the gains are valid.  K [.,N,m,n] are the gains G_t = K[b,t]
+ * (K_sb = 0: shared by the batch; N m n: per problem); the anchors xa = xhat[b], ua = uhat[b] are the nominal as it stands when the
+ * launch begins.  `a` is read as by isls_sample_nominal_* (phase, active, problem_ids and the statistics mean the same) and the
+ * draws come from the same counters: a closed-loop and an open-loop round with one seed see the same noise.  Per problem b:
+ *   1. eps[s,t,:] as above (sample 0: zero).
+ *   2. x[s,0] = xa_0 ;  u[s,t] = min(max((ua_t + G_t (x[s,t] - xa_t)) + eps[s,t], u_lo), u_hi) ;  x[s,t+1] = f(x[s,t], u[s,t]).
+ *      The feedback product is summed over the state index ascending and added to ua_t first; the drawn noise is then added with
+ *      a sum that is never contracted.
+ *   3. costs[b,s] as above, by the same code; a NaN is written as +inf.
+ *   4. Smin, smin, w_s, ess as above (the same fixed order) ;  d_t = sum_s w_s eps[s,t] -- the DRAWN noise, not the realised clipped
+ *      deviation: that depends on the sample's state and could not be generated again without its rollout, the draw can.
+ *   5. The candidate is the closed-loop rollout of v_t = ua_t + d_t from xa_0: u_new_t = min(max(v_t + G_t (x_new_t - xa_t), u_lo),
+ *      u_hi), c_new its cost.  c_new < Smin: (xhat, uhat)[b] <- (x_new, u_new), cost_after = c_new, took_best = 0.  Otherwise (also
+ *      c_new NaN): sample smin is rolled out again in closed loop from its regenerated draws, (xhat, uhat)[b] <- (x[smin], u[smin]),
+ *      cost_after = Smin, took_best = 1.  What is stored are the realised states and the realised, clipped controls: the new nominal
+ *      is dynamically consistent and inside the clip.  cost_before = costs[b,0]: the cost of the nominal itself where it is
+ *      consistent and inside the clip (sample 0 then never leaves it).
+ *   xhat[b,0] is never written; a costs[b,0] that is not finite leaves the problem as it is, with the statistics as above.
+ * The update keeps the new states and controls in LDS until the choice is made (the anchors are needed until then).
+ * ISLS_ERR_ARG before any launch: a NULL K, a negative K_sb, and everything isls_sample_nominal_* refuses.  ISLS_ERR_UNSUPPORTED: as
+ * above, the LDS limit being N (n + m) words (plus a dense LTI model's) within the same 48 KB. */
+int isls_sample_nominal_fb_f64(const isls_sample_args *a, const void *K, int64_t K_sb, void *stream);
+int isls_sample_nominal_fb_f32(const isls_sample_args *a, const void *K, int64_t K_sb, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Closed-loop covariance of a batch of stage-local controllers: the analytic counterpart of isls_mc_closed_loop_*.  The
  * reference has no covariance code (it samples, or constrains phi_u S0 phi_u' in its SLS form); this is the first and second

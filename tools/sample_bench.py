@@ -8,6 +8,9 @@ share of problems whose straight-line guess crosses the bump and whose cost afte
 round in front than without.
 
     python tools/sample_bench.py [--batch 4096] [--samples 1024] [--blocks 7] [--out profiles/sample_bench.json]
+    python tools/sample_bench.py --feedback [...]    the closed-loop round (sample_nominal(feedback=)): its two launches beside the
+                                 open-loop ones in the same blocks, gains from a regularised backward pass, and the warm start of
+                                 (b) with feedback=True at the recorded sigma and at 0.3; added to --out under keys of their own
 """
 import argparse
 import json
@@ -131,14 +134,76 @@ def measure(name, make, ref, kw, S, blocks):
             f"{name}_numpy_ms_extrapolated_to_batch": numpy_ms * e.B}
 
 
+def measure_feedback(name, make, kw, S, blocks):
+    """Both launches of a round in closed loop about the gains of a backward pass (isls_sample_nominal_fb_*) and, in the same
+    blocks, in open loop: each between its own HIP events through `phase`, medians over the blocks."""
+    from isls import Regularization
+    q = make()
+    e = q.engine
+    q.sample_nominal(samples=S, seed=0, feedback=True, regularization=Regularization(), **kw)   # warm-up; leaves gains in e.K
+    K = e.K.clone()
+    sigma = e._t(np.full(e.m, float(kw["sigma"])))
+    costs_ = torch.zeros(e.B, S, dtype=e.dtype, device=e.device)
+    clip = [None if "clip_u" not in kw else e._t(np.full(e.m, float(v))) for v in kw.get("clip_u", (0, 0))]
+    ms = {(fb, ph): [] for fb in (False, True) for ph in (1, 2)}
+    for k in range(blocks):
+        for fb in (False, True):
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            for ph in (1, 2):
+                ev[ph - 1].record()
+                e.sample_round(sigma, costs_, u_lo=clip[0], u_hi=clip[1], temperature=kw["temperature"], seed=100 + k, phase=ph,
+                               K=K if fb else None)
+            ev[2].record()
+            torch.cuda.synchronize()
+            ms[fb, 1].append(ev[0].elapsed_time(ev[1]))
+            ms[fb, 2].append(ev[1].elapsed_time(ev[2]))
+    med = lambda fb, ph: float(np.median(ms[fb, ph]))            # noqa: E731
+    return {f"{name}_sample_cost_fb_kernel_ms": med(True, 1), f"{name}_sample_update_fb_kernel_ms": med(True, 2),
+            f"{name}_sample_cost_kernel_ms_beside_fb": med(False, 1), f"{name}_sample_update_kernel_ms_beside_fb": med(False, 2)}
+
+
+def feedback_main(a):
+    """--feedback: the closed-loop kernels beside the open-loop ones, and the warm-start experiment on (b) with feedback=True at the
+    recorded sigma and at a smaller one; written under new keys of the existing file (the recorded open-loop figures stay)."""
+    from isls import Regularization
+    B, N, S = a.batch, a.horizon, a.samples
+    out = json.load(open(a.out)) if os.path.exists(a.out) else {}
+    make_di, _, kw_di = di_problem(B, N)
+    out.update(measure_feedback("di", make_di, kw_di, S, a.blocks))
+    make_q, _, kw_q = quad_problem(B, N)
+    out.update(measure_feedback("quad_bump", make_q, kw_q, S, a.blocks))
+    plain = make_q()
+    plain.solve(max_iter=20, regularization=Regularization())
+    for sigma in (kw_q["sigma"], 0.3):
+        warm = make_q()
+        w = warm.sample_nominal(samples=S, seed=0, feedback=True, regularization=Regularization(), **{**kw_q, "sigma": sigma})
+        warm.solve(max_iter=20, regularization=Regularization())
+        tag = f"quad_bump_fb_sigma_{sigma:g}"
+        out.update({f"{tag}_median_cost_before": float(np.median(w.cost_before)),
+                    f"{tag}_median_cost_after_sampling": float(np.median(w.cost_after)),
+                    f"{tag}_share_moved": float(np.mean(w.cost_after < w.cost_before)),
+                    f"{tag}_median_cost_warm": float(np.median(warm.cost)),
+                    f"{tag}_share_lower_with_warm_start": float(np.mean(warm.cost < plain.cost))})
+    out["quad_bump_fb_median_cost_plain"] = float(np.median(plain.cost))
+    out["feedback_batch_horizon_samples_blocks"] = [B, N, S, a.blocks]
+    print(json.dumps({k: v for k, v in out.items() if "fb" in k or "feedback" in k}))
+    with open(a.out, "w") as f:
+        json.dump(out, f)
+        f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--feedback", action="store_true", help="measure the closed-loop round (feedback=) beside the open-loop one and "
+                    "add its figures to --out; the recorded open-loop figures stay")
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--horizon", type=int, default=100)
     ap.add_argument("--samples", type=int, default=1024)
     ap.add_argument("--blocks", type=int, default=7)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sample_bench.json"))
     a = ap.parse_args()
+    if a.feedback:
+        return feedback_main(a)
     B, N, S = a.batch, a.horizon, a.samples
     out = dict(batch=B, horizon=N, samples=S, blocks=a.blocks, dtype="float64",
                not_measured=["rocprofv3 kernel-trace durations", "fp32", "other S, N, B"])
