@@ -22,65 +22,23 @@ struct ProjP {
 
 // BLOCK = largest workgroup the instance is launched with: up to 256 threads (R <= 256, the usual case: rows = time
 // steps or N*m) a wave may use the whole register file; 1024-thread workgroups are capped at 128 VGPRs.
+// ROWS = some set of the stage carries ISLS_SET_ROW_PAR / ISLS_SET_ROW_B (p.kind[s] keeps the flag bits): every thread reads
+// its own row's block of `par` / `b` (project_rows_moving_kernel).  The shared form (project_rows_kernel) stays an instance of
+// its own: there the set operands are uniform over the wavefront (scalar loads, addresses in SGPRs); per-lane addresses for
+// everybody would make them vector loads and cost registers in a kernel that sits at its VGPR caps.  One body for both
+// (project_rows_body.inc), a kernel name each: the shared form keeps its symbol and its code.
 template <typename T, int D, int BLOCK>
 __global__ __launch_bounds__(BLOCK, (BLOCK <= 256 ? 2 : 1)) void project_rows_kernel(ProjP<T> p)
 {
-    __shared__ T red[2][16];                                   // [a / b][wavefront]
-    const int pb = blockIdx.x, r = threadIdx.x;
-    if (p.active != nullptr && p.active[pb] == 0) return;      // uniform per workgroup
-    const bool inr = r < p.R;
-    const bool row = inr && (p.row_mask == nullptr || p.row_mask[inr ? r : 0] != 0);   // rows outside the mask pass through
-    T x0[D], x[D];
-    const T *src = p.y_in + (int64_t)pb * p.in_sp + (int64_t)(inr ? r : 0) * p.in_sr;
-#pragma unroll
-    for (int j = 0; j < D; ++j) x0[j] = src[j];
-    CSet<T> sets[kMaxSets];
-#pragma unroll
-    for (int s = 0; s < kMaxSets; ++s) {
-        sets[s].kind = p.kind[s];
-        sets[s].dim = p.dim[s];
-        sets[s].A = p.A[s] ? p.A[s] + (int64_t)pb * p.A_sp[s] : nullptr;
-        sets[s].b = p.b[s] ? p.b[s] + (int64_t)pb * p.b_sp[s] : nullptr;
-        sets[s].par = p.par[s] ? p.par[s] + (int64_t)pb * p.par_sp[s] : nullptr;
-    }
-    int it = 0;
-    if (p.algorithm == ISLS_PROJ_ALG_ADMM && p.nsets == 1 && sets[0].A == nullptr) {   // direct primitive
-        T v[kMaxSetDim];
-#pragma unroll
-        for (int i = 0; i < kMaxSetDim; ++i) v[i] = i < D ? x0[i < D ? i : 0] : T(0);
-        project_primitive<T>(sets[0].kind, D, sets[0].par, v);
-#pragma unroll
-        for (int j = 0; j < D; ++j) x[j] = v[j];
-    } else {
-        const int nw = (blockDim.x + 63) >> 6, wid = r >> 6;
-        // Workgroup-wide maxima once per inner iteration: two barriers per call (partials visible; buffer free again).  The set
-        // operands stay in global memory here: staging them in LDS as sls_admm.hip does measured 7 % slower for config 4's rows
-        // (151 vs 141 us: the fp64 kernel spills more).
-        auto block_max = [&](T &a, T &b) {
-            if (!row) { a = T(0); b = T(0); }
-            a = wave_max(a);
-            b = wave_max(b);
-            if ((r & 63) == 0) { red[0][wid] = a; red[1][wid] = b; }
-            __syncthreads();
-            T ma = red[0][0], mb = red[1][0];
-            for (int w = 1; w < nw; ++w) { ma = red[0][w] > ma ? red[0][w] : ma; mb = red[1][w] > mb ? red[1][w] : mb; }
-            __syncthreads();
-            a = ma;
-            b = mb;
-        };
-        if (p.algorithm == ISLS_PROJ_ALG_DYKSTRA)
-            it = dykstra_row<T, D>(x0, p.nsets, sets, p.max_iter, p.threshold, x, block_max);
-        else if (p.algorithm == ISLS_PROJ_ALG_SOC)
-            it = project_soc_row<T, D>(x0, sets[0], p.rho, p.max_iter, p.threshold, x, block_max);
-        else
-            it = project_set_convex_row<T, D>(x0, p.nsets, sets, p.rho, p.max_iter, p.threshold, x, block_max);
-    }
-    if (inr) {
-        T *dst = p.y_out + (int64_t)pb * p.out_sp + (int64_t)r * p.out_sr;
-#pragma unroll
-        for (int j = 0; j < D; ++j) dst[j] = row ? x[j] : x0[j];
-    }
-    if (r == 0 && p.iters) p.iters[pb] = it;
+    constexpr bool ROWS = false;
+#include "project_rows_body.inc"
+}
+
+template <typename T, int D, int BLOCK>
+__global__ __launch_bounds__(BLOCK, (BLOCK <= 256 ? 2 : 1)) void project_rows_moving_kernel(ProjP<T> p)
+{
+    constexpr bool ROWS = true;
+#include "project_rows_body.inc"
 }
 
 template <typename T>
@@ -91,15 +49,21 @@ int launch_project(const isls_project_args &a, hipStream_t s)
     if (a.algorithm < ISLS_PROJ_ALG_ADMM || a.algorithm > ISLS_PROJ_ALG_SOC) return ISLS_ERR_UNSUPPORTED;
     const bool dyk = a.algorithm == ISLS_PROJ_ALG_DYKSTRA;
     const bool direct = a.algorithm == ISLS_PROJ_ALG_ADMM && a.nsets == 1 && a.sets[0].A == nullptr;
+    bool rows = false;                                         // a per-row table in this stage: the ROWS instance
     for (int i = 0; i < a.nsets; ++i) {
         const isls_cset &c = a.sets[i];
-        if (c.kind < ISLS_SET_BOX || c.kind > ISLS_SET_MULTILINEAR) return ISLS_ERR_UNSUPPORTED;
+        const int kind = c.kind & ~ISLS_SET_ROW_FLAGS;
+        if (kind < ISLS_SET_BOX || kind > ISLS_SET_MULTILINEAR) return ISLS_ERR_UNSUPPORTED;
         if (c.dim < 1 || c.dim > kMaxSetDim) return ISLS_ERR_ARG;
         if (!direct && !dyk && (!c.A || !c.b)) return ISLS_ERR_ARG;
-        if (c.kind != ISLS_SET_SOC_UNIT && !c.par) return ISLS_ERR_ARG;
+        if (kind != ISLS_SET_SOC_UNIT && !c.par) return ISLS_ERR_ARG;
         if ((direct || dyk) && c.dim != a.d) return ISLS_ERR_ARG;      // the set acts on the row itself
+        if ((c.kind & ISLS_SET_ROW_PAR) && kind == ISLS_SET_SOC_UNIT) return ISLS_ERR_ARG;   // no parameters to move
+        if ((c.kind & ISLS_SET_ROW_B) && (direct || dyk)) return ISLS_ERR_ARG;               // b is not used there
+        rows = rows || (c.kind & ISLS_SET_ROW_FLAGS) != 0;
     }
-    if (a.algorithm == ISLS_PROJ_ALG_SOC && (a.nsets != 1 || a.sets[0].kind != ISLS_SET_SOC_UNIT)) return ISLS_ERR_ARG;
+    if (a.algorithm == ISLS_PROJ_ALG_SOC && (a.nsets != 1 || (a.sets[0].kind & ~ISLS_SET_ROW_FLAGS) != ISLS_SET_SOC_UNIT))
+        return ISLS_ERR_ARG;
     if (!direct && a.max_iter < 1) return ISLS_ERR_ARG;
     if (!direct && !dyk && !(a.rho > 0)) return ISLS_ERR_ARG;
     if (a.P == 0) return ISLS_OK;
@@ -119,10 +83,12 @@ int launch_project(const isls_project_args &a, hipStream_t s)
     p.in_sp = a.in_sp; p.in_sr = a.in_sr; p.out_sp = a.out_sp; p.out_sr = a.out_sr;
     p.iters = a.iters; p.active = a.active; p.row_mask = a.row_mask;
     const int threads = ((a.R + 63) / 64) * 64;
+#define CALL_(K_, D_)                                                                                         \
+    if (threads <= 256) hipLaunchKernelGGL((K_<T, D_, 256>), dim3(a.P), dim3(threads), 0, s, p);              \
+    else if (threads <= 512) hipLaunchKernelGGL((K_<T, D_, 512>), dim3(a.P), dim3(threads), 0, s, p); /* 256 VGPRs: no spills at fp64 */ \
+    else hipLaunchKernelGGL((K_<T, D_, 1024>), dim3(a.P), dim3(threads), 0, s, p)
 #define CALL(D_)                                                                                              \
-    if (threads <= 256) hipLaunchKernelGGL((project_rows_kernel<T, D_, 256>), dim3(a.P), dim3(threads), 0, s, p); \
-    else if (threads <= 512) hipLaunchKernelGGL((project_rows_kernel<T, D_, 512>), dim3(a.P), dim3(threads), 0, s, p); /* 256 VGPRs: no spills at fp64 */ \
-    else hipLaunchKernelGGL((project_rows_kernel<T, D_, 1024>), dim3(a.P), dim3(threads), 0, s, p)
+    if (rows) { CALL_(project_rows_moving_kernel, D_); } else { CALL_(project_rows_kernel, D_); }
     switch (a.d) {
         case 1: CALL(1); break;
         case 2: CALL(2); break;
@@ -130,6 +96,7 @@ int launch_project(const isls_project_args &a, hipStream_t s)
         default: CALL(4); break;
     }
 #undef CALL
+#undef CALL_
     int rc = check_launch();
     if (rc == ISLS_OK && a.next) {                             // next stage, in place on this stage's output
         isls_project_args nx = *a.next;

@@ -280,6 +280,7 @@ EXPORTED = [f"isls_{k}_{s}" for s in ("f64", "f32") for k in
 
 
 SET_BOX, SET_SOC_UNIT, SET_SQUARE, SET_LINEAR, SET_QUADRATIC, SET_SHELL, SET_MULTILINEAR = 1, 2, 3, 4, 5, 6, 7
+SET_ROW_PAR, SET_ROW_B = 0x100, 0x200          # ISLS_SET_ROW_*: flag bits of isls_cset.kind, one par block / one b per row
 ALG_ADMM, ALG_DYKSTRA, ALG_SOC = 0, 1, 2
 MAX_ROW_DIM, MAX_SET_DIM, MAX_SETS = 4, 5, 4
 
@@ -544,6 +545,26 @@ def _dense(x, shape, name):
     if not _contiguous(x):
         raise ValueError(f"{name}: must be C-contiguous")
     return x
+
+
+def _row_par_words(kind, dim, arr, name):
+    """Words Wp of one row's parameter block of a per-row table (include/isls_hip.h ISLS_SET_ROW_PAR); SQUARE / MULTILINEAR:
+    from the q of the table, which every row must share (read from the table once, when the descriptor is built: a device
+    table is copied to the host for that; project_args_chain reads the numpy table before it is moved and passes the width
+    on as `par_words`)."""
+    fixed = {SET_BOX: 2 * dim, SET_LINEAR: 2 + dim, SET_QUADRATIC: 2, SET_SHELL: 2 + dim}
+    if kind in fixed:
+        return fixed[kind]
+    if arr.ndim not in (2, 3):
+        raise ValueError(f"{name}: with par_rows=True [Rtot, Wp] or [P, Rtot, Wp], got {tuple(arr.shape)}")
+    col = arr[..., 0]
+    col = np.asarray(col.cpu() if _is_torch(col) else col)
+    q = int(col.flat[0])
+    if np.any(col != q):
+        raise ValueError(f"{name}: every row of a per-row table must carry the same q")
+    if not 1 <= q <= MAX_SET_DIM:
+        raise ValueError(f"{name}: q = {q} outside 1 .. {MAX_SET_DIM}")
+    return 3 + q + 2 * q * q if kind == SET_SQUARE else 1 + 2 * q + q * dim
 
 
 def ff_record_elems(B, N, n, m):
@@ -825,10 +846,14 @@ class Kernels:
 
     @staticmethod
     def project_args(y_in, y_out, sets, rho=1.0, max_iter=200, threshold=1e-4, iters=None, active=None, cols=None,
-                     algorithm=ALG_ADMM, row_mask=None, next_stage=None):
+                     algorithm=ALG_ADMM, row_mask=None, next_stage=None, row0=0):
         """isls_project_args for rows y[P,R,D]; `cols=(c0, d)` projects the coordinate block [c0, c0+d) of every row
         (the rest of the row is not touched).  sets: list of dicts kind, dim, A[dim,d] | [P,dim,d], b, par (arrays of
-        the dtype of y; a leading P axis gives per-problem operands)."""
+        the dtype of y; a leading P axis gives per-problem operands).  A dict with par_rows=True carries par [Rtot,Wp] or
+        [P,Rtot,Wp], one parameter block per row (ISLS_SET_ROW_PAR; `par_words`, if given, is Wp as the caller read it from
+        the table's q, else it is read here), with b_rows=True b [Rtot,dim] or [P,Rtot,dim]
+        (ISLS_SET_ROW_B); Rtot >= row0 + R, and the call applies the rows row0 .. row0+R of those tables
+        (project_args_set_row0 moves that window)."""
         P, R, D = y_in.shape
         c0, d = cols if cols is not None else (0, D)
         if not (1 <= d <= MAX_ROW_DIM) or c0 < 0 or c0 + d > D or not (1 <= len(sets) <= MAX_SETS):
@@ -844,13 +869,40 @@ class Kernels:
         a.y_in, a.y_out = _ptr(y_in) + c0 * esz, _ptr(y_out) + c0 * esz
         a.in_sp = a.out_sp = R * D
         a.in_sr = a.out_sr = D
-        keep = []
+        keep, row_ops = [], []
+        direct = int(algorithm) == ALG_ADMM and len(sets) == 1 and sets[0].get("A") is None
         for i, st in enumerate(sets):
             c = a.sets[i]
             c.kind, c.dim = int(st["kind"]), int(st["dim"])
+            kind = c.kind                                        # the primitive; c.kind takes the flag bits below
+            if kind & ~0xff:
+                raise ValueError(f"sets[{i}].kind: a SET_* primitive; per-row tables are asked for with par_rows / b_rows")
             for name, core in (("A", (c.dim, d)), ("b", (c.dim,)), ("par", None)):
                 arr = st.get(name)
                 if arr is None:
+                    if st.get(name + "_rows"):
+                        raise ValueError(f"sets[{i}].{name}_rows without sets[{i}].{name}" +
+                                         (": SET_SOC_UNIT has no parameters" if name == "par" else ""))
+                    continue
+                if name != "A" and st.get(name + "_rows"):       # one block per row: [Rtot, W] or [P, Rtot, W]
+                    if name == "par":
+                        if kind == SET_SOC_UNIT:
+                            raise ValueError(f"sets[{i}].par_rows: SET_SOC_UNIT has no parameters")
+                        W = st.get("par_words") or _row_par_words(kind, c.dim, arr, f"sets[{i}].par")
+                    else:
+                        if direct or int(algorithm) == ALG_DYKSTRA:
+                            raise ValueError(f"sets[{i}].b_rows: b is not used by the direct form and by ALG_DYKSTRA")
+                        W = c.dim
+                    if arr.ndim not in (2, 3) or arr.shape[-1] != W or (arr.ndim == 3 and arr.shape[0] != P):
+                        raise ValueError(f"sets[{i}].{name}: with {name}_rows=True [Rtot, {W}] or [{P}, Rtot, {W}], got "
+                                         f"{tuple(arr.shape)}")
+                    if not _contiguous(arr):
+                        raise ValueError(f"sets[{i}].{name}: must be C-contiguous")
+                    Rtot = int(arr.shape[-2])
+                    c.kind |= SET_ROW_PAR if name == "par" else SET_ROW_B
+                    setattr(c, name + "_sp", Rtot * W if arr.ndim == 3 else 0)
+                    row_ops.append((i, name, _ptr(arr), W * esz, Rtot))
+                    keep.append(arr)
                     continue
                 per = arr.ndim == (len(core) + 1 if core is not None else 2)
                 if core is not None:
@@ -864,9 +916,43 @@ class Kernels:
         if next_stage is not None:                               # a ProjectArgs applied in place to this stage's output
             a.next = C.addressof(next_stage)
         a._keep = keep + [row_mask, next_stage]
+        a._row_ops, a._next_stage, a._row0 = row_ops, next_stage, 0
+        Kernels._point_rows(a, int(row0))
         a._spec = dict(sets=sets, rho=rho, max_iter=max_iter, threshold=threshold, cols=(c0, d), algorithm=int(algorithm),
-                       row_mask=row_mask, next_stage=next_stage)                                 # to rebuild elsewhere
+                       row_mask=row_mask, next_stage=next_stage, row0=int(row0))                 # to rebuild elsewhere
         return a
+
+    @staticmethod
+    def _point_rows(a, row0):
+        """the flagged operands of ONE stage -> the window of their tables that starts at row `row0`"""
+        for i, name, base, stride, Rtot in a._row_ops:
+            if row0 < 0 or row0 + a.R > Rtot:
+                raise IslsError(f"sets[{i}].{name}: rows {row0} .. {row0 + a.R} of a per-row table of {Rtot} rows; pad the table "
+                                "(repeat its last row) so that it covers the horizon at every step")
+        for i, name, base, stride, Rtot in a._row_ops:
+            setattr(a.sets[i], name, base + row0 * stride)
+        a._row0 = row0
+
+    @staticmethod
+    def project_args_set_row0(a, row0):
+        """Move the window of the per-row tables of a descriptor and of every stage behind it (`next`) to start at row `row0`:
+        a host-side update of the pointers in the descriptors -- base + row0 * Wp * element size for every flagged operand --,
+        which the library reads at each call.  No kernel, no copy, no synchronisation.  Returns the descriptor."""
+        st = a
+        while st is not None:
+            Kernels._point_rows(st, int(row0))
+            st = st._next_stage
+        return a
+
+    @staticmethod
+    def project_args_per_row(a):
+        """True if any stage of the descriptor carries a per-row table"""
+        st = a
+        while st is not None:
+            if st._row_ops:
+                return True
+            st = st._next_stage
+        return False
 
     @staticmethod
     def project_args_chain(y_in, y_out, stages, wrap=lambda a: a, iters=None, active=None):
@@ -879,10 +965,13 @@ class Kernels:
             if cs.cols != stages[0].cols:
                 raise ValueError("the stages of a ConvexSets chain must act on the same coordinate block")
             sets = [{k_: (wrap(np.ascontiguousarray(v)) if isinstance(v, np.ndarray) else v) for k_, v in st.items()} for st in cs.sets]
+            for i, (st, dst) in enumerate(zip(cs.sets, sets)):    # the block width from the host's table: no read of the device
+                if st.get("par_rows") and isinstance(st.get("par"), np.ndarray):
+                    dst["par_words"] = _row_par_words(int(st["kind"]), int(st["dim"]), st["par"], f"sets[{i}].par")
             mask = cs.row_mask(R)
             nxt = Kernels.project_args(y_in if k == 0 else y_out, y_out, sets, rho=cs.rho, max_iter=cs.max_iter, threshold=cs.threshold,
                                        iters=iters if k == 0 else None, active=active, cols=cs.cols, algorithm=cs.algorithm,
-                                       row_mask=None if mask is None else wrap(mask), next_stage=nxt)
+                                       row_mask=None if mask is None else wrap(mask), next_stage=nxt, row0=stages[0].row0)
         return nxt
 
     def project_rows(self, y_in, y_out, sets, stream=None, **kw):

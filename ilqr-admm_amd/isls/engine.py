@@ -394,6 +394,15 @@ class Engine:
         if u_sets is not None:
             self.u_lo = self.u_hi = None
 
+    def advance_sets(self, k=1, x=True, u=True):
+        """Move the window of the per-row tables of the constraint sets (ConvexSets with par_rows / b_rows) k rows on: the
+        sets follow a plan that moves through time.  A host-side update of the pointers in the isls_project_args descriptors
+        the engine holds -- the argument blocks of build_outer keep the descriptors' addresses and the library reads them at
+        each call, so they stay valid.  No kernel, no copy, no synchronisation.  x / u: which block's sets move."""
+        for desc, on in ((self.x_sets, x), (self.u_sets, u)):
+            if on and desc is not None and capi.Kernels.project_args_per_row(desc):
+                capi.Kernels.project_args_set_row0(desc, desc._row0 + int(k))
+
     # ---- single kernels -----------------------------------------------------------------------------------
     def evaluate_cost(self, out=None):
         """cost of the nominal into `out` (default: self.cost); also refreshes c0x, c0u about it"""

@@ -496,6 +496,13 @@ class iSLS(Base):
         APPLIED control only.  table_future [steps, W] or [batch, steps, W] (a costs.Custom(table=) cost): row s enters the
         window as its last row after step s; without it the last row is held.  The via-point cost of set_cost_variables is
         horizon-relative: it is reused unchanged in every window (a via point at step t stays t steps ahead of the plant).
+        A ConvexSets with per-row tables (par_rows / b_rows: moving obstacles) follows the loop by the rows it has left from its
+        row0: exactly N -- horizon-relative, it stays put as well; N + steps or more -- world time, its window moves up one row
+        per control step (pointers in the descriptors, no device work) and the object's row0 is steps further on afterwards, so
+        that a second call continues; anything between is an IslsError that asks for a padded table.  The object's row0 is
+        written once, after the last step: if the call raises on the way (an IslsError of a launch; the LinAlgError on a status row
+        comes after the last step and after row0 is written), the object still says where the call began, while the engine's descriptors stand where the loop stopped -- the next call builds its
+        descriptors from the object's row0 again, so it repeats those rows and does not skip any.
         Returns an MpcResult: x [batch, steps+1, n] (the measured states, x[:, 0] the first), u [batch, steps, m] (the applied
         controls), cost, status, admm_iters [batch, steps] (of the plan each step was taken from).  They are read once, after
         the last step; then, with no regularisation, LinAlgError("Quu not positive definite") if any status row has
@@ -511,6 +518,18 @@ class iSLS(Base):
         T_, iters, B, N, n, m = int(steps), int(iters), self.batch, self.N, self.x_dim, self.u_dim
         if T_ < 1 or iters < 1:
             raise ValueError("mpc: steps >= 1 and iters >= 1")
+        # per-row constraint sets (ConvexSets par_rows / b_rows): a table of exactly N rows from row0 is horizon-relative and
+        # stays put, like the via-point cost; one of N + steps rows or more is in world time and its window moves up one row
+        # per control step (Engine.advance_sets: pointers in the descriptors, no device work)
+        moving = {}
+        for blk, pr in (("x", project_x), ("u", project_u)):   # (checked ahead of any device work)
+            if isinstance(pr, ConvexSets) and pr.per_row:
+                left = pr.total_rows - pr.row0
+                if left != N and left < N + T_:
+                    raise capi.IslsError(f"project_{blk}: {left} rows of its per-row tables are left from row0 = {pr.row0}; {N} (the "
+                                         f"horizon: sets that stay put in every window) or at least {N + T_} (the horizon + steps: "
+                                         "sets in world time) are needed -- pad the table by repeating its last row")
+                moving[blk] = left != N
         self._sync_cost_table()
         if table_future is not None and e.cost_tab is None:
             raise capi.IslsError("table_future is the future of a costs.Custom(table=) cost's table: set such a cost_function, or move "
@@ -581,6 +600,8 @@ class iSLS(Base):
             e.mpc_step(plant_par=plant, u_lo=u_lo, u_hi=u_hi, w=None if w is None else w[s], noise_std=noise_std, seed=seed, step=s,
                        feedback=feedback, shift_z=warm_start_z, tab_next=None if table_future is None else table_future[s],
                        x_meas_out=x_log[:, s], u_out=u_log[:, s], x_next_out=x_log[:, s + 1])
+            if any(moving.values()):
+                e.advance_sets(1, x=moving.get("x", False), u=moving.get("u", False))
             if not warm_start_z:
                 for zz in (e.zx, e.zu):
                     if zz is not None:
@@ -588,6 +609,9 @@ class iSLS(Base):
         f = self._cost_function
         if getattr(f, "table", None) is not None:               # the cost object follows the window the engine holds now
             f._table = e.cost_tab.cpu().numpy().astype(np.float64)
+        for blk, pr in (("x", px), ("u", pu)):                  # ... and the sets' objects the rows consumed
+            if moving.get(blk):
+                pr.advance(T_)
         r = MpcResult(x_log.cpu().numpy(), u_log.cpu().numpy(), cost_log.cpu().numpy(), st_log.cpu().numpy(), it_log.cpu().numpy())
         self.admm_iters = r.admm_iters[:, -1].copy()
         self.cost_log.append(self.cost)

@@ -60,9 +60,15 @@ class ConvexSets:
     object and run the same iteration on the device instead (ISLS_PROJ_SETS / isls_project_rows).
 
     sets: list of dict(kind=SET_*, dim=, A=[dim,d], b=[dim], par=[...]) -- `par` as documented in include/isls_hip.h.
+
+    Moving sets: a set dict with `par_rows=True` carries one parameter block per time-step row, par [Rtot, Wp] (or
+    [P, Rtot, Wp], one table per problem), and with `b_rows=True` one offset per row, b [Rtot, dim] (or [P, Rtot, dim]);
+    Rtot >= the rows of a call (ISLS_SET_ROW_PAR / ISLS_SET_ROW_B).  A call on R rows applies rows row0 .. row0+R of the
+    tables: `row0` is the window's start, shared by every stage of a `.then` chain, `advance(k)` moves it, `total_rows`
+    is Rtot.  `iSLS.mpc` moves the window by one row per control step.
     """
 
-    def __init__(self, dim, cols, sets, rho=1.0, max_iter=200, threshold=1e-4, algorithm=ALG_ADMM, rows=None, then=None):
+    def __init__(self, dim, cols, sets, rho=1.0, max_iter=200, threshold=1e-4, algorithm=ALG_ADMM, rows=None, then=None, row0=0):
         """algorithm: ALG_ADMM = project_set_convex, ALG_DYKSTRA = project_set_convex_dykstra (sets act on the rows themselves;
         threshold is its `tol`), ALG_SOC = project_soc (one SOC set with A, b).  rows: indices (or a boolean mask) of the
         time-step rows the sets apply to, the others pass through (None = all).  then: another ConvexSets applied to the
@@ -70,6 +76,55 @@ class ConvexSets:
         self.dim, self.cols, self.sets = int(dim), (int(cols[0]), int(cols[1])), list(sets)
         self.rho, self.max_iter, self.threshold = float(rho), int(max_iter), float(threshold)
         self.algorithm, self.rows, self.then = int(algorithm), rows, then
+        self.last_iters = None                                  # inner iterations of the last host-route call of this stage
+        if int(row0) or then is None or not then.row0:          # a chain takes the window of the stage it is appended to
+            self.row0 = row0
+        else:
+            self.row0 = then.row0
+
+    @property
+    def row0(self):
+        """first row of the per-row tables that a call applies (the same for every stage of the chain)"""
+        return self._row0
+
+    @row0.setter
+    def row0(self, r):
+        if int(r) < 0:
+            raise ValueError("row0 >= 0")
+        for st in self.stages():
+            st._row0 = int(r)
+
+    def advance(self, k=1):
+        """Move the window of the per-row tables k rows on (all stages); returns self."""
+        self.row0 = self._row0 + int(k)
+        return self
+
+    @property
+    def per_row(self):
+        """True if any set of any stage carries a per-row table (par_rows / b_rows)."""
+        return any(st.get("par_rows") or st.get("b_rows") for cs in self.stages() for st in cs.sets)
+
+    @property
+    def total_rows(self):
+        """Rows Rtot of the per-row tables (the same for every table of the chain), None without per-row sets."""
+        tot = {int(np.shape(st[name])[-2]) for cs in self.stages() for st in cs.sets
+               for name, key in (("par", "par_rows"), ("b", "b_rows")) if st.get(key)}
+        if len(tot) > 1:
+            raise ValueError(f"the per-row tables of a ConvexSets must have the same number of rows, got {sorted(tot)}")
+        return tot.pop() if tot else None
+
+    def problem(self, p):
+        """The sets of problem p alone: per-problem operands ([P, ...]) sliced, shared ones as they are (the host route
+        serves one problem per call)."""
+        def one(st):
+            out = dict(st)
+            for name, nd in (("A", 2), ("b", 2 if st.get("b_rows") else 1), ("par", 2 if st.get("par_rows") else 1)):
+                if st.get(name) is not None and np.ndim(st[name]) == nd + 1:
+                    out[name] = np.asarray(st[name])[p]
+            return out
+        nxt = self.then.problem(p) if self.then is not None else None
+        return ConvexSets(self.dim, self.cols, [one(st) for st in self.sets], rho=self.rho, max_iter=self.max_iter,
+                          threshold=self.threshold, algorithm=self.algorithm, rows=self.rows, then=nxt, row0=self._row0)
 
     def row_mask(self, R):
         """int32 [R] mask of the rows this stage touches, or None for all rows."""
@@ -87,7 +142,51 @@ class ConvexSets:
         return out
 
     @staticmethod
-    def _primitive(st):
+    def _primitive_rows(st, rows):
+        """The primitive with row i of its argument projected on the set of table row rows[i]: the reference's closure over
+        an array of per-row parameters, by numpy broadcasting."""
+        kind, d = st["kind"], st["dim"]
+        par = np.asarray(st["par"], dtype=np.float64)
+        if par.ndim != 2:
+            raise ValueError("the host route serves one problem per call: take ConvexSets.problem(p) of per-problem tables")
+        T = par[rows]                                           # [R, Wp]
+        if kind == SET_BOX:
+            return lambda v: project_bound(v, T[:, :d], T[:, d:2 * d])
+        if kind == SET_LINEAR:
+            return lambda v: project_linear_batch(v, T[:, 2:], T[:, 0], T[:, 1])
+        if kind == SET_QUADRATIC:
+            return lambda v: project_quadratic_batch(v, T[:, 0], T[:, 1])
+        if kind == SET_SHELL:
+            return lambda v: project_quadratic_batch(v - T[:, 2:], T[:, 0], T[:, 1]) + T[:, 2:]
+        if kind not in (SET_SQUARE, SET_MULTILINEAR):
+            raise ValueError("SET_SOC_UNIT has no parameters: par_rows does not apply")
+        q = int(par[0, 0])
+        if np.any(par[:, 0] != q):
+            raise ValueError("every row of a per-row SET_SQUARE / SET_MULTILINEAR table must have the same q")
+        if kind == SET_MULTILINEAR:
+            return lambda v: np.stack([project_multilinear(r, t[1 + 2 * q:].reshape(q, -1), t[1:1 + q], t[1 + q:1 + 2 * q])
+                                       for r, t in zip(np.atleast_2d(v), T)])
+        l, u, c = T[:, 1], T[:, 2], T[:, 3:3 + q]
+        Wt, Wit = T[:, 3 + q:3 + q + q * q], T[:, 3 + q + q * q:3 + q + 2 * q * q]
+        fixed = bool(np.all(Wt == Wt[:1]) and np.all(Wit == Wit[:1]))     # the keep-out helpers: only the centres move
+
+        def square(v):
+            out = np.array(v, dtype=np.float64, copy=True)
+            y = out[:, :q] - c
+            w = y @ Wt[0].reshape(q, q).T if fixed else np.einsum("rj,rij->ri", y, Wt.reshape(-1, q, q))
+            z = w.copy()
+            j = np.argmax(np.abs(w), axis=-1)
+            low = np.nonzero(np.abs(w).max(axis=-1) < l)[0]
+            z[low, j[low]] = l[low] * np.sign(w[low, j[low]])
+            z = np.clip(z, -u[:, None], u[:, None])
+            out[:, :q] = (z @ Wit[0].reshape(q, q).T if fixed else np.einsum("rj,rij->ri", z, Wit.reshape(-1, q, q))) + c
+            return out
+        return square
+
+    @staticmethod
+    def _primitive(st, rows=None):
+        if st.get("par_rows"):
+            return ConvexSets._primitive_rows(st, rows)
         kind, par = st["kind"], st.get("par")
         if kind == SET_BOX:
             d = st["dim"]
@@ -119,32 +218,75 @@ class ConvexSets:
         c0, d = self.cols
         sel = slice(None) if self.rows is None else np.flatnonzero(self.row_mask(y.shape[0]))
         arg = y[sel, c0:c0 + d].copy()
-        prims = [self._primitive(s) for s in self.sets]
+        rows, tot = np.arange(self._row0, self._row0 + y.shape[0])[sel], self.total_rows
+        if tot is not None and self._row0 + y.shape[0] > tot:
+            raise ValueError(f"rows {self._row0} .. {self._row0 + y.shape[0]} of per-row tables of {tot} rows")
+        prims = [self._primitive(s, rows) for s in self.sets]
+
+        def offset(s):                                          # [dim], or [R, dim]: one offset per row (b_rows)
+            b = np.asarray(s["b"], dtype=np.float64)
+            if not s.get("b_rows"):
+                return b
+            if b.ndim != 2:
+                raise ValueError("the host route serves one problem per call: take ConvexSets.problem(p) of per-problem tables")
+            return b[rows]
+        info = {}
         if self.algorithm == ALG_DYKSTRA:
-            blk = project_set_convex_dykstra(arg, prims, max_iter=self.max_iter, tol=self.threshold)
+            blk = project_set_convex_dykstra(arg, prims, max_iter=self.max_iter, tol=self.threshold, info=info)
         elif self.algorithm == ALG_SOC:
-            blk = project_soc(arg, np.asarray(self.sets[0]["A"], dtype=np.float64), np.asarray(self.sets[0]["b"], dtype=np.float64),
-                              rho=self.rho, max_iter=self.max_iter, tol=self.threshold)
+            blk = project_soc(arg, np.asarray(self.sets[0]["A"], dtype=np.float64), offset(self.sets[0]),
+                              rho=self.rho, max_iter=self.max_iter, tol=self.threshold, info=info)
         else:
             blk = project_set_convex(arg, [np.asarray(s["A"], dtype=np.float64) for s in self.sets],
-                                     [np.asarray(s["b"], dtype=np.float64) for s in self.sets], projections=prims, rho=self.rho,
-                                     max_iter=self.max_iter, threshold=self.threshold)
+                                     [offset(s) for s in self.sets], projections=prims, rho=self.rho,
+                                     max_iter=self.max_iter, threshold=self.threshold, info=info)
+        self.last_iters = info["iters"]
         y[sel, c0:c0 + d] = np.atleast_2d(blk)
         out = y.reshape(np.shape(flat))
         return self.then(out) if self.then is not None else out
 
 
+def refuse_per_row(project, who):
+    """ValueError if `project` is a ConvexSets with per-row tables: `who` works on rows that are not time steps."""
+    if isinstance(project, ConvexSets) and project.per_row:
+        raise ValueError(f"{who} does not serve per-row constraint sets (par_rows / b_rows): its rows are not the time steps of a "
+                         "plan; they are served by ilqr_admm, mpc, ADMM_LQT_DP and project_rows")
+
+
+def _moving_centres(centres, q, name):
+    """centres [k, q] -> (array, False); [Rtot, k, q] or [B, Rtot, k, q] (a centre per time-step row) -> (array, True)"""
+    c = np.asarray(centres, dtype=np.float64)
+    if c.ndim not in (2, 3, 4) or c.shape[-1] != q:
+        raise ValueError(f"{name}: centres [k, {q}], [Rtot, k, {q}] (moving) or [B, Rtot, k, {q}] (moving, per problem), got {c.shape}")
+    return c, c.ndim > 2
+
+
+def _row_table(head, c_i, tail=()):
+    """per-row parameter table [..., Rtot, Wp]: the fixed words `head`, the centres c_i [..., Rtot, q], the fixed words `tail`"""
+    lead = c_i.shape[:-1]
+    parts = [np.broadcast_to(np.asarray(head, dtype=np.float64), lead + (len(head),)), c_i]
+    if len(tail):
+        parts.append(np.broadcast_to(np.asarray(tail, dtype=np.float64), lead + (len(tail),)))
+    return np.ascontiguousarray(np.concatenate(parts, axis=-1))
+
+
 def keepout_rectangles(dim, centres, sizes, angle, margin=0.5, upper=1e5, rho=10.0, max_iter=15, threshold=1e-3):
     """State constraint of notebooks/Car/Iterative LQR with state constraints.ipynb cell 18: stay outside rotated
     rectangles (width, length = sizes[i] + margin, rotated by `angle`, centred at centres[i]) in the first two
-    coordinates of a `dim`-vector."""
+    coordinates of a `dim`-vector.  centres [k, 2]; [Rtot, k, 2] or [B, Rtot, k, 2]: rectangles that move, one centre per
+    time-step row (per-row tables, see ConvexSets); sizes and angle stay fixed."""
     Rm = np.array([[np.cos(angle), -np.sin(angle)], [np.sin(angle), np.cos(angle)]])
+    cs, moving = _moving_centres(centres, 2, "keepout_rectangles")
     sets = []
-    for c, a in zip(np.asarray(centres, dtype=np.float64), np.asarray(sizes, dtype=np.float64)):
+    for i, a in enumerate(np.asarray(sizes, dtype=np.float64)):
         a_safe = a + margin
         W = np.diag(a_safe[0] / a_safe) @ Rm.T
-        par = np.concatenate([[2, a_safe[0] / 2, upper], c, W.ravel(), np.linalg.inv(W).ravel()])
-        sets.append(dict(kind=SET_SQUARE, dim=dim, A=np.eye(dim), b=np.zeros(dim), par=par))
+        head, tail = [2, a_safe[0] / 2, upper], np.concatenate([W.ravel(), np.linalg.inv(W).ravel()])
+        if moving:
+            sets.append(dict(kind=SET_SQUARE, dim=dim, A=np.eye(dim), b=np.zeros(dim), par=_row_table(head, cs[..., i, :], tail),
+                             par_rows=True))
+        else:
+            sets.append(dict(kind=SET_SQUARE, dim=dim, A=np.eye(dim), b=np.zeros(dim), par=np.concatenate([head, cs[i], tail])))
     return ConvexSets(dim, (0, dim), sets, rho=rho, max_iter=max_iter, threshold=threshold)
 
 
@@ -153,11 +295,20 @@ def spherical_keepout(dim, centres, radii, margin=1.1, upper=1e2, q=None, admm_i
     """State constraint of notebooks/Double integrator/LQR and SLS with spherical obstacle avoidance.ipynb cell 12: keep the
     first q coordinates (default: all) of every row outside the balls |y - c_i| < margin r_i -- project_set_convex over the
     shells (margin r_i)^2 / 2 <= |y - c_i|^2 / 2 <= upper, then project_set_convex_dykstra over the same shells, both on the
-    device (ISLS_SET_SHELL, ISLS_PROJ_ALG_ADMM then ISLS_PROJ_ALG_DYKSTRA)."""
+    device (ISLS_SET_SHELL, ISLS_PROJ_ALG_ADMM then ISLS_PROJ_ALG_DYKSTRA).  centres [k, q]; [Rtot, k, q] or [B, Rtot, k, q]:
+    balls that move, one centre per time-step row (per-row tables, see ConvexSets)."""
     q = dim if q is None else int(q)
-    mk = lambda: [dict(kind=SET_SHELL, dim=q, A=np.eye(q), b=np.zeros(q),                       # noqa: E731
-                       par=np.concatenate([[0.5 * (margin * r) ** 2, upper], np.asarray(c, dtype=np.float64)]))
-                  for c, r in zip(centres, radii)]
+    cs, moving = _moving_centres(centres, q, "spherical_keepout")
+
+    def mk():
+        out = []
+        for i, r in enumerate(radii):
+            head = [0.5 * (margin * r) ** 2, upper]
+            if moving:
+                out.append(dict(kind=SET_SHELL, dim=q, A=np.eye(q), b=np.zeros(q), par=_row_table(head, cs[..., i, :]), par_rows=True))
+            else:
+                out.append(dict(kind=SET_SHELL, dim=q, A=np.eye(q), b=np.zeros(q), par=np.concatenate([head, cs[i]])))
+        return out
     dyk = ConvexSets(dim, (0, q), mk(), max_iter=dykstra_iter, threshold=dykstra_tol, algorithm=ALG_DYKSTRA)
     return ConvexSets(dim, (0, q), mk(), rho=1.0, max_iter=admm_iter, threshold=admm_threshold, then=dyk)
 
@@ -351,25 +502,32 @@ def _consensus_residual_loop(update, max_iter, threshold, rel=1e-5):
             if abs(prev_p - p) / (prev_p + 1e-30) < rel and abs(prev_d - d) / (prev_d + 1e-30) < rel:
                 break
         prev_p, prev_d = p, d
+    return min(j + 1, max_iter) if max_iter > 0 else 0
 
 
-def project_set_convex(x0, As=[], bs=[], projections=[], rho=1, max_iter=200, threshold=1e-4, verbose=False):
+def _col(b):
+    """offset b of A x + b against the [dim, rows] layout of the inner solvers: [dim], or [rows, dim] with one offset per row"""
+    return b[:, None] if b.ndim == 1 else b.T
+
+
+def project_set_convex(x0, As=[], bs=[], projections=[], rho=1, max_iter=200, threshold=1e-4, verbose=False, info=None):
     """Projection onto the intersection {x : A_i x + b_i in C_i} by consensus ADMM (isls/projections.py:289-374):
-    x = (I + rho sum A_i'A_i)^-1 (x0 + rho sum A_i'(z_i - b_i - lmb_i)); z_i = P_i(A_i x + b_i + lmb_i); lmb_i += A_i x + b_i - z_i."""
+    x = (I + rho sum A_i'A_i)^-1 (x0 + rho sum A_i'(z_i - b_i - lmb_i)); z_i = P_i(A_i x + b_i + lmb_i); lmb_i += A_i x + b_i - z_i.
+    b_i: [dim_i], or [rows, dim_i] with one offset per row of x0.  info: a dict that receives "iters", the iterations run."""
     X0 = (x0[None] if x0.ndim == 1 else x0).T
     single = X0.shape[1] == 1                 # the reference squeezes whenever nb_size == 1, also for a [1, d] input (projections.py:371-374)
     x = X0.copy()
-    z = [A @ x + b[:, None] for A, b in zip(As, bs)]
+    z = [A @ x + _col(b) for A, b in zip(As, bs)]
     lmb = [np.zeros_like(zi) for zi in z]
     lhs_inv = np.linalg.inv(np.eye(X0.shape[0]) + rho * sum(A.T @ A for A in As))
     state = {"x": x}
 
     def update():
-        rhs = sum(A.T @ (zi - b[:, None] - li) for A, b, zi, li in zip(As, bs, z, lmb))
+        rhs = sum(A.T @ (zi - _col(b) - li) for A, b, zi, li in zip(As, bs, z, lmb))
         xk = lhs_inv @ (X0 + rho * rhs)
         p_max = d_max = 0.0
         for i, (A, b, P) in enumerate(zip(As, bs, projections)):
-            Axb = A @ xk + b[:, None]
+            Axb = A @ xk + _col(b)
             z_new = P((Axb + lmb[i]).T).T
             prim = Axb - z_new
             dual = rho * A.T @ (z_new - z[i])
@@ -380,13 +538,16 @@ def project_set_convex(x0, As=[], bs=[], projections=[], rho=1, max_iter=200, th
         state["x"] = xk
         return p_max, d_max
 
-    _consensus_residual_loop(update, max_iter, threshold)
+    iters = _consensus_residual_loop(update, max_iter, threshold)
+    if info is not None:
+        info["iters"] = iters
     out = state["x"].T
     return out[0] if single else out
 
 
-def project_soc(z0, A, b, rho=1e0, max_iter=100, tol=1e-5, verbose=False):
-    """Projection onto {z : A z + b in SOC} by ADMM (isls/projections.py:163-234)."""
+def project_soc(z0, A, b, rho=1e0, max_iter=100, tol=1e-5, verbose=False, info=None):
+    """Projection onto {z : A z + b in SOC} by ADMM (isls/projections.py:163-234).  b: [dim], or [rows, dim] with one offset
+    per row of z0; info: a dict that receives "iters"."""
     single = z0.ndim == 1
     Z0 = (z0[None] if single else z0).T
     z = Z0.copy()
@@ -396,21 +557,23 @@ def project_soc(z0, A, b, rho=1e0, max_iter=100, tol=1e-5, verbose=False):
 
     def update():
         zk = state["z"]
-        x = project_soc_unit((A @ zk + b[:, None] + lmb).T).T
-        z_new = lhs_inv @ (Z0 + rho * A.T @ (-b[:, None] + x - lmb))
-        prim = A @ z_new + b[:, None] - x
+        x = project_soc_unit((A @ zk + _col(b) + lmb).T).T
+        z_new = lhs_inv @ (Z0 + rho * A.T @ (-_col(b) + x - lmb))
+        prim = A @ z_new + _col(b) - x
         dual = rho * (z_new - zk)
         lmb[...] = lmb + prim
         state["z"] = z_new
         return float(np.max(np.linalg.norm(prim, axis=0))), float(np.max(np.linalg.norm(dual, axis=0)))
 
-    _consensus_residual_loop(update, max_iter, tol)
+    iters = _consensus_residual_loop(update, max_iter, tol)
+    if info is not None:
+        info["iters"] = iters
     out = state["z"].T
     return out[0] if single else out
 
 
-def project_set_convex_dykstra(x0, projections=[], max_iter=200, tol=1e-4, verbose=False):
-    """Dykstra's alternating projections (isls/projections.py:465-504)."""
+def project_set_convex_dykstra(x0, projections=[], max_iter=200, tol=1e-4, verbose=False, info=None):
+    """Dykstra's alternating projections (isls/projections.py:465-504).  info: a dict that receives "iters", the passes run."""
     single = x0.ndim == 1
     u = (x0[None] if single else x0).copy()
     z = np.zeros((len(projections),) + u.shape)
@@ -423,4 +586,6 @@ def project_set_convex_dykstra(x0, projections=[], max_iter=200, tol=1e-4, verbo
             z[i] = u - (prev_u - prev_z)
             cI += np.linalg.norm(prev_z - z[i], axis=-1) ** 2
         k += 1
+    if info is not None:
+        info["iters"] = k
     return u

@@ -19,7 +19,7 @@ import torch
 
 from . import _capi as capi
 from .engine import _stream_ptr
-from .projections import ConvexSets
+from .projections import ConvexSets, refuse_per_row
 
 
 def _row_projection(project, C):
@@ -27,6 +27,7 @@ def _row_projection(project, C):
     if project is False or project is None:
         return None
     if isinstance(project, ConvexSets):
+        refuse_per_row(project, "the SLS iteration over the feedback columns (isls_admm, ADMM_SLS)")
         if project.dim != C or project.cols != (0, C):
             raise ValueError(f"the projection acts on rows [d, phi] of dimension {C}; this ConvexSets acts on "
                              f"columns {project.cols} of rows of dimension {project.dim}")

@@ -30,7 +30,7 @@ from . import _capi as capi
 from . import sls_dense as dense
 from .base import Base
 from .models import LTI
-from .projections import Box, ConvexSets
+from .projections import Box, ConvexSets, refuse_per_row
 
 
 class SLS(Base):
@@ -344,6 +344,8 @@ class SLS(Base):
         the iteration runs over the feedback columns with the Riccati kernels instead.  Returns du, phi_u[, logs].
         `rel_tol` (not in the reference's signature) is the threshold of its second stop rule, hard-coded to 1e-2 there
         (sls.py:426); 0 disables it, which pins the iteration count (that rule fires on rounding noise)."""
+        for pr in (project_x, project_u):
+            refuse_per_row(pr, "SLS.ADMM_SLS")
         has_rho_x = rho_x is not None and np.any(np.asarray(rho_x) != 0)
         if project_x or has_rho_x or not isinstance(project_u, ConvexSets):
             # state constraints, state weights or projections given as the reference's callables: ADMM over the feedback

@@ -400,6 +400,23 @@ int isls_rollout_ls_f32(const isls_rollout_args *a, void *stream);
                                 keep-out shells of notebooks/Double integrator/...spherical obstacle avoidance.ipynb cell 12  */
 #define ISLS_SET_MULTILINEAR 7 /* par: q, l[q], u[q], M[q*dim]: l <= M y <= u, y - M'(M M')^-1 (M y - clip(M y, l, u))
                                   (project_multilinear, projections.py:46-61); q <= ISLS_MAX_SET_DIM                           */
+/* Moving sets: flag bits ORed into isls_cset.kind (isls_project_rows_* and what runs through it: isls_admm_update_*,
+ * the outer driver, the column passes).  The rows of a problem are time steps there, and a flagged operand holds one block
+ * per row, back to back, so that a keep-out region can move along the horizon:
+ *   ISLS_SET_ROW_PAR  the block of row r of problem p starts at par + p*par_sp + r*Wp, Wp = words of the primitive's
+ *                     parameter block as listed above (BOX 2 dim, SQUARE 3 + q + 2 q^2, LINEAR 2 + dim, QUADRATIC 2,
+ *                     SHELL 2 + dim, MULTILINEAR 1 + 2 q + q dim).  For SQUARE and MULTILINEAR Wp is taken from row 0's q:
+ *                     every row must carry the same q.  ISLS_ERR_ARG on ISLS_SET_SOC_UNIT, which has no parameters.
+ *   ISLS_SET_ROW_B    b holds one [dim] offset per row, at b + p*b_sp + r*dim.  ISLS_PROJ_ALG_ADMM and ISLS_PROJ_ALG_SOC;
+ *                     ISLS_ERR_ARG in the direct form and under ISLS_PROJ_ALG_DYKSTRA, where b is not used.
+ * A stays per call or per problem.  par_sp == 0 / b_sp == 0: one table shared by all problems.  A table has at least R rows;
+ * a caller that follows a longer table through time moves the pointer by whole rows between calls.  Additive within ABI
+ * version 107: no struct changes, and a library built before the flags existed rejects a flagged kind with
+ * ISLS_ERR_UNSUPPORTED (kind out of range) -- a loud failure, never a misread of the table as one block.
+ * isls_sls_admm_* returns ISLS_ERR_UNSUPPORTED for a flagged set. */
+#define ISLS_SET_ROW_PAR 0x100
+#define ISLS_SET_ROW_B 0x200
+#define ISLS_SET_ROW_FLAGS (ISLS_SET_ROW_PAR | ISLS_SET_ROW_B)
 
 /* algorithm of isls_project_rows_* over the sets of a call */
 #define ISLS_PROJ_ALG_ADMM 0     /* project_set_convex: consensus ADMM over A_i y + b_i in C_i   (projections.py:289-374)       */
@@ -410,10 +427,10 @@ int isls_rollout_ls_f32(const isls_rollout_args *a, void *stream);
                                     kind ISLS_SET_SOC_UNIT with A [dim,d], b [dim]; threshold = tol                             */
 
 typedef struct isls_cset {
-    int32_t kind, dim;          /* primitive and dimension of A y + b                               */
+    int32_t kind, dim;          /* primitive (ISLS_SET_*, | ISLS_SET_ROW_PAR / ISLS_SET_ROW_B) and dimension of A y + b */
     const void *A;              /* [dim, d] row-major; NULL only for the direct form                */
-    const void *b;              /* [dim]                                                            */
-    const void *par;            /* primitive parameters                                             */
+    const void *b;              /* [dim]; with ISLS_SET_ROW_B [rows, dim]                           */
+    const void *par;            /* primitive parameters; with ISLS_SET_ROW_PAR [rows, Wp]           */
     int64_t A_sp, b_sp, par_sp; /* element strides between problems (0 = shared by all problems)    */
 } isls_cset;
 
@@ -496,7 +513,9 @@ typedef struct isls_sls_admm_args {
     const void *Linv;
     const void *r_side;
     const void *rr;
-    isls_project_args proj;   /* nsets, sets, rho, max_iter, threshold are used (d = D)          */
+    isls_project_args proj;   /* nsets, sets, rho, max_iter, threshold are used (d = D); a set with ISLS_SET_ROW_PAR /
+                               * ISLS_SET_ROW_B is ISLS_ERR_UNSUPPORTED: the kernel stages one block per set in LDS, and its
+                               * rows are not time steps */
     void *x_u;                /* [P,R,D] out: du = x_u[:,:,0], phi_u[:, :p] = x_u[:,:,1:]         */
     void *z, *lmb;            /* [P,R,D] out, nullable                                            */
     void *logs;               /* nullable                                                         */
