@@ -274,7 +274,7 @@ __global__ __launch_bounds__(64) void mpc_step_kernel(MpcP<T> p)
                         if (c + GL * j < m) s.u[(int64_t)t * m + c + GL * j] = out[n + c + GL * j];
                 }
                 if (t < N - 1) {
-                    mdl.step(x, u, xn);
+                    model_step_at<MODEL>(mdl, x, u, t, xn);   // (a table model: row t of the window, a global read)
 #pragma unroll
                     for (int j = 0; j < NX; ++j) x[j] = j < n ? xn[j] : T(0);
                 }

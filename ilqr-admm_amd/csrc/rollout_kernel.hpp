@@ -101,6 +101,34 @@ __host__ __device__ constexpr int ro_tab_rec(int ntab) { return ntab > 0 ? ntab 
 // the slot's model words with a table cost: the model's own (even), then the two side records
 __host__ __device__ constexpr int ro_mdl_words(int mdlw, int ntab) { return ntab > 0 ? mdlw + (mdlw & 1) + 2 * ro_tab_rec(ntab) : mdlw; }
 
+// ---- a user model with a per-step table (isls.models.Custom(table=)) --------------------------------
+// A run-time compiled program whose user model reads a table of NTAB words per step defines ISLS_USER_MODEL_NTAB before it includes
+// this header.  The table lies behind the model's parameters in the buffer `model_par` names, [par | row 0 | ... | row N-1] per
+// trajectory (or once, batch stride 0), and Model<T, NX, NU, ISLS_MODEL_USER> (user_model.hpp) then has `rows` (row 0 in global
+// memory) and step_row(x, u, row, xn).  In the search the row of step t arrives as the cost table's does: a register ring of its
+// own, D steps ahead, and two side records of its own in LDS (below the cost table's), read back as broadcasts by `step`.  The
+// winner's replays, whose lanes stand at different steps, read their row from global memory.  The library's own build: 0, no code.
+#ifdef ISLS_USER_MODEL_NTAB
+constexpr int kRoModelTab = ISLS_USER_MODEL_NTAB;
+#else
+constexpr int kRoModelTab = 0;
+#endif
+template <int MODEL>
+constexpr int ro_model_ntab = MODEL == ISLS_MODEL_USER ? kRoModelTab : 0;
+// one step of `m` with the row the caller holds (LDS or global) / with row t of the model's own table in global memory
+template <int MODEL, typename M, typename T, int NX, int NU>
+__device__ __forceinline__ void model_step_row(const M &m, const T (&x)[NX], const T (&u)[NU], const T *row, T (&xn)[NX])
+{
+    if constexpr (ro_model_ntab<MODEL> > 0) m.step_row(x, u, row, xn);
+    else m.step(x, u, xn);
+}
+template <int MODEL, typename M, typename T, int NX, int NU>
+__device__ __forceinline__ void model_step_at(const M &m, const T (&x)[NX], const T (&u)[NU], int t, T (&xn)[NX])
+{
+    if constexpr (ro_model_ntab<MODEL> > 0) m.step_row(x, u, m.rows + (int64_t)t * ro_model_ntab<MODEL>, xn);
+    else m.step(x, u, xn);
+}
+
 // ---- built-in forward models -------------------------------------------------
 // sin_cos: isls_common.hpp
 template <typename T, int NX, int NU, int MODEL>
@@ -443,7 +471,7 @@ __device__ __forceinline__ void ro_replay(const Model<T, NX, NU, MODEL> &model, 
                     for (int r = 0; r < RPL; ++r) uo[i * NU + r] = accept ? uown[r] : uhm * o.uh[r];
                 }
                 T xn[NX];
-                model.step(xw, u, xn);
+                model_step_at<MODEL>(model, xw, u, t < N ? t : N - 1, xn);   // (a table model: its row by a global read)
 #pragma unroll
                 for (int j = 0; j < NX; ++j) xw[j] = xn[j];
             }
@@ -473,7 +501,7 @@ __device__ __forceinline__ void ro_xreplay(const Model<T, NX, NU, MODEL> &model,
 #pragma unroll
             for (int j = 0; j < NX; ++j) stage[t * NX + j] = xw[j];
         }
-        model.step(xw, u, xn);
+        model_step_at<MODEL>(model, xw, u, tt, xn);
 #pragma unroll
         for (int j = 0; j < NX; ++j) xw[j] = xn[j];
     }
@@ -496,9 +524,11 @@ __global__ __launch_bounds__(64, OCC) void rollout_kernel(RoP<T> p)
     const int GL = L > 8 ? L : 8, TPW = p.tpw;
     const bool stage_on = p.stage_on != 0;
     constexpr int NTAB = RoCost<T, NX, NU, kRoUserCost>::NTAB, TABP = ro_tab_rec(NTAB);   // a user cost's table row, its side record
-    constexpr int MDLW = ro_mdl_words(Model<T, NX, NU, MODEL>::LDS_WORDS, NTAB);
+    constexpr int MTAB = ro_model_ntab<MODEL>, MTABP = ro_tab_rec(MTAB);                  // a user model's table row, its side record
+    constexpr int MDLW = ro_mdl_words(ro_mdl_words(Model<T, NX, NU, MODEL>::LDS_WORDS, MTAB), NTAB);
     // single-word loads per lane and step that cover the row in the narrowest slot of the occupancy class (16 lanes / 8 lanes)
     constexpr int TL = NTAB > 0 ? (NTAB + (OCC == 2 ? 16 : 8) - 1) / (OCC == 2 ? 16 : 8) : 1;
+    constexpr int TLM = MTAB > 0 ? (MTAB + (OCC == 2 ? 16 : 8) - 1) / (OCC == 2 ? 16 : 8) : 1;
     const int SLOT = LY::slot_elems(L, GL, NSEG, N, stage_on, MDLW);
     const int lane = threadIdx.x;
     // lanes beyond TPW*GL join the last slot as extra idle candidate lanes (c >= GL): they help nobody and
@@ -515,6 +545,7 @@ __global__ __launch_bounds__(64, OCC) void rollout_kernel(RoP<T> p)
     T *c_aug = slot, *c_pln = c_aug + GL, *mdl = c_pln + GL;
     T *recs = static_cast<T *>(__builtin_assume_aligned(mdl + LY::mdl_elems(MDLW), W == 2 ? 2 * sizeof(T) : sizeof(T)));
     T *const tabrec = recs - 2 * TABP;                         // the table row's side records [2][TABP], right below the records
+    T *const mtabrec = tabrec - 2 * MTABP;                     // the model's: [2][MTABP], below the cost's
     T *ck = recs + 2 * RECP;
     T *stage = recs;                                           // winner trajectory: x over the dead records + checkpoints,
     const int uoff = p.u_off;                                  // u behind them (recorded during the search)
@@ -573,6 +604,12 @@ __global__ __launch_bounds__(64, OCC) void rollout_kernel(RoP<T> p)
     Model<T, NX, NU, MODEL> model;
     model.load(p.par + (int64_t)bb * p.par_sb, mdl, c < GL ? c : 0, GL);
     slot_sync();
+    // the model's table row: load j of a lane fetches word c + GL * j of it; lanes past its end repeat word 0 and store nothing
+    const char *pm[TLM];
+    if constexpr (MTAB > 0) {
+#pragma unroll
+        for (int j = 0; j < TLM; ++j) pm[j] = reinterpret_cast<const char *>(model.rows + ((c < GL && c + GL * j < MTAB) ? c + GL * j : 0));
+    }
     const T *Qtab = p.Qtab + (int64_t)bb * p.Qtab_sb, *ztab = p.ztab + (int64_t)bb * p.ztab_sb;
     const T ustd = p.u_std;
     // pseudo-Huber cost model: compiled into the kernels of the Tassa model only, selected at run time
@@ -633,6 +670,8 @@ __global__ __launch_bounds__(64, OCC) void rollout_kernel(RoP<T> p)
         Vec ra[D][JM], rb[D];
         T rt[D][TL];                                           // the table row's ring (NTAB > 0)
         constexpr int64_t stpt = (int64_t)NTAB * (int64_t)sizeof(T);
+        T rm[D][TLM];                                          // the model's table row: a ring of its own (MTAB > 0)
+        constexpr int64_t stpm = (int64_t)MTAB * (int64_t)sizeof(T);
         const char *ca[JM], *cb;
 #pragma unroll
         for (int j = 0; j < JM; ++j) ca[j] = reinterpret_cast<const char *>(pa[j]);
@@ -648,6 +687,10 @@ __global__ __launch_bounds__(64, OCC) void rollout_kernel(RoP<T> p)
 #pragma unroll
                 for (int j = 0; j < TL; ++j) rt[d][j] = *reinterpret_cast<const T *>(pt[j]);
             }
+            if constexpr (MTAB > 0) {
+#pragma unroll
+                for (int j = 0; j < TLM; ++j) rm[d][j] = *reinterpret_cast<const T *>(pm[j]);
+            }
             const int64_t adv = tf < N - 1 ? 1 : 0;
             tf += (int)adv;
 #pragma unroll
@@ -656,6 +699,10 @@ __global__ __launch_bounds__(64, OCC) void rollout_kernel(RoP<T> p)
             if constexpr (NTAB > 0) {
 #pragma unroll
                 for (int j = 0; j < TL; ++j) pt[j] += adv * stpt;
+            }
+            if constexpr (MTAB > 0) {
+#pragma unroll
+                for (int j = 0; j < TLM; ++j) pm[j] += adv * stpm;
             }
             __builtin_amdgcn_sched_barrier(0);                  // keep the issue order = consumption order (vmcnt is in-order)
         }
@@ -681,6 +728,10 @@ __global__ __launch_bounds__(64, OCC) void rollout_kernel(RoP<T> p)
             _Pragma("unroll") for (int j = 0; j < TL; ++j)                                                                  \
                 if (c < GL && c + GL * j < NTAB) tabrec[d * TABP + c + GL * j] = rt[d][j];                                  \
         }                                                                                                                   \
+        if constexpr (MTAB > 0) {                             /* the model's row of step t into its side record */          \
+            _Pragma("unroll") for (int j = 0; j < TLM; ++j)                                                                 \
+                if (c < GL && c + GL * j < MTAB) mtabrec[d * MTABP + c + GL * j] = rm[d][j];                                \
+        }                                                                                                                   \
         slot_sync();                                          /* record(t) visible to the slot */                           \
         if (!TAILF || t + D < N) {                            /* refill this ring entry with step t + D (the tail skips */  \
             _Pragma("unroll") for (int j = 0; j < JM; ++j)    /* fetches nobody consumes: the wave would wait for them)  */  \
@@ -688,6 +739,9 @@ __global__ __launch_bounds__(64, OCC) void rollout_kernel(RoP<T> p)
             rb[d] = ISLS_RO_LD(cb);                                                                                         \
             if constexpr (NTAB > 0) {                                                                                       \
                 _Pragma("unroll") for (int j = 0; j < TL; ++j) rt[d][j] = *reinterpret_cast<const T *>(pt[j]);              \
+            }                                                                                                               \
+            if constexpr (MTAB > 0) {                                                                                       \
+                _Pragma("unroll") for (int j = 0; j < TLM; ++j) rm[d][j] = *reinterpret_cast<const T *>(pm[j]);             \
             }                                                                                                               \
             if (TAILF) {                                                                                                    \
                 const int64_t adv = tf < N - 1 ? 1 : 0;                                                                     \
@@ -697,12 +751,18 @@ __global__ __launch_bounds__(64, OCC) void rollout_kernel(RoP<T> p)
                 if constexpr (NTAB > 0) {                                                                                   \
                     _Pragma("unroll") for (int j = 0; j < TL; ++j) pt[j] += adv * stpt;                                     \
                 }                                                                                                           \
+                if constexpr (MTAB > 0) {                                                                                   \
+                    _Pragma("unroll") for (int j = 0; j < TLM; ++j) pm[j] += adv * stpm;                                    \
+                }                                                                                                           \
             } else {                                                                                                        \
                 ++tf;                                                                                                       \
                 _Pragma("unroll") for (int j = 0; j < JM; ++j) ca[j] += stp[j];                                             \
                 cb += stpb;                                                                                                 \
                 if constexpr (NTAB > 0) {                                                                                   \
                     _Pragma("unroll") for (int j = 0; j < TL; ++j) pt[j] += stpt;                                           \
+                }                                                                                                           \
+                if constexpr (MTAB > 0) {                                                                                   \
+                    _Pragma("unroll") for (int j = 0; j < TLM; ++j) pm[j] += stpm;                                          \
                 }                                                                                                           \
             }                                                                                                               \
         }                                                                                                                   \
@@ -785,7 +845,7 @@ __global__ __launch_bounds__(64, OCC) void rollout_kernel(RoP<T> p)
             cst = cst1; cu = cu1; ag = ag1;                                                                                 \
         }                                                                                                                   \
         T xn[NX];                                                                                                           \
-        model.step(x, u, xn);                                 /* x = f(x, u)   (isls.py:332) */                             \
+        model_step_row<MODEL>(model, x, u, mtabrec + d * MTABP, xn); /* x = f(x, u)   (isls.py:332) */                      \
         _Pragma("unroll") for (int j = 0; j < NX; ++j) x[j] = xn[j];                                                        \
     }
 
@@ -1058,10 +1118,11 @@ __host__ __device__ constexpr int ro_pick_jm(int occ, int jm)
 // dimensions, decision for decision.  Fills p (tpw, seg_lanes, seg_len, nseg, stage_on, u_off; fa_on off when the stage does
 // not fit) and `out`.  A user cost's table enters the same way: its two side records lie behind the model's words.
 template <typename T, int NX, int NU, int MDLW0>
-int plan_rollout(RoP<T> &p, const isls_rollout_args &a, bool want_fused, bool *stage_ok, RoLaunch &out, int ntab = 0)
+int plan_rollout(RoP<T> &p, const isls_rollout_args &a, bool want_fused, bool *stage_ok, RoLaunch &out, int ntab = 0, int mtab = 0)
 {
     using LY = RoLayout<NX, NU>;
-    const int MDLW = ro_mdl_words(MDLW0, ntab);                // ntab: the words per step of a user cost's table (its side records)
+    // ntab, mtab: the words per step of a user cost's table and of a user model's (their side records, the model's first)
+    const int MDLW = ro_mdl_words(ro_mdl_words(MDLW0, mtab), ntab);
     const int GL = a.L > 8 ? a.L : 8;
     int TPW = kWave / GL;
     // two waves per SIMD where a batch of 4096 launches more waves than SIMDs (slots of >= 16 lanes), the whole register

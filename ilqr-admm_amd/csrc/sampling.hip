@@ -48,6 +48,10 @@ static int launch_sample_round(const isls_sample_args &a, bool fb, const T *K, i
         const int rc = urtc::check_table(a.cost_model, a.N, a.ztab, a.ztab_sb, a.nvia);
         if (rc != ISLS_OK) return rc;
     }
+    if (umodel) {                                              // a table model: [par | N rows] behind model_par
+        const int rc = urtc::check_model_table(a.model, a.N, a.model_par, a.model_par_sb);
+        if (rc != ISLS_OK) return rc;
+    }
     const int64_t chunks = ((int64_t)a.S + kWave - 1) / kWave;
     if ((int64_t)a.B * chunks > 0x7fffffff) return ISLS_ERR_UNSUPPORTED;
     if (a.phase < 0 || a.phase > 2) return ISLS_ERR_ARG;

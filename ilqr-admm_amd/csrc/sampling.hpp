@@ -234,7 +234,7 @@ __global__ __launch_bounds__(64) void sample_cost_kernel(SampleP<T> p)
         draw.controls((unsigned int)s, (unsigned int)t, uh, u, e);
         cost.add(x, u, t, N);
         if (t < N - 1) {
-            mdl.step(x, u, xn);
+            model_step_at<MODEL>(mdl, x, u, t, xn);
 #pragma unroll
             for (int j = 0; j < NX; ++j) x[j] = xn[j];
         }
@@ -261,7 +261,7 @@ __device__ __forceinline__ T smp_rollout(const Model<T, NX, NU, MODEL> &mdl, Sam
         }
         cost.add(x, u, t, N);
         if (t < N - 1) {
-            mdl.step(x, u, xn);
+            model_step_at<MODEL>(mdl, x, u, t, xn);
 #pragma unroll
             for (int j = 0; j < NX; ++j) x[j] = xn[j];
         }
@@ -485,7 +485,7 @@ __global__ __launch_bounds__(64) void sample_cost_fb_kernel(SampleFbP<T> q)
         smp_clip_add<T, NU>(draw, v, eps, u);
         cost.add(x, u, t, N);
         if (t < N - 1) {
-            mdl.step(x, u, xn);
+            model_step_at<MODEL>(mdl, x, u, t, xn);
 #pragma unroll
             for (int j = 0; j < NX; ++j) x[j] = xn[j];
         }
@@ -524,7 +524,7 @@ __device__ __forceinline__ T smp_rollout_fb(const Model<T, NX, NU, MODEL> &mdl, 
         }
         cost.add(x, u, t, N);
         if (t < N - 1) {
-            mdl.step(x, u, xn);
+            model_step_at<MODEL>(mdl, x, u, t, xn);
 #pragma unroll
             for (int j = 0; j < NX; ++j) x[j] = xn[j];
         }

@@ -12,9 +12,9 @@ enum Fn { FN_LIN = 0, FN_LOOP, FN_STEP, FN_MC, FN_MPC };           // the order 
 
 // the functions of model `id` for a launch of dims (n, m)
 template <typename T>
-int prepare(int id, int n, int m, hipStream_t s, const std::vector<hipFunction_t> **fns)
+int prepare(int id, int n, int m, hipStream_t s, const std::vector<hipFunction_t> **fns, const urtc::Program **pg = nullptr)
 {
-    return urtc::prepare(id, urtc::kNone, urtc::dtype_of<T>(), n, m, s, fns);
+    return urtc::prepare(id, urtc::kNone, urtc::dtype_of<T>(), n, m, s, fns, pg);
 }
 
 }  // namespace
@@ -24,9 +24,11 @@ template <typename T>
 int launch_linearize_user(const isls_linearize_args &a, hipStream_t s)
 {
     if (a.B < 0 || a.N < 1 || !a.model_par || !a.A || !a.Bm || !a.xhat || !a.uhat) return ISLS_ERR_ARG;
+    int rc = urtc::check_model_table(a.model, a.N, a.model_par, a.model_par_sb);
+    if (rc != ISLS_OK) return rc;
     if (a.B == 0) return ISLS_OK;
     const std::vector<hipFunction_t> *fns;
-    const int rc = prepare<T>(a.model, a.n, a.m, s, &fns);
+    rc = prepare<T>(a.model, a.n, a.m, s, &fns);
     if (rc != ISLS_OK) return rc;
     const int steps = kWave / (a.n + a.m);                   // steps per workgroup (user_linearize_kernel's S)
     UserLinP<T> p;
@@ -44,6 +46,7 @@ template int launch_linearize_user<float>(const isls_linearize_args &, hipStream
 template <typename T>
 int launch_dense_closed_loop_user(const DenseLoopP<T> &p0, const isls_dense_loop_args &a, hipStream_t s)
 {
+    if (urtc::model_n_tab(a.model) != 0) return ISLS_ERR_UNSUPPORTED;   // a table model: not served (isls_hip.h)
     const std::vector<hipFunction_t> *fns;
     const int rc = prepare<T>(a.model, a.n, a.m, s, &fns);
     if (rc != ISLS_OK) return rc;
@@ -57,6 +60,7 @@ template int launch_dense_closed_loop_user<float>(const DenseLoopP<float> &, con
 template <typename T>
 int launch_mc_closed_loop_user(const McP<T> &p0, int model, int grid, int lanes, size_t smem, hipStream_t s)
 {
+    if (urtc::model_n_tab(model) != 0) return ISLS_ERR_UNSUPPORTED;     // a table model: not served (isls_hip.h)
     const std::vector<hipFunction_t> *fns;
     const int rc = prepare<T>(model, p0.n, p0.m, s, &fns);
     if (rc != ISLS_OK) return rc;
@@ -72,8 +76,12 @@ template int launch_mc_closed_loop_user<float>(const McP<float> &, int, int, int
 template <typename T>
 int launch_mpc_step_user(const MpcP<T> &p0, int model, int grid, size_t smem, hipStream_t s)
 {
+    // a table model: the window [par | N rows] in par, and a plant buffer that reaches row 0 at least
+    int rc = urtc::check_model_table(model, p0.N, p0.par, p0.par_sb);
+    if (rc == ISLS_OK) rc = urtc::check_model_table(model, p0.N, p0.plant, p0.plant_sb, 1);
+    if (rc != ISLS_OK) return rc;
     const std::vector<hipFunction_t> *fns;
-    const int rc = prepare<T>(model, p0.n, p0.m, s, &fns);
+    rc = prepare<T>(model, p0.n, p0.m, s, &fns);
     if (rc != ISLS_OK) return rc;
     MpcP<T> p = p0;
     void *args[] = {&p};
@@ -84,20 +92,29 @@ int launch_mpc_step_user(const MpcP<T> &p0, int model, int grid, size_t smem, hi
 template int launch_mpc_step_user<double>(const MpcP<double> &, int, int, size_t, hipStream_t);
 template int launch_mpc_step_user<float>(const MpcP<float> &, int, int, size_t, hipStream_t);
 
+// run = 0: the entry point without a table (one parameter row per state row); run >= 1: isls_user_model_step_tab_*
 template <typename T>
-static int user_step(int32_t id, int32_t R, const void *par, int64_t par_sb, const void *x, const void *u, void *xn, hipStream_t s)
+static int user_step(int32_t id, int32_t R, const void *par, int64_t par_sb, const void *x, const void *u, void *xn, hipStream_t s,
+                     int32_t run = 0, int32_t N = 0, const int32_t *tix = nullptr)
 {
     if (R < 0 || !par || !x || !u || !xn || par_sb < 0) return ISLS_ERR_ARG;
     int n, m;
     int rc = urtc::dims(urtc::KIND_MODEL, id, &n, &m);
-    if (rc != ISLS_OK || R == 0) return rc;
+    if (rc != ISLS_OK) return rc;
+    const int W = urtc::model_n_tab(id);
+    if ((W > 0) != (run > 0)) return ISLS_ERR_ARG;             // a table model steps through the _tab entry, and only it
+    if (W > 0 && ((rc = urtc::check_model_table(id, N, par, par_sb)) != ISLS_OK || (!tix && run > N))) return ISLS_ERR_ARG;
+    if (R == 0) return rc;
     const std::vector<hipFunction_t> *fns;
-    if ((rc = prepare<T>(id, n, m, s, &fns)) != ISLS_OK) return rc;
+    const urtc::Program *pg;
+    if ((rc = prepare<T>(id, n, m, s, &fns, &pg)) != ISLS_OK) return rc;
     int R_ = R;
     const T *par_ = (const T *)par, *x_ = (const T *)x, *u_ = (const T *)u;
     T *xn_ = (T *)xn;
-    void *args[] = {&R_, &par_, &par_sb, &x_, &u_, &xn_};
-    return urtc::launch((*fns)[FN_STEP], (R + 63) / 64, 0, s, args);
+    int run_ = run > 0 ? run : 1;
+    void *args[] = {&R_, &par_, &par_sb, &x_, &u_, &xn_, &run_, &tix};
+    if (W > 0 && pg->stab < 0) return ISLS_ERR_UNSUPPORTED;
+    return urtc::launch((*fns)[W > 0 ? pg->stab : FN_STEP], (R + 63) / 64, 0, s, args);
 }
 
 }  // namespace isls
@@ -110,6 +127,13 @@ ISLS_API int isls_user_model_create(const char *source, int32_t n, int32_t m, in
 {
     return urtc::create(urtc::KIND_MODEL, source, n, m, n_par, 0, id);
 }
+
+ISLS_API int isls_user_model_create_tab(const char *source, int32_t n, int32_t m, int32_t n_par, int32_t n_tab, int32_t *id)
+{
+    return urtc::create(urtc::KIND_MODEL, source, n, m, n_par, n_tab, id);
+}
+
+ISLS_API int isls_user_model_n_tab(int32_t id) { return is_user_model(id) ? urtc::model_n_tab(id) : ISLS_ERR_ARG; }
 
 ISLS_API int64_t isls_user_model_log(int32_t id, char *buf, int64_t len) { return urtc::copy_log(urtc::KIND_MODEL, id, buf, len); }
 
@@ -129,4 +153,14 @@ ISLS_API int isls_user_model_step_f32(int32_t id, int32_t R, const void *par, in
                                       void *stream)
 {
     return user_step<float>(id, R, par, par_sb, x, u, xn, (hipStream_t)stream);
+}
+ISLS_API int isls_user_model_step_tab_f64(int32_t id, int32_t R, int32_t run, int32_t N, const void *par, int64_t par_sb,
+                                          const int32_t *t, const void *x, const void *u, void *xn, void *stream)
+{
+    return run < 1 ? ISLS_ERR_ARG : user_step<double>(id, R, par, par_sb, x, u, xn, (hipStream_t)stream, run, N, t);
+}
+ISLS_API int isls_user_model_step_tab_f32(int32_t id, int32_t R, int32_t run, int32_t N, const void *par, int64_t par_sb,
+                                          const int32_t *t, const void *x, const void *u, void *xn, void *stream)
+{
+    return run < 1 ? ISLS_ERR_ARG : user_step<float>(id, R, par, par_sb, x, u, xn, (hipStream_t)stream, run, N, t);
 }

@@ -3,11 +3,15 @@
 //     #include "user_model_ad.hpp"
 //     namespace isls_user { <the user's step<S, P>> }
 //     #define ISLS_USER_NPAR <P>
+//     [#define ISLS_USER_MODEL_NTAB <W>]                                                      -- a model with a per-step table
 //     #include "user_model.hpp"
 // and its name expressions instantiate, for one (n, m, dtype): every (JM, OCC) variant of rollout_kernel that the launch plan
 // of a built-in model of the same dimensions can pick, user_linearize_kernel, dense_closed_loop_kernel, user_step_kernel and
 // mc_closed_loop_kernel (monte_carlo.hpp) and mpc_step_kernel (mpc.hpp).
 // The rollout kernel is the built-ins' template as it is: only Model<T, NX, NU, ISLS_MODEL_USER> below is new.
+// With ISLS_USER_MODEL_NTAB the user's step takes the W words of step t as `const P *row` behind `par` (plain P: nothing is
+// differentiated with respect to them); a source of the other form than its registration says does not compile.  The table lies
+// behind the parameters in the buffer the launch names as the model's: [par (P) | row 0 | ... | row N-1] (isls_hip.h).
 #pragma once
 
 #include "monte_carlo.hpp"
@@ -20,23 +24,46 @@
 #error "ISLS_USER_NPAR: the parameter count of the user model"
 #endif
 
+#ifndef ISLS_USER_MODEL_NTAB
+#define ISLS_USER_MODEL_NTAB 0
+#endif
+
 namespace isls {
 
 constexpr int kUserParWords = ISLS_USER_NPAR > 0 ? ISLS_USER_NPAR : 1;
 
-// the user's parameters live in registers, like the nonlinear built-ins' (no LDS words: the same launch plan as theirs)
+// the user's step in the form its registration names: with the row of step t, or without
+template <typename S, typename T>
+__device__ __forceinline__ void user_step(const S *x, const S *u, const T *par, const T *row, S *xn)
+{
+#if ISLS_USER_MODEL_NTAB > 0
+    ::isls_user::step<S, T>(x, u, par, row, xn);
+#else
+    ::isls_user::step<S, T>(x, u, par, xn);
+#endif
+}
+
+// the user's parameters live in registers, like the nonlinear built-ins' (no LDS words: the same launch plan as theirs).  A table
+// model keeps the address of row 0 (behind the parameters): step() is the step with that row -- the plant of isls_mpc_step --,
+// step_row() the step with the row the kernel hands it (model_step_row / model_step_at, rollout_kernel.hpp)
 template <typename T, int NX, int NU>
 struct Model<T, NX, NU, ISLS_MODEL_USER> {
     static constexpr int LDS_WORDS = 0;
     T par[kUserParWords];
+    const T *rows;
     __device__ __forceinline__ void load(const T *p, T *, int, int)
     {
 #pragma unroll
         for (int i = 0; i < kUserParWords; ++i) par[i] = i < ISLS_USER_NPAR ? p[i] : T(0);
+        rows = p + ISLS_USER_NPAR;
     }
     __device__ __forceinline__ void step(const T (&x)[NX], const T (&u)[NU], T (&xn)[NX]) const
     {
-        ::isls_user::step<T, T>(x, u, par, xn);
+        user_step<T, T>(x, u, par, rows, xn);
+    }
+    __device__ __forceinline__ void step_row(const T (&x)[NX], const T (&u)[NU], const T *row, T (&xn)[NX]) const
+    {
+        user_step<T, T>(x, u, par, row, xn);
     }
 };
 
@@ -71,7 +98,7 @@ __global__ __launch_bounds__(64) void user_linearize_kernel(UserLinP<T> p)
             u[i] = D(p.uhat[(bN + t) * NU + i]);
             u[i].d[0] = NX + i == j ? T(1) : T(0);
         }
-        ::isls_user::step<D, T>(x, u, par, xn);
+        user_step<D, T>(x, u, par, pp + ISLS_USER_NPAR + (int64_t)t * ISLS_USER_MODEL_NTAB, xn);   // row t: a plain global read
         if (j < NX) {
 #pragma unroll
             for (int i = 0; i < NX; ++i) tA[(ts * NX + i) * NX + j] = xn[i].d[0];
@@ -101,6 +128,28 @@ __global__ __launch_bounds__(64) void user_step_kernel(int R, const T *par, int6
 #pragma unroll
     for (int i = 0; i < NU; ++i) ur[i] = u[(int64_t)r * NU + i];
     mdl.step(xr, ur, yr);
+#pragma unroll
+    for (int i = 0; i < NX; ++i) xn[(int64_t)r * NX + i] = yr[i];
+}
+
+// The same for a table model (isls_user_model_step_tab_*; the last name expression of such a model's program): the state rows
+// come in runs of `run` rows per parameter block [par | rows] (par_sb per run), and row r steps with table row tix[r], or
+// (tix == NULL) with its place r % run in its run.
+template <typename T, int NX, int NU>
+__global__ __launch_bounds__(64) void user_step_tab_kernel(int R, const T *par, int64_t par_sb, const T *x, const T *u, T *xn, int run,
+                                                           const int32_t *tix)
+{
+    const int r = blockIdx.x * kWave + threadIdx.x;
+    if (r >= R) return;
+    Model<T, NX, NU, ISLS_MODEL_USER> mdl;
+    mdl.load(par + (int64_t)(r / run) * par_sb, nullptr, 0, 1);
+    const int t = tix ? tix[r] : r % run;
+    T xr[NX], ur[NU], yr[NX];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) xr[i] = x[(int64_t)r * NX + i];
+#pragma unroll
+    for (int i = 0; i < NU; ++i) ur[i] = u[(int64_t)r * NU + i];
+    model_step_at<ISLS_MODEL_USER>(mdl, xr, ur, t, yr);
 #pragma unroll
     for (int i = 0; i < NX; ++i) xn[(int64_t)r * NX + i] = yr[i];
 }

@@ -207,7 +207,7 @@ int load_program(Program &pg, const std::vector<hipFunction_t> **out, hipStream_
 // ---- the registry and the program cache (both under g_mu) --------------------------------------------------------------------
 struct Source {
     std::string source;
-    int n, m, npar, ntab;                                    // ntab: words per step of a cost's table (0: none)
+    int n, m, npar, ntab;                                    // ntab: words per step of the source's table (0: none)
     std::string log;
 };
 
@@ -273,6 +273,7 @@ int program(int model, int cost, int dtype, Program **out)
     pg.ro0 = (int)pg.names.size();
     pg.mdlw = mdlw;
     pg.ntab = uc ? uc->ntab : 0;
+    pg.mtab = um ? um->ntab : 0;
     pg.ro.clear();
     if (model != kNone) {
 #define ISLS_URTC_VARIANTS_(NX_, NU_) if (n == NX_ && m == NU_) ro_variants<NX_, NU_>(pg.ro);
@@ -290,8 +291,15 @@ int program(int model, int cost, int dtype, Program **out)
         for (const char *k : {"isls::sample_cost_kernel<", "isls::sample_update_kernel<", "isls::sample_cost_fb_kernel<", "isls::sample_update_fb_kernel<"})
             pg.names.push_back(k + T + ", " + dims + ", " + tmodel + ">");
     }
+    // a table model's own program: its row-wise step with a row per state row, behind every other name
+    pg.stab = -1;
+    if (um && !uc && um->ntab > 0) {
+        pg.stab = (int)pg.names.size();
+        pg.names.push_back("isls::user_step_tab_kernel<" + T + ", " + dims + ">");
+    }
     std::string src = uc ? "#include \"user_cost_ad.hpp\"\n" : "#include \"user_model_ad.hpp\"\n";
     if (um) src += wrap_source("isls_user", "user_model", um->source) + "#define ISLS_USER_NPAR " + std::to_string(um->npar) + "\n";
+    if (um && um->ntab > 0) src += "#define ISLS_USER_MODEL_NTAB " + std::to_string(um->ntab) + "\n";
     if (uc) src += wrap_source("isls_user_cost", "user_cost", uc->source) + "#define ISLS_USER_COST_NPAR " + std::to_string(uc->npar) + "\n";
     if (uc && uc->ntab > 0) src += "#define ISLS_USER_COST_NTAB " + std::to_string(uc->ntab) + "\n";
     src += uc ? "#include \"user_cost.hpp\"\n" : "#include \"user_model.hpp\"\n";
@@ -307,7 +315,7 @@ int create(Kind kind, const char *source, int n, int m, int n_par, int n_tab, in
 {
     if (!source || !id) return ISLS_ERR_ARG;
     if (!dims_supported(n, m) || n_par < 0 || n_par > ISLS_USER_MAX_PAR) return ISLS_ERR_UNSUPPORTED;
-    if (n_tab < 0 || n_tab > ISLS_USER_MAX_TAB || (kind == KIND_MODEL && n_tab != 0)) return ISLS_ERR_UNSUPPORTED;
+    if (n_tab < 0 || n_tab > ISLS_USER_MAX_TAB) return ISLS_ERR_UNSUPPORTED;
     auto src = std::make_unique<Source>();
     src->source = source; src->n = n; src->m = m; src->npar = n_par; src->ntab = n_tab;
     if (refused_source(src->source)) return ISLS_ERR_ARG;     // plain arithmetic: no hand-written ISA through this door
@@ -372,6 +380,30 @@ int n_tab(int cost)
     return src ? src->ntab : ISLS_ERR_ARG;
 }
 
+int model_n_tab(int model)
+{
+    if (!is_user_model(model)) return 0;
+    std::lock_guard<std::mutex> lk(g_mu);
+    const Source *src = find(KIND_MODEL, model);
+    return src ? src->ntab : ISLS_ERR_ARG;
+}
+
+int check_model_table(int model, int N, const void *par, int64_t par_sb, int rows_min)
+{
+    if (!is_user_model(model)) return ISLS_OK;
+    int P, W;
+    {
+        std::lock_guard<std::mutex> lk(g_mu);
+        const Source *src = find(KIND_MODEL, model);
+        if (!src) return ISLS_ERR_ARG;
+        P = src->npar; W = src->ntab;
+    }
+    if (W <= 0) return ISLS_OK;
+    if (!par || N < 1) return ISLS_ERR_ARG;
+    if (rows_min >= 0 && rows_min < N) return par_sb == 0 || par_sb >= (int64_t)P + (int64_t)rows_min * W ? ISLS_OK : ISLS_ERR_ARG;
+    return par_sb == 0 || par_sb == (int64_t)P + (int64_t)N * W ? ISLS_OK : ISLS_ERR_ARG;
+}
+
 int check_table(int cost, int N, const void *tab, int64_t tab_sb, int nvia)
 {
     const int W = n_tab(cost);
@@ -420,17 +452,18 @@ int launch_rollout_user(RoP<T> &p, const isls_rollout_args &a, hipStream_t s, bo
     const std::vector<hipFunction_t> *fns;
     int rc = ucost ? urtc::check_table(a.cost_model, a.N, a.ztab, a.ztab_sb, a.nvia) : ISLS_OK;   // the table: ztab, ztab_sb, nvia
     if (rc != ISLS_OK) return rc;
+    if ((rc = urtc::check_model_table(a.model, a.N, a.model_par, a.model_par_sb)) != ISLS_OK) return rc;   // a model's: behind model_par
     rc = urtc::prepare(a.model, ucost ? a.cost_model : urtc::kNone, urtc::dtype_of<T>(), a.n, a.m, s, &fns, &pg);
     if (rc != ISLS_OK) return rc;
     if (ucost) p.cpar_sb = a.cost_par_sb;
     RoLaunch pl;
     rc = ISLS_ERR_UNSUPPORTED;
     // the model enters the plan through its LDS words only (a dense LTI model's [A B]; none for the others and for user models),
-    // a cost's table through the side records of its row behind them
+    // a cost's table and a user model's through the side records of their rows behind them
 #define ISLS_URTC_PLAN_(NX_, NU_)                                                                              \
     if (a.n == NX_ && a.m == NU_)                                                                              \
         rc = pg->mdlw ? plan_rollout<T, NX_, NU_, NX_ * (NX_ + NU_)>(p, a, want_fused, nullptr, pl, pg->ntab)  \
-                      : plan_rollout<T, NX_, NU_, 0>(p, a, want_fused, nullptr, pl, pg->ntab);
+                      : plan_rollout<T, NX_, NU_, 0>(p, a, want_fused, nullptr, pl, pg->ntab, pg->mtab);
     ISLS_FOR_EACH_DIMS(ISLS_URTC_PLAN_)
 #undef ISLS_URTC_PLAN_
     if (rc != ISLS_OK) return rc;

@@ -24,13 +24,15 @@ struct Program {                                             // one key: a model
     std::vector<std::string> names, lowered;                 // name expressions and their mangled names
     int ro0 = 0, mdlw = 0;                                   // index of the first rollout variant; LDS words of the model (plan_rollout)
     int ntab = 0;                                            // words per step of the cost's table (its side records enter the plan too)
+    int mtab = 0;                                            // ... and of the user model's table (likewise)
+    int stab = -1;                                           // index of user_step_tab_kernel (a table model's own program)
     int smp0 = -1;                                           // index of sample_cost_kernel; sample_update_kernel and the two *_fb_kernel behind it (a key with a model)
     std::vector<std::pair<int, int>> ro;                     // (JM, OCC) of the rollout variants: names[ro0 + i]
     std::map<int, std::pair<hipModule_t, std::vector<hipFunction_t>>> dev;   // device -> module, functions
 };
 
 // isls_user_{model,cost}_create: register `source` (an id is assigned even when the compile fails) and compile its own program
-// (the model's, or the cost's expansion and value) for fp64; n_tab: words per step of a cost's table (0: none, and for a model)
+// (the model's, or the cost's expansion and value) for fp64; n_tab: words per step of the source's table (0: none)
 int create(Kind kind, const char *source, int n, int m, int n_par, int n_tab, int32_t *id);
 // isls_user_*_log / _code / _load: the compiler's messages for a source so far; the code object of a key, compiled on first use;
 // the same loaded onto the current device
@@ -39,6 +41,12 @@ int copy_code(int model, int cost, int dtype, void *buf, int64_t *len);
 int load(int model, int cost, int dtype);
 int dims(Kind kind, int id, int *n, int *m);                 // ISLS_ERR_ARG: no such id
 int n_tab(int cost);                                         // words per step of the cost's table (0: none); ISLS_ERR_ARG: no such id
+int model_n_tab(int model);                                  // the same of a user model's table; 0 for every built-in model
+// A launch's model parameters against a table model's registration, before anything is compiled, loaded or launched (no GPU
+// needed): a model with P parameters and a table of W words per step takes [par (P) | row 0 | ... | row N-1] -- par != NULL and
+// par_sb == 0 (one block for the batch) or P + N * W (one per trajectory); rows_min < N: a buffer that need only reach that many
+// rows (the plant of isls_mpc_step: row 0), par_sb == 0 or >= P + rows_min * W.  ISLS_ERR_ARG otherwise; any other model: ISLS_OK.
+int check_model_table(int model, int N, const void *par, int64_t par_sb, int rows_min = -1);
 // A launch's table fields against the cost's registration, before anything is compiled, loaded or launched (no GPU needed): a
 // cost with a table of W words needs tab != NULL, tab_sb == 0 or N * W, and nvia == W (nvia < 0: not given); the fields of a cost
 // without a table are ignored.  ISLS_ERR_ARG otherwise, and for an id nobody registered.

@@ -24,7 +24,7 @@ REG_AFTER_GAIN, REG_AFTER_LS = 0, 1             # isls_reg_update_args.mode
 SOLVE_CHOL, SOLVE_INV = 0, 1
 MODEL_LTI, MODEL_ARM3R, MODEL_CAR, MODEL_DI, MODEL_TASSA = 0, 1, 2, 3, 4
 MODEL_USER_BASE, USER_MAX_PAR = 1024, 16      # ids of user models (isls_user_model_create), parameters per model at most
-USER_MAX_TAB = 16                              # words per step of a user cost's table (isls_user_cost_create_tab), at most
+USER_MAX_TAB = 16                              # words per step of a user cost's / model's table (isls_user_*_create_tab), at most
 DTYPE_F64, DTYPE_F32 = 0, 1
 COST_VIA, COST_PHUBER = 0, 1
 COST_USER_BASE = 1024                          # ids of user costs (isls_user_cost_create)
@@ -270,13 +270,13 @@ class AdvanceArgs(C.Structure):
 EXPORTED = [f"isls_{k}_{s}" for s in ("f64", "f32") for k in
             ("riccati_gain", "riccati_ff", "riccati_gain_ff", "riccati_ff_prepare", "rollout_ls", "admm_update", "project_rows", "sls_admm", "sls_closed_loop", "columns_rollout", "columns_admm", "dense_closed_loop", "mc_closed_loop", "mpc_step", "sample_nominal", "sample_nominal_fb", "cov_closed_loop", "sls_controller", "expand_quadratic", "linearize",
              "accept_step", "reduce_convergence", "reduce_convergence_table", "ilqr_admm_outer", "outer_advance", "columns_iteration",
-             "user_model_step", "user_cost_value", "user_cost_value_tab", "user_cost_expand", "riccati_gain_reg", "reg_update")] + \
+             "user_model_step", "user_model_step_tab", "user_cost_value", "user_cost_value_tab", "user_cost_expand", "riccati_gain_reg", "reg_update")] + \
            ["isls_ff_segments", "isls_ff_record_elems", "isls_sls_controller_work_elems", "isls_mc_work_elems", "isls_version", "isls_dims_supported", "isls_dims_generic", "isls_error_string", "isls_timing_create",
             "isls_timing_destroy", "isls_timing_reset", "isls_timing_pause", "isls_timing_read_ms",
             "isls_gain_memo_stats", "isls_gain_memo_clear",
             "isls_user_model_create", "isls_user_model_log", "isls_user_model_code", "isls_user_model_load",
             "isls_user_cost_create", "isls_user_cost_log", "isls_user_cost_code", "isls_user_cost_load",
-            "isls_user_cost_create_tab", "isls_user_cost_n_tab"]
+            "isls_user_cost_create_tab", "isls_user_cost_n_tab", "isls_user_model_create_tab", "isls_user_model_n_tab"]
 
 
 SET_BOX, SET_SOC_UNIT, SET_SQUARE, SET_LINEAR, SET_QUADRATIC, SET_SHELL, SET_MULTILINEAR = 1, 2, 3, 4, 5, 6, 7
@@ -320,6 +320,8 @@ def load_hip_library(path=None):
     lib.isls_timing_read_ms.restype = C.c_double
     lib.isls_timing_read_ms.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     lib.isls_user_model_create.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
+    lib.isls_user_model_create_tab.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
+    lib.isls_user_model_n_tab.argtypes = [C.c_int32]
     lib.isls_user_model_log.restype = C.c_int64
     lib.isls_user_model_log.argtypes = [C.c_int32, C.c_char_p, C.c_int64]
     lib.isls_user_model_code.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int64)]
@@ -405,7 +407,7 @@ class _UserKind:
         return buf.value.decode(errors="replace")
 
     def create(self, source, n, m, n_par, n_tab=0):
-        """n_tab > 0 (costs only): a cost with a per-step table of that many words; the key of one without is what it was"""
+        """n_tab > 0: a source with a per-step table of that many words; the key of one without is what it was"""
         key = (str(source), int(n), int(m), int(n_par)) + ((int(n_tab),) if n_tab else ())
         if key in self.ids:
             return self.ids[key]
@@ -438,10 +440,21 @@ _USER_MODEL, _USER_COST = _UserKind("model", MODEL_USER_BASE), _UserKind("cost",
 user_model_log, user_cost_log = _USER_MODEL.log, _USER_COST.log
 
 
-def user_model_create(source, n, m, n_par):
-    """Compile a user model for gfx950 (fp64 at once, fp32 on first use) and return its id; the same (source, n, m, n_par)
-    is compiled once per process.  IslsError carries the compile log."""
-    return _USER_MODEL.create(source, n, m, n_par)
+def user_model_create(source, n, m, n_par, n_tab=0):
+    """Compile a user model for gfx950 (fp64 at once, fp32 on first use) and return its id; the same (source, n, m, n_par, n_tab)
+    is compiled once per process.  n_tab > 0: the model reads a table of that many words per step (isls_user_model_create_tab;
+    the five-argument `step`).  IslsError carries the compile log."""
+    return _USER_MODEL.create(source, n, m, n_par, n_tab)
+
+
+def user_model_n_tab(model_id):
+    """Words per step of the model's table (0: a model without one, and every built-in model)."""
+    if int(model_id) < MODEL_USER_BASE:
+        return 0
+    rc = library().isls_user_model_n_tab(C.c_int32(model_id))
+    if rc < 0:
+        raise IslsError(f"isls_user_model_n_tab -> {rc}: {library().isls_error_string(rc).decode()}")
+    return rc
 
 
 def user_model_code(model_id, dtype=np.float64):
@@ -1300,6 +1313,18 @@ class Kernels:
         ptr, sb = _par(par, R, "par")
         return self._invoke("user_model_step", _sfx(xn), C.c_int32(model_id), C.c_int32(R), C.c_void_p(ptr), C.c_int64(sb),
                             C.c_void_p(_ptr(x)), C.c_void_p(_ptr(u)), C.c_void_p(_ptr(xn)), stream=stream)
+
+    def user_model_step_tab(self, model_id, par, x, u, xn, run, N, t=None, stream=None):
+        """isls_user_model_step_tab: xn [R,n] = f(x [R,n], u [R,m]; row) of a table model; the rows come in runs of `run` per
+        parameter block par [P + N W] (shared) or [R / run, P + N W]; row r takes table row t[r] (int32 [R]) or r % run."""
+        R, n = xn.shape
+        _dense(x, (R, n), "x"), _dense(u, (R, u.shape[1]), "u")
+        if t is not None:
+            _dense(t, (R,), "t")
+        ptr, sb = _par(par, R // int(run), "par")
+        return self._invoke("user_model_step_tab", _sfx(xn), C.c_int32(model_id), C.c_int32(R), C.c_int32(int(run)), C.c_int32(int(N)),
+                            C.c_void_p(ptr), C.c_int64(sb), C.c_void_p(_ptr(t)), C.c_void_p(_ptr(x)), C.c_void_p(_ptr(u)),
+                            C.c_void_p(_ptr(xn)), stream=stream)
 
     def user_cost_value(self, cost_id, par, x, u, cost, stream=None, tab=None):
         """isls_user_cost_value: cost [R] = sum_t stage(x [R,N,n], u [R,N,m]) with par [P] (shared) or [R,P]; a cost with a table

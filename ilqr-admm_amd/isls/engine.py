@@ -108,6 +108,7 @@ class Engine:
         # problem description
         self.model = None
         self.model_par = None
+        self.model_tab_w = 0                                  # words per step of a user model's table (models.Custom(table=)), 0: none
         self.Qtab = self.ztab = self.seq = self.q_nonzero = None
         self.u_std = 0.0
         self.cost_model, self.cost_par = capi.COST_VIA, None
@@ -182,13 +183,41 @@ class Engine:
 
     def set_model(self, model_id, par):
         """Built-in forward model (ISLS_MODEL_*) or a user model (models.Custom.model_id); par is [P] (shared) or [B,P] (per
-        trajectory)."""
-        self.model, self.model_par = int(model_id), self._t(par)
+        trajectory).  A user model with a per-step table of W words: [P + N W] or [B, P + N W], [par | row 0 | ... | row N-1]
+        (models.Custom.device_params; include/isls_hip.h) -- model_table is the view of its rows."""
+        W = capi.user_model_n_tab(model_id)
+        par = self._t(par)
+        if W and (par.ndim not in (1, 2) or not 0 <= par.shape[-1] - self.N * W <= capi.USER_MAX_PAR
+                  or (par.ndim == 2 and par.shape[0] != self.B)):
+            raise ValueError(f"model {model_id} reads a table of {W} words per step: its parameters are [P + {self.N} * {W}] or "
+                             f"[{self.B}, P + {self.N} * {W}] (par | rows), got {tuple(par.shape)}")
+        self.model, self.model_par, self.model_tab_w = int(model_id), par, W
         if self.model >= capi.MODEL_USER_BASE:                # a user model: its module goes onto the device now, outside any capture
             with torch.cuda.device(self.device):
                 capi.user_model_load(self.model, self.dtype)
         self._load_user_cost()
         self._ab_stale()
+
+    @property
+    def model_table(self):
+        """The rows of a table model inside model_par, as a view [N, W] or [B, N, W] (None: a model without a table): what is
+        written INTO it is what the next launch reads -- the argument blocks cached over model_par stay valid."""
+        if not self.model_tab_w:
+            return None
+        P = self.model_par.shape[-1] - self.N * self.model_tab_w
+        return self.model_par[..., P:].unflatten(-1, (self.N, self.model_tab_w))
+
+    def update_model_table(self, table):
+        """New values for the model's table ([N, W], or [B, N, W] where the engine holds one block per trajectory), copied INTO
+        model_par with one copy_: nothing is compiled, allocated on the device or marshalled again.  A linearisation made with the
+        old rows is stale afterwards."""
+        view = self.model_table
+        t = table if isinstance(table, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(table), dtype=self.dtype)
+        if view is None or tuple(t.shape) not in (tuple(view.shape), tuple(view.shape[-2:])):
+            raise ValueError(f"update_model_table: the table is {None if view is None else tuple(view.shape)}, got {tuple(t.shape)}")
+        view.copy_(t)
+        if self._ab_src == LINEARIZED:
+            self._ab_src = None
 
     @property
     def user_cost(self):

@@ -70,7 +70,11 @@ class iSLS(Base):
             if model.x_dim != self.x_dim or model.u_dim != self.u_dim:
                 raise ValueError("model dimensions do not match x_dim/u_dim")
             self._forward_model, self._host_model = model, False
-            self.engine.set_model(model.model_id, model.params())
+            if getattr(model, "table", None) is not None:      # models.Custom(table=): [par | rows] is what the device reads
+                self.engine.set_model(model.model_id, model.device_params(self.batch, self.N))
+                self._model_table_version = model._table_version
+            else:
+                self.engine.set_model(model.model_id, model.params())
             return
         if not callable(model):
             raise TypeError("forward_model must be an isls.models descriptor or a callable f(x, u)")
@@ -105,6 +109,12 @@ class iSLS(Base):
         else:
             raise TypeError("cost_function must be None, an isls.costs object or a callable cost(x, u)")
 
+    def _sync_tables(self):
+        """set_table on the model or on the cost since this object last looked: the model's rows first, so that the cost of the
+        nominal is evaluated with both in place."""
+        self._sync_model_table()
+        self._sync_cost_table()
+
     def _sync_cost_table(self):
         """costs.Custom.set_table since this object last looked: the new values go INTO the engine's device table (no compile, no
         allocation, cached argument blocks stay valid) and the nominal's cost is evaluated again with them."""
@@ -114,6 +124,22 @@ class iSLS(Base):
         self.engine.update_cost_table(f.table)
         self._table_version = f._table_version
         self.engine.evaluate_cost()
+
+    def _sync_model_table(self):
+        """models.Custom.set_table since this object last looked: the new rows go INTO the engine's model_par (one copy_, no
+        compile, cached argument blocks stay valid)."""
+        mdl = self._forward_model
+        if self._host_model or getattr(mdl, "table", None) is None or mdl._table_version == self._model_table_version:
+            return
+        self.engine.update_model_table(mdl.table)
+        self._model_table_version = mdl._table_version
+
+    def _refuse_table_model(self, what):
+        """The entry points a models.Custom(table=) is not served by: their kernels step the model with no notion of time."""
+        if not self._host_model and getattr(self._forward_model, "table", None) is not None:
+            raise capi.IslsError(f"{what} does not serve a model with a per-step table (models.Custom(table=)): fold the schedule into "
+                                 "the state (a clock state that the step reads), or run the loop yourself with the model's "
+                                 "__call__(x, u, t=)")
 
     @property
     def AB(self):
@@ -144,7 +170,7 @@ class iSLS(Base):
     @nominal_values.setter
     def nominal_values(self, value):
         e = self.engine
-        self._sync_cost_table()
+        self._sync_tables()
         if e.Qtab is None:                                      # no via-point cost (a callable cost only): a zero table
             e.set_quadratic_cost(np.zeros((1, self.x_dim)), np.zeros((1, self.x_dim, self.x_dim)), np.zeros(self.N, dtype=np.int32), 0.0)
         e.set_nominal(self._batched(value[0], 2), self._batched(value[1], 2))
@@ -179,7 +205,7 @@ class iSLS(Base):
 
     @property
     def cost(self):
-        self._sync_cost_table()
+        self._sync_tables()
         c = self.engine.cost.detach().cpu().numpy()
         return float(c[0]) if self.batch == 1 else c
 
@@ -249,7 +275,7 @@ class iSLS(Base):
 
     def _expand(self, Cts=None, cts=None):
         e = self.engine
-        self._sync_cost_table()
+        self._sync_tables()
         if Cts is None:
             if not e.user_cost:                                 # (a user cost's expansion writes Cux)
                 e.Cux = None
@@ -367,7 +393,7 @@ class iSLS(Base):
         if regularization is not None and method == 'batch':
             raise capi.IslsError("solve(method='batch') does not serve a regularisation (its column passes have no such term); use method='dp'")
         self._set_regularization(regularization)
-        self._sync_cost_table()
+        self._sync_tables()
         e = self.engine
         e.outer_active.fill_(1)
         prev = np.atleast_1d(np.array(self.cost, dtype=np.float64)).copy()
@@ -438,7 +464,7 @@ class iSLS(Base):
         stop rules |dcost| < 1e-3 / oscillation < 1e-3.  Returns the residual log of the last outer iteration."""
         if self._host_cost and get_Cs is None:
             raise ValueError("a callable cost_function needs get_Cs (its gradient / Hessian along the nominal)")
-        self._sync_cost_table()
+        self._sync_tables()
         max_iter = k_max if k_max is not None else max_iter
         L = max_line_search if max_line_search is not None else max_line_search_iter
         tol = threshold if threshold is not None else tol
@@ -482,7 +508,7 @@ class iSLS(Base):
     # ---- receding-horizon control of the whole batch ----------------------------------------------------------------------
     def mpc(self, steps, iters=1, project_x=False, project_u=False, rho_x=None, rho_u=None, alpha=1, max_admm_iter=5,
             max_line_search_iter=20, tol=1e-3, plant_params=None, noise_scale=0.0, w=None, seed=0, feedback=True,
-            warm_start_z=False, clip_u=None, table_future=None, regularization=None):
+            warm_start_z=False, clip_u=None, table_future=None, regularization=None, model_table_future=None, plant_table=None):
         """Model-predictive control of every trajectory of the batch for `steps` control steps, with no host round trip per step.
         Per control step s: `iters` outer iterations of ilqr_admm's device route about the current plan (same stop rules per
         trajectory, tol_cost = tol_osc = 1e-3, same gain / feed-forward / line-search settings), then one launch
@@ -496,6 +522,12 @@ class iSLS(Base):
         APPLIED control only.  table_future [steps, W] or [batch, steps, W] (a costs.Custom(table=) cost): row s enters the
         window as its last row after step s; without it the last row is held.  The via-point cost of set_cost_variables is
         horizon-relative: it is reused unchanged in every window (a via point at step t stays t steps ahead of the plant).
+        A models.Custom(table=) model: its table is the window of a world-time table that the engine keeps on the device;
+        model_table_future [steps, W] or [batch, steps, W] are the rows behind the window -- row s enters it as its last row after
+        control step s, without it the last row is held -- and per control step the window inside the model's device buffer is
+        refreshed with one device-to-device copy ahead of the re-roll.  The plant of step s steps with the window's row 0
+        (world row s) and `plant_params`; plant_table [steps, W] or [batch, steps, W] supplies its own row s instead: a forecast
+        against the truth.  Afterwards the model object's table is the last window.
         A ConvexSets with per-row tables (par_rows / b_rows: moving obstacles) follows the loop by the rows it has left from its
         row0: exactly N -- horizon-relative, it stays put as well; N + steps or more -- world time, its window moves up one row
         per control step (pointers in the descriptors, no device work) and the object's row0 is steps further on afterwards, so
@@ -530,7 +562,10 @@ class iSLS(Base):
                                          f"horizon: sets that stay put in every window) or at least {N + T_} (the horizon + steps: "
                                          "sets in world time) are needed -- pad the table by repeating its last row")
                 moving[blk] = left != N
-        self._sync_cost_table()
+        self._sync_tables()
+        mtab = e.model_table                                   # a models.Custom(table=): the window [N, W] / [B, N, W] in model_par
+        if mtab is None and (model_table_future is not None or plant_table is not None):
+            raise capi.IslsError("model_table_future / plant_table belong to a models.Custom(table=) forward model")
         if table_future is not None and e.cost_tab is None:
             raise capi.IslsError("table_future is the future of a costs.Custom(table=) cost's table: set such a cost_function, or move "
                                  "the via points of set_cost_variables yourself")
@@ -539,7 +574,7 @@ class iSLS(Base):
         plant = None
         if plant_params is not None:
             pp = np.ascontiguousarray(plant_params, dtype=np.float64)
-            P_ = e.model_par.shape[-1]
+            P_ = e.model_par.shape[-1] - N * e.model_tab_w
             if pp.ndim not in (1, 2) or pp.shape[-1] != P_ or (pp.ndim == 2 and pp.shape[0] != B):
                 raise capi.IslsError(f"plant_params: [{P_}] for every trajectory or [{B}, {P_}] (one row per trajectory), got "
                                      f"{pp.shape}")
@@ -570,6 +605,37 @@ class iSLS(Base):
             if per_traj:
                 tf = (tf if tf.ndim == 3 else tf.unsqueeze(0).expand(B, T_, W)).permute(1, 0, 2).contiguous()
             table_future = tf
+        world = plants = None
+        if mtab is not None:
+            # the world-time table [.., N + steps, W] on the device, and every step's plant buffer [par | its row]: built once
+            W, MP = e.model_tab_w, e.model_par.shape[-1] - N * e.model_tab_w
+
+            def rows(v, name):
+                if v is None:
+                    return None
+                v = e._t(v)
+                if tuple(v.shape) not in ((T_, W), (B, T_, W)):
+                    raise ValueError(f"{name}: [{T_}, {W}] or [{B}, {T_}, {W}], got {tuple(v.shape)}")
+                return v
+            fut, ptab = rows(model_table_future, "model_table_future"), rows(plant_table, "plant_table")
+            if fut is not None and fut.ndim == 3 and self._forward_model.table.ndim == 2:
+                # (with per-trajectory parameters the engine's window is [B, N, W], but the object's table is one for the batch:
+                # per-trajectory futures would leave windows that the object cannot hold afterwards)
+                raise ValueError(f"model_table_future: [{T_}, {W}] (the model's table is shared by the batch)")
+            if fut is None:
+                fut = mtab[..., -1:, :].expand(*mtab.shape[:-2], T_, W)
+            elif fut.ndim < mtab.ndim:
+                fut = fut.unsqueeze(0).expand(B, T_, W)
+            world = torch.cat([mtab, fut], dim=-2).contiguous()
+            prow = world[..., :T_, :] if ptab is None else ptab                  # the plant's row of step s
+            ppar = e.model_par[..., :MP] if plant is None else plant
+            per = prow.ndim == 3 or ppar.ndim == 2
+            if per:
+                prow = (prow if prow.ndim == 3 else prow.unsqueeze(0).expand(B, T_, W)).permute(1, 0, 2)
+                plants = torch.cat([(ppar if ppar.ndim == 2 else ppar.unsqueeze(0).expand(B, MP)).unsqueeze(0).expand(T_, B, MP), prow], dim=-1)
+            else:
+                plants = torch.cat([ppar.unsqueeze(0).expand(T_, MP), prow], dim=-1)
+            plants = plants.contiguous()
         L, J = int(max_line_search_iter), int(max_admm_iter)
         z = lambda *s_, dt=e.dtype: torch.zeros(*s_, dtype=dt, device=e.device)   # noqa: E731
         x_log, u_log, cost_log = z(B, T_ + 1, n), z(B, T_, m), z(B, T_)
@@ -597,7 +663,9 @@ class iSLS(Base):
                     e.accept_x_step(tol_cost=1e-3, tol_osc=1e-3)
             cost_log[:, s].copy_(e.cost)
             st_log[:, s].copy_(e.status)
-            e.mpc_step(plant_par=plant, u_lo=u_lo, u_hi=u_hi, w=None if w is None else w[s], noise_std=noise_std, seed=seed, step=s,
+            if world is not None:                              # the window moves up: one device-to-device copy INTO model_par
+                mtab.copy_(world[..., s + 1:s + 1 + N, :])
+            e.mpc_step(plant_par=plant if plants is None else plants[s], u_lo=u_lo, u_hi=u_hi, w=None if w is None else w[s], noise_std=noise_std, seed=seed, step=s,
                        feedback=feedback, shift_z=warm_start_z, tab_next=None if table_future is None else table_future[s],
                        x_meas_out=x_log[:, s], u_out=u_log[:, s], x_next_out=x_log[:, s + 1])
             if any(moving.values()):
@@ -609,6 +677,10 @@ class iSLS(Base):
         f = self._cost_function
         if getattr(f, "table", None) is not None:               # the cost object follows the window the engine holds now
             f._table = e.cost_tab.cpu().numpy().astype(np.float64)
+        if mtab is not None:                                    # ... and so does the model object
+            mdl = self._forward_model
+            last = mtab.cpu().numpy().astype(np.float64)
+            mdl._table = np.ascontiguousarray(last if last.ndim == mdl._table.ndim else last[0])
         for blk, pr in (("x", px), ("u", pu)):                  # ... and the sets' objects the rows consumed
             if moving.get(blk):
                 pr.advance(T_)
@@ -736,6 +808,7 @@ class iSLS(Base):
         """Monte-Carlo closed loop of the dense controller about the nominal of problem `problem` through the forward model
         (isls/isls_base.py:28-42): x0 [M, n] -> (x_log [M,N,n], u_log [M,N,m]); one device thread per initial state."""
         e = self.engine
+        self._refuse_table_model("get_trajectory_sls (the dense closed loop)")
         if noise_scale or self._host_model:
             # process noise comes from numpy's global generator, one draw per step in the reference's order: host loop
             # through the (numpy-callable) forward model, isls/isls_base.py:28-42
@@ -775,6 +848,7 @@ class iSLS(Base):
         if self._host_model or e.model is None:
             raise capi.IslsError("monte_carlo runs on the device: set forward_model to an isls.models descriptor (models.Custom for a "
                                  "model of your own), not a Python callable")
+        self._refuse_table_model("monte_carlo")
         xhat, uhat = (None, None) if absolute else (e.xhat, e.uhat)
         if x0 is None and x0s is None:
             x0 = e.xhat[:, 0].contiguous()
@@ -839,7 +913,7 @@ class iSLS(Base):
             if regularization is not iSLS._KEEP:
                 self._set_regularization(regularization)
             feedback = self._sampling_gains
-        self._sync_cost_table()
+        self._sync_tables()
         if e.Qtab is None:                                      # no via-point cost: a zero table (the nominal_values setter's rule)
             e.set_quadratic_cost(np.zeros((1, self.x_dim)), np.zeros((1, self.x_dim, self.x_dim)), np.zeros(self.N, dtype=np.int32), 0.0)
         try:
@@ -925,6 +999,7 @@ class iSLS(Base):
         """Batch-form backward pass + open-loop line search with the acceptance test costs[ind] < cost
         (isls/isls.py:191-225).  Returns fp_success (bool, or a bool array when batched)."""
         e = self.engine
+        self._refuse_table_model("the batch form (iterate_once_batch, solve(method='batch'))")
         self.backward_pass_batch(**kwargs)
         zero_K = torch.zeros(self.batch, self.N, self.u_dim, self.x_dim, dtype=e.dtype, device=e.device)
         e.status.zero_()

@@ -171,7 +171,7 @@ class UserSource:
     """What models.Custom and costs.Custom share: the validation and registration of a run-time compiled source (`noun`: model |
     cost) and the way their host-side evaluations put numpy arrays on the device."""
 
-    _table = None                                            # a cost's per-step table (costs.Custom(table=)): [N, W] or [B, N, W]
+    _table = None                                            # the per-step table (Custom(table=)): [N, W] or [B, N, W]
 
     def _register(self, noun, create, x_dim, u_dim, params, source, table=None):
         self.x_dim, self.u_dim = int(x_dim), int(u_dim)
@@ -227,10 +227,66 @@ class Custom(UserSource, Model):
     the contract of csrc/user_model_ad.hpp).  The library compiles it at run time for gfx950 (hiprtc) into the rollout kernel of
     the built-in models, the dense closed loop, a row-wise step and a linearisation on forward-mode dual numbers -- A, B come
     from `step` itself, there is no get_AB to write.  `params` is [P] (shared) or [B, P] (one row per trajectory), P <= 16.
-    Only the (x_dim, u_dim) pairs with the row-per-lane kernels are served (`isls._capi.supported_dims()`)."""
+    Only the (x_dim, u_dim) pairs with the row-per-lane kernels are served (`isls._capi.supported_dims()`).
 
-    def __init__(self, x_dim, u_dim, params, source):
-        self.model_id = self._register("model", capi.user_model_create, x_dim, u_dim, params, source)
+    Per-step data (a payload dropped at step 40, a wind forecast, a variable time step, a mode schedule, x+ = A_t x + B_t u):
+    `table` is [N, W] (shared by the batch) or [B, N, W] (one per trajectory), 1 <= W <= 16, and `source` then defines the
+    five-argument form
+
+        template <typename S, typename P>
+        __device__ void step(const S *x, const S *u, const P *par, const P *row, S *xn);
+
+    `row` the W words of step t: plain P, never differentiated.  `set_table` replaces the values (same shape) between two calls of
+    a solver -- a receding-horizon window, a new forecast: no compile, one copy into the buffer the engine holds.  On the device
+    the table rides behind the parameters, [par | row 0 | ... | row N-1] (`device_params`; include/isls_hip.h).  Such a model is
+    linearised at every iteration.  Served: solve / iterate_once_dp / solve_ilqr / ilqr_admm, mpc (model_table_future=,
+    plant_table=) and sample_nominal; monte_carlo, isls_admm and the dense closed loop refuse it."""
+
+    def __init__(self, x_dim, u_dim, params, source, table=None):
+        par, tab = np.atleast_1d(np.asarray(params)), None if table is None else np.asarray(table)
+        if tab is not None and par.ndim == 2 and tab.ndim == 3 and tab.shape[0] != par.shape[0]:
+            raise ValueError(f"per-trajectory params [{par.shape[0]}, P] and a per-trajectory table [{tab.shape[0]}, N, W]: "
+                             "one row and one table per trajectory")
+        self.model_id = self._register("model", capi.user_model_create, x_dim, u_dim, params, source, table=table)
+
+    @property
+    def table(self):
+        """The host copy of the per-step table ([N, W] or [B, N, W]; None: a model without one)."""
+        return self._table
+
+    def set_table(self, table):
+        """New values for the table, of the shape it has: the next call of a solver on any iSLS holding this model uses them --
+        no compile, and the engine copies them into the device buffer it already has."""
+        if self._table is None:
+            raise ValueError("set_table: this model was built without a table")
+        table = np.array(table, dtype=np.float64, order="C")
+        if table.shape != self._table.shape:
+            raise ValueError(f"set_table: the table is {self._table.shape}, got {table.shape} (a new shape is a new Custom)")
+        self._table, self._table_version = table, self._table_version + 1
+
+    @property
+    def n_tab(self):
+        """Words per step of the table (0: none)."""
+        return 0 if self._table is None else int(self._table.shape[-1])
+
+    def device_params(self, batch=None, N=None, table=None):
+        """The buffer a launch names as the model's parameters: params() for a model without a table, else [P + N W] (shared
+        parameters and a shared table) or [batch, P + N W] -- [par | row 0 | ... | row N-1], a shared part replicated where the
+        other is per trajectory.  `table`: another table of the same form in the object's place (a plant's)."""
+        tab = self._table if table is None else np.asarray(table, dtype=np.float64)
+        if tab is None:
+            return self._params
+        par = self._params
+        if N is not None and tab.shape[-2] != N:
+            raise ValueError(f"the model's table has {tab.shape[-2]} steps, the horizon {N}")
+        rows = par.shape[0] if par.ndim == 2 else (tab.shape[0] if tab.ndim == 3 else None)
+        if rows is None:
+            return np.concatenate([par, tab.reshape(-1)])
+        if batch is not None and rows != batch:
+            raise ValueError(f"per-trajectory params / table of {rows} trajectories, the batch has {batch}")
+        if tab.ndim == 3 and tab.shape[0] != rows:
+            raise ValueError(f"a per-trajectory table [{tab.shape[0]}, N, W] needs {tab.shape[0]} trajectories, got {rows}")
+        return np.concatenate([np.broadcast_to(par, (rows, par.shape[-1])), np.broadcast_to(tab, (rows,) + tab.shape[-2:]).reshape(rows, -1)], axis=1)
 
     def code(self, dtype=np.float64):
         """The gfx950 code object of the model (all its kernels) for dtype."""
@@ -239,9 +295,41 @@ class Custom(UserSource, Model):
     def _load(self, dtype):
         capi.user_model_load(self.model_id, dtype)
 
-    def __call__(self, x, u):
-        """x [..., n], u [..., m] -> f(x, u) [..., n] (numpy, fp64), evaluated on the device."""
+    def _call_table(self, x, u, t):
+        """__call__ of a table model: trajectories [N, n] / [B, N, n] step with row t at step t; anything else needs t=."""
+        tab, n, m = self._table, self.x_dim, self.u_dim
+        N, per = tab.shape[-2], self._params.ndim == 2 or tab.ndim == 3
+        lead = np.broadcast_shapes(x.shape[:-1], u.shape[:-1])
+        R = int(np.prod(lead)) if lead else 1
+        xs, us = np.broadcast_to(x, lead + (n,)).reshape(R, n), np.broadcast_to(u, lead + (m,)).reshape(R, m)
+        if t is None:
+            if len(lead) not in (1, 2) or lead[-1] != N:
+                raise ValueError(f"a table model steps trajectories [{N}, n] / [B, {N}, n] with row t at step t; single rows need t=")
+            run, groups, tix = N, R // N, None
+        else:
+            tix = np.ascontiguousarray(np.broadcast_to(np.asarray(t), lead).reshape(R), dtype=np.int32)
+            if tix.size and (tix.min() < 0 or tix.max() >= N):
+                raise ValueError(f"t: steps in [0, {N}), got [{tix.min()}, {tix.max()}]")
+            run, groups = 1, R
+        if not per:
+            groups = None
+        import torch
+        from .engine import kernels
+        dev = torch.device("cuda", torch.cuda.current_device())
+        self._load(np.float64)
+        dt = lambda a: torch.as_tensor(np.array(a, dtype=np.float64, order="C"), device=dev)   # noqa: E731
+        xn = torch.empty(R, n, dtype=torch.float64, device=dev)
+        kernels().user_model_step_tab(self.model_id, dt(self.device_params(groups, N)), dt(xs), dt(us), xn, run, N,
+                                      t=None if tix is None else torch.as_tensor(tix, device=dev),
+                                      stream=torch.cuda.current_stream().cuda_stream)
+        return xn.cpu().numpy().reshape(lead + (n,))
+
+    def __call__(self, x, u, t=None):
+        """x [..., n], u [..., m] -> f(x, u) [..., n] (numpy, fp64), evaluated on the device.  A table model: trajectories
+        [N, n] / [B, N, n] use row t at step t; single rows take t= (an int or an int array broadcastable to the rows)."""
         x, u = np.asarray(x, dtype=np.float64), np.asarray(u, dtype=np.float64)
+        if self._table is not None:
+            return self._call_table(x, u, t)
         lead = np.broadcast_shapes(x.shape[:-1], u.shape[:-1])
         R = int(np.prod(lead)) if lead else 1
         torch, kern, dev, (par, xs, us) = self._on_device(R, "{0} rows of x, u, got {1}",
@@ -251,10 +339,13 @@ class Custom(UserSource, Model):
         kern.user_model_step(self.model_id, par, xs, us, xn, stream=torch.cuda.current_stream().cuda_stream)
         return xn.cpu().numpy().reshape(lead + (self.x_dim,))
 
-    def get_AB(self, x, u):
+    def get_AB(self, x, u, t=None):
         """A [N,n,n], B [N,n,m] along x [N,n], u [N,m] in the reference's convention (or [Bt,N,...] for a batch), on the device
-        by the same dual-number kernel the solver linearises with."""
+        by the same dual-number kernel the solver linearises with.  A table model: row t at step t; single rows x [n] / [R, n]
+        take t= and give A [n,n] / [R,n,n]."""
         x, u = np.asarray(x, dtype=np.float64), np.asarray(u, dtype=np.float64)
+        if self._table is not None:
+            return self._get_AB_table(x, u, t)
         single = x.ndim == 2
         xb, ub = (x[None], u[None]) if single else (x, u)
         Bt, N = xb.shape[:2]
@@ -264,3 +355,37 @@ class Custom(UserSource, Model):
         kern.linearize(self.model_id, par, xs, us, A, Bm, stream=torch.cuda.current_stream().cuda_stream)
         A, Bm = A.cpu().numpy(), Bm.cpu().numpy()
         return (A[0], Bm[0]) if single else (A, Bm)
+
+    def _get_AB_table(self, x, u, t):
+        tab, n, m = self._table, self.x_dim, self.u_dim
+        N = tab.shape[-2]
+        if t is not None:
+            # single rows: each is a one-step trajectory whose table is row t of the model's, at step 0
+            lead = np.broadcast_shapes(x.shape[:-1], u.shape[:-1])
+            R = int(np.prod(lead)) if lead else 1
+            tix = np.broadcast_to(np.asarray(t), lead).reshape(R).astype(np.int64)
+            if tix.size and (tix.min() < 0 or tix.max() >= N):
+                raise ValueError(f"t: steps in [0, {N}), got [{tix.min()}, {tix.max()}]")
+            if tab.ndim == 3 and tab.shape[0] != R:
+                raise ValueError(f"a per-trajectory table [{tab.shape[0]}, N, W] needs {tab.shape[0]} rows, got {R}")
+            rows = tab[tix] if tab.ndim == 2 else tab[np.arange(R), tix]
+            xb, ub = np.broadcast_to(x, lead + (n,)).reshape(R, 1, n), np.broadcast_to(u, lead + (m,)).reshape(R, 1, m)
+            par = self.device_params(R, 1, table=rows[:, None, :])
+            out = lambda a: a[:, 0].reshape(lead + a.shape[2:])   # noqa: E731
+        else:
+            if x.ndim not in (2, 3) or x.shape[-2] != N:
+                raise ValueError(f"a table model linearises trajectories [{N}, n] / [B, {N}, n] with row t at step t; single rows need t=")
+            single = x.ndim == 2
+            xb, ub = (x[None], u[None]) if single else (x, u)
+            par = self.device_params(xb.shape[0] if (self._params.ndim == 2 or tab.ndim == 3) else None, N)
+            out = lambda a: a[0] if single else a                 # noqa: E731
+        import torch
+        from .engine import kernels
+        dev = torch.device("cuda", torch.cuda.current_device())
+        self._load(np.float64)
+        dt = lambda a: torch.as_tensor(np.array(a, dtype=np.float64, order="C"), device=dev)   # noqa: E731
+        Bt, Nt = xb.shape[:2]
+        A = torch.zeros(Bt, Nt, n, n, dtype=torch.float64, device=dev)
+        Bm = torch.zeros(Bt, Nt, n, m, dtype=torch.float64, device=dev)
+        kernels().linearize(self.model_id, dt(par), dt(xb), dt(ub), A, Bm, stream=torch.cuda.current_stream().cuda_stream)
+        return out(A.cpu().numpy()), out(Bm.cpu().numpy())

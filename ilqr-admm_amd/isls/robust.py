@@ -280,6 +280,7 @@ def isls_admm(self, dim, get_AB=None, get_Cs=None, project_x=False, project_u=Fa
         # the column passes (isls_columns_*) take Cuu alone: a user cost's x-u cross terms would be dropped without a word
         raise capi.IslsError("isls_admm does not serve a user cost (costs.Custom): its column passes have no Cux term; use solve / "
                              "ilqr_admm, or hand the cost over as a callable with get_Cs")
+    self._refuse_table_model("isls_admm")                                      # its column roll-outs step the model with no notion of time
     B, N, n, m, C = self.batch, self.N, self.x_dim, self.u_dim, int(dim) + 1
     if not 1 <= dim <= n or C > capi.MAX_ROW_DIM:
         raise ValueError(f"dim must be in [1, {min(n, capi.MAX_ROW_DIM - 1)}]")

@@ -75,7 +75,7 @@ extern "C" {
  * model_par_sb = n_par).  Fast (n, m) pairs only (isls_dims_supported), cost model ISLS_COST_VIA; no model hint (lin_on). */
 #define ISLS_MODEL_USER_BASE 1024
 #define ISLS_USER_MAX_PAR 16        /* parameters of a user model, at most                                             */
-#define ISLS_USER_MAX_TAB 16        /* words per step of a user cost's table, at most (isls_user_cost_create_tab)      */
+#define ISLS_USER_MAX_TAB 16        /* words per step of a user cost's or a user model's table, at most (isls_user_*_create_tab) */
 #define ISLS_DTYPE_F64 0
 #define ISLS_DTYPE_F32 1
 
@@ -837,6 +837,32 @@ int isls_user_model_step_f64(int32_t id, int32_t R, const void *par, int64_t par
                              void *stream);
 int isls_user_model_step_f32(int32_t id, int32_t R, const void *par, int64_t par_sb, const void *x, const void *u, void *xn,
                              void *stream);
+
+/* A model with a per-step table of n_tab words (1 .. ISLS_USER_MAX_TAB): a schedule, a forecast, a variable time step, a linear
+ * time-varying system.  `source` then defines the five-argument form
+ *     template <typename S, typename P> __device__ void step(const S *x, const S *u, const P *par, const P *row, S *xn);
+ * `row` the n_tab words of step t (plain P: nothing is differentiated with respect to them); a source of the other form is a
+ * compile error.  The table travels stateless, behind the parameters in the buffer every argument block names as the model's
+ * (model_par / par), per trajectory or once for the batch:
+ *     [ par (n_par) | row 0 | row 1 | ... | row N-1 ],     batch stride 0 or n_par + N * n_tab.
+ * ISLS_ERR_ARG, before anything is compiled for a pair, loaded or launched: model_par == NULL, any other stride.  The values may
+ * change between two launches (a receding-horizon window): nothing is compiled or bound for them.
+ * Served: isls_rollout_ls_* (and the drivers that embed it: the row of a step arrives with the step's other operands, prefetched
+ * into a side record in LDS), isls_linearize_* (also inside isls_outer_advance_*), isls_sample_nominal_* / _fb_*, isls_mpc_step_*
+ * (the re-roll reads row t of model_par as it stands at the launch; the plant steps with row 0 of plant_par, the same layout,
+ * which need not reach further than that row: plant_sb == 0 or >= n_par + n_tab) and isls_user_model_step_tab_*.
+ * Not served, ISLS_ERR_UNSUPPORTED: isls_dense_closed_loop_*, isls_mc_closed_loop_* (fold the schedule into the state, or run the
+ * loop step by step).  ISLS_ERR_UNSUPPORTED from the create: n_tab outside [0, ISLS_USER_MAX_TAB]. */
+int isls_user_model_create_tab(const char *source, int32_t n, int32_t m, int32_t n_par, int32_t n_tab, int32_t *id);
+/* Words per step of the model's table (0: a model without one); ISLS_ERR_ARG: no such model. */
+int isls_user_model_n_tab(int32_t id);
+/* isls_user_model_step for a table model: the R state rows come in runs of `run` rows per parameter block (par: [par | N rows],
+ * par_sb = 0 or n_par + N * n_tab per run); row r steps with table row t[r] (t: R device words in [0, N)), or, t == NULL, with its
+ * place r % run in its run (run <= N).  A table model steps through this entry only, and only a table model does. */
+int isls_user_model_step_tab_f64(int32_t id, int32_t R, int32_t run, int32_t N, const void *par, int64_t par_sb, const int32_t *t,
+                                 const void *x, const void *u, void *xn, void *stream);
+int isls_user_model_step_tab_f32(int32_t id, int32_t R, int32_t run, int32_t N, const void *par, int64_t par_sb, const int32_t *t,
+                                 const void *x, const void *u, void *xn, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * User-written cost functions, compiled at run time for gfx950 like the user models.  `source` defines

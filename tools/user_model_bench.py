@@ -12,6 +12,8 @@ L = 20, J = 5, control box + the two keep-out rectangles).
   from closed forms on one side and dual numbers on the other);
 * the run-time compile of the Custom source (fp64, fresh source) and one `solve` iteration of the host slow path (the car as a
   numpy callable plus get_AB) at a small batch, for contrast.
+`--legs table` times the per-step table of a models.Custom instead: the car with its constants in `params` against the same car
+reading them from a shared [N, 2] table and from a [B, N, 2] table (table_legs).
 Prints the numbers and one JSON line."""
 import argparse
 import json
@@ -63,14 +65,86 @@ def timed(fn, reps):
     return a.elapsed_time(b) * 1e3 / reps            # us per call
 
 
+def car_with_push(c, table):
+    """The car of tests/user_models.py with two constants c[0] = dt and c[1] = a lateral push, read from `par` or from `row`: the
+    same arithmetic either way, so the forms differ in where the two words come from and in nothing else."""
+    sig = "const P *par, const P *row, S *xn" if table else "const P *par, S *xn"
+    return f"""template <typename S, typename P>
+__device__ void step(const S *x, const S *u, {sig}) {{
+    const P dt = {c}[0];
+    S sn, cs;
+    isls::sin_cos(x[2], sn, cs);
+    xn[0] = x[0] + dt * x[3] * cs;
+    xn[1] = x[1] + dt * x[3] * sn + {c}[1];
+    xn[2] = isls::py_mod(x[2] + dt * x[3] * u[0], P(2 * 3.14159265358979323846));
+    xn[3] = x[3] + dt * u[1];
+}}"""
+
+
+def table_legs(args):
+    """--legs table: the car with its constants in `params`, with a shared [N, 2] table (row = [dt, lateral push 0]) and with a
+    [B, N, 2] table of the same rows, one engine each from the same start; the rollout launch and the outer iteration of the
+    three alternate within this call.  The yardstick is the params form of the same call."""
+    from isls import models
+    B, N = args.batch, 200
+    cfg = P.config4(batch=B, N=N, seed=0)
+    rows = np.tile([cfg["dt"], 0.0], (N, 1))
+    forms = {"params": models.Custom(4, 2, rows[0], car_with_push("par", False)),
+             "table_shared": models.Custom(4, 2, [0.0], car_with_push("row", True), table=rows),
+             "table_per_traj": models.Custom(4, 2, [0.0], car_with_push("row", True), table=np.broadcast_to(rows, (B, N, 2)).copy())}
+    eng = {k: make(cfg, B, mdl).engine for k, mdl in forms.items()}
+    for x in eng.values():                            # realistic K, k and ADMM targets, the same for the three
+        x.run_outer()
+    torch.cuda.synchronize()
+    best0 = {k: x.best.clone() for k, x in eng.items()}
+
+    def ls(k):
+        eng[k].best.copy_(best0[k])
+        eng[k].rollout(20)
+    outs = {}
+    for k in eng:
+        ls(k)
+        torch.cuda.synchronize()
+        outs[k] = [t.clone() for t in (eng[k].xx, eng[k].xu, eng[k].cost_new, eng[k].best)]
+    ls_equal = {k: all(torch.equal(a, b) for a, b in zip(outs["params"], outs[k])) for k in eng if k != "params"}
+    ls_t, ot = {k: [] for k in eng}, {k: [] for k in eng}
+    for _ in range(args.rounds):
+        for k in eng:
+            ls(k)
+            ls_t[k].append(timed(lambda: ls(k), args.reps))
+
+    def outer(x):
+        x.run_outer()
+        x.advance()
+    for _ in range(args.rounds):
+        for k, x in eng.items():
+            ot[k].append(timed(lambda: outer(x), max(1, args.reps // 4)))
+    med = lambda v: float(np.median(v))               # noqa: E731
+    spread = lambda v: float(np.max(v) - np.min(v))   # noqa: E731
+    res = dict(legs="table", batch=B, N=N, L=20, J=5, rounds=args.rounds,
+               ls_us={k: med(v) for k, v in ls_t.items()}, ls_spread_us={k: spread(v) for k, v in ls_t.items()},
+               ls_bitwise_equal_to_params=ls_equal,
+               outer_us={k: med(v) for k, v in ot.items()}, outer_spread_us={k: spread(v) for k, v in ot.items()})
+    for k in eng:
+        print(f"{k:15s} B={B}: line search {res['ls_us'][k]:.1f} us (spread {res['ls_spread_us'][k]:.1f}), outer iteration "
+              f"{res['outer_us'][k]:.1f} us (spread {res['outer_spread_us'][k]:.1f})")
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--legs", choices=["model", "table"], default="model",
+                    help="model: built-in against Custom (the default); table: params form against the two table forms")
     args = ap.parse_args()
     from isls import models
     torch.cuda.set_device(0)
+    if args.legs == "table":
+        if args.rounds < 5:
+            ap.error("--legs table alternates the forms over at least 5 rounds")
+        return table_legs(args)
     B = args.batch
     cfg = P.config4(batch=B, N=200, seed=0)
     dt = cfg["dt"]
