@@ -319,20 +319,13 @@ def load_hip_library(path=None):
     lib.isls_timing_pause.argtypes = [C.c_void_p, C.c_int]
     lib.isls_timing_read_ms.restype = C.c_double
     lib.isls_timing_read_ms.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
-    lib.isls_user_model_create.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
-    lib.isls_user_model_create_tab.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
-    lib.isls_user_model_n_tab.argtypes = [C.c_int32]
-    lib.isls_user_model_log.restype = C.c_int64
-    lib.isls_user_model_log.argtypes = [C.c_int32, C.c_char_p, C.c_int64]
-    lib.isls_user_model_code.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int64)]
-    lib.isls_user_model_load.argtypes = [C.c_int32, C.c_int32]
-    lib.isls_user_cost_create.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
-    lib.isls_user_cost_create_tab.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
-    lib.isls_user_cost_n_tab.argtypes = [C.c_int32]
-    lib.isls_user_cost_log.restype = C.c_int64
-    lib.isls_user_cost_log.argtypes = [C.c_int32, C.c_char_p, C.c_int64]
-    lib.isls_user_cost_code.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int64)]
-    lib.isls_user_cost_load.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    src = [C.c_char_p, i32, i32, i32]                          # user models and user costs: (source, n, m, n_par)
+    for noun, ids in (("model", [i32]), ("cost", [i32, i32])):   # a cost's code / load take (cost id, model id)
+        for what, argtypes in (("create", src + [C.POINTER(i32)]), ("create_tab", src + [i32, C.POINTER(i32)]), ("n_tab", [i32]),
+                               ("log", [i32, C.c_char_p, C.c_int64]), ("code", ids + [i32, C.c_void_p, C.POINTER(C.c_int64)]),
+                               ("load", ids + [i32])):
+            getattr(lib, f"isls_user_{noun}_{what}").argtypes = argtypes
+        getattr(lib, f"isls_user_{noun}_log").restype = C.c_int64
     return lib
 
 
@@ -388,7 +381,7 @@ def _dtype_code(dtype):
 
 
 class _UserKind:
-    """The four entry points of one kind of source (`noun`: model | cost).  A cost's code and load also take the model it is
+    """The entry points of one kind of source (`noun`: model | cost).  A cost's code and load also take the model it is
     paired with (-1: expansion and value only); ids of the two kinds count independently from `base`."""
 
     def __init__(self, noun, base):
@@ -420,6 +413,13 @@ class _UserKind:
         self.ids[key] = uid.value
         return uid.value
 
+    def n_tab(self, uid):
+        """Words per step of the source's table (0: a source without one)."""
+        rc = self._fn("n_tab")(C.c_int32(uid))
+        if rc < 0:
+            raise IslsError(f"isls_user_{self.noun}_n_tab -> {rc}: {library().isls_error_string(rc).decode()}")
+        return rc
+
     def code(self, uid, *model, dtype):
         args, size = [C.c_int32(v) for v in (uid,) + model] + [_dtype_code(dtype)], C.c_int64(0)
         rc = self._fn("code")(*args, None, C.byref(size))
@@ -438,6 +438,7 @@ class _UserKind:
 
 _USER_MODEL, _USER_COST = _UserKind("model", MODEL_USER_BASE), _UserKind("cost", COST_USER_BASE)
 user_model_log, user_cost_log = _USER_MODEL.log, _USER_COST.log
+user_cost_n_tab = _USER_COST.n_tab
 
 
 def user_model_create(source, n, m, n_par, n_tab=0):
@@ -449,12 +450,7 @@ def user_model_create(source, n, m, n_par, n_tab=0):
 
 def user_model_n_tab(model_id):
     """Words per step of the model's table (0: a model without one, and every built-in model)."""
-    if int(model_id) < MODEL_USER_BASE:
-        return 0
-    rc = library().isls_user_model_n_tab(C.c_int32(model_id))
-    if rc < 0:
-        raise IslsError(f"isls_user_model_n_tab -> {rc}: {library().isls_error_string(rc).decode()}")
-    return rc
+    return _USER_MODEL.n_tab(model_id) if int(model_id) >= MODEL_USER_BASE else 0
 
 
 def user_model_code(model_id, dtype=np.float64):
@@ -472,14 +468,6 @@ def user_cost_create(source, n, m, n_par, n_tab=0):
     it is used with); the same (source, n, m, n_par, n_tab) is registered once per process.  n_tab > 0: the cost reads a table
     of that many words per step (isls_user_cost_create_tab; the six-argument `stage`).  IslsError carries the compile log."""
     return _USER_COST.create(source, n, m, n_par, n_tab)
-
-
-def user_cost_n_tab(cost_id):
-    """Words per step of the cost's table (0: a cost without one)."""
-    rc = library().isls_user_cost_n_tab(C.c_int32(cost_id))
-    if rc < 0:
-        raise IslsError(f"isls_user_cost_n_tab -> {rc}: {library().isls_error_string(rc).decode()}")
-    return rc
 
 
 def user_cost_code(cost_id, model=-1, dtype=np.float64):

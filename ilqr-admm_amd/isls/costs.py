@@ -82,20 +82,6 @@ class Custom(UserSource):
     def __init__(self, x_dim, u_dim, params, source, table=None):
         self.cost_model = self._register("cost", capi.user_cost_create, x_dim, u_dim, params, source, table=table)
 
-    @property
-    def table(self):
-        """The host copy of the per-step table ([N, W] or [B, N W]; None: a cost without one)."""
-        return self._table
-
-    def set_table(self, table):
-        """New values for the table, of the shape it has: the next call of a solver on any iSLS holding this cost uses them."""
-        if self._table is None:
-            raise ValueError("set_table: this cost was built without a table")
-        table = np.array(table, dtype=np.float64, order="C")
-        if table.shape != self._table.shape:
-            raise ValueError(f"set_table: the table is {self._table.shape}, got {table.shape} (a new shape is a new costs.Custom)")
-        self._table, self._table_version = table, self._table_version + 1
-
     def code(self, model=None, dtype=np.float64):
         """The gfx950 code object of the cost for dtype: with `model` (an isls.models object or a model id) every kernel of the
         pair -- line search, expansion, value --, without one the expansion and the value."""

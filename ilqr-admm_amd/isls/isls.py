@@ -101,7 +101,7 @@ class iSLS(Base):
                 self.engine.set_cost_model(function.cost_model, function.params())
             else:
                 self.engine.set_cost_model(function.cost_model, function.params(), table=table)
-                self._table_version = function._table_version
+                self._cost_table_version = function._table_version
         elif callable(function):
             # the reference's `cost_function(x[L,N,n], u[L,N,m]) -> [L]` (isls.py:360): evaluated on the host for every
             # candidate of the line search; its expansion comes from the caller's get_Cs
@@ -110,29 +110,21 @@ class iSLS(Base):
             raise TypeError("cost_function must be None, an isls.costs object or a callable cost(x, u)")
 
     def _sync_tables(self):
-        """set_table on the model or on the cost since this object last looked: the model's rows first, so that the cost of the
-        nominal is evaluated with both in place."""
-        self._sync_model_table()
-        self._sync_cost_table()
+        """set_table on the model or on the cost since this object last looked: the new values go INTO the buffer the engine holds
+        (one copy_, no compile, no allocation; cached argument blocks stay valid).  The model's rows first (update_model_table
+        marks the linearisation stale), so that the cost of the nominal is then evaluated again with both in place."""
+        if not self._host_model:
+            self._sync_table(self._forward_model, "_model_table_version", self.engine.update_model_table)
+        if not self._host_cost and self._sync_table(self._cost_function, "_cost_table_version", self.engine.update_cost_table):
+            self.engine.evaluate_cost()
 
-    def _sync_cost_table(self):
-        """costs.Custom.set_table since this object last looked: the new values go INTO the engine's device table (no compile, no
-        allocation, cached argument blocks stay valid) and the nominal's cost is evaluated again with them."""
-        f = self._cost_function
-        if self._host_cost or getattr(f, "table", None) is None or f._table_version == self._table_version:
-            return
-        self.engine.update_cost_table(f.table)
-        self._table_version = f._table_version
-        self.engine.evaluate_cost()
-
-    def _sync_model_table(self):
-        """models.Custom.set_table since this object last looked: the new rows go INTO the engine's model_par (one copy_, no
-        compile, cached argument blocks stay valid)."""
-        mdl = self._forward_model
-        if self._host_model or getattr(mdl, "table", None) is None or mdl._table_version == self._model_table_version:
-            return
-        self.engine.update_model_table(mdl.table)
-        self._model_table_version = mdl._table_version
+    def _sync_table(self, obj, seen, update):
+        """update(obj.table) if obj has a table whose version is not the one this object last saw (the attribute `seen`)"""
+        if getattr(obj, "table", None) is None or obj._table_version == getattr(self, seen):
+            return False
+        update(obj.table)
+        setattr(self, seen, obj._table_version)
+        return True
 
     def _refuse_table_model(self, what):
         """The entry points a models.Custom(table=) is not served by: their kernels step the model with no notion of time."""

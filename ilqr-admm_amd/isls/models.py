@@ -169,12 +169,12 @@ class TassaCar(Model):
 
 class UserSource:
     """What models.Custom and costs.Custom share: the validation and registration of a run-time compiled source (`noun`: model |
-    cost) and the way their host-side evaluations put numpy arrays on the device."""
+    cost), its per-step table and the way their host-side evaluations put numpy arrays on the device."""
 
     _table = None                                            # the per-step table (Custom(table=)): [N, W] or [B, N, W]
 
     def _register(self, noun, create, x_dim, u_dim, params, source, table=None):
-        self.x_dim, self.u_dim = int(x_dim), int(u_dim)
+        self._noun, self.x_dim, self.u_dim = noun, int(x_dim), int(u_dim)
         if table is not None:
             table = np.array(table, dtype=np.float64, order="C")
             if table.ndim not in (2, 3) or table.shape[-1] < 1:
@@ -201,17 +201,39 @@ class UserSource:
     def params(self):
         return self._params
 
-    def _on_device(self, rows, need, *arrays):
+    @property
+    def table(self):
+        """The host copy of the per-step table ([N, W] or [B, N, W]; None: a source without one)."""
+        return self._table
+
+    def set_table(self, table):
+        """New values for the table, of the shape it has: the next call of a solver on any iSLS holding this object uses them --
+        no compile, and the engine copies them into the device buffer it already has."""
+        if self._table is None:
+            raise ValueError(f"set_table: this {self._noun} was built without a table")
+        table = np.array(table, dtype=np.float64, order="C")
+        if table.shape != self._table.shape:
+            cls = "costs.Custom" if self._noun == "cost" else "Custom"
+            raise ValueError(f"set_table: the table is {self._table.shape}, got {table.shape} (a new shape is a new {cls})")
+        self._table, self._table_version = table, self._table_version + 1
+
+    @property
+    def n_tab(self):
+        """Words per step of the table (0: none)."""
+        return 0 if self._table is None else int(self._table.shape[-1])
+
+    def _on_device(self, rows, need, *arrays, par=None):
         """(torch, kernels, device, [parameters, *arrays] as fp64 device tensors) for an evaluation of `rows` trajectories on the
-        current device, the module put there by _load(); per-trajectory parameters need one row each (`need`: the error's words)."""
+        current device, the module put there by _load(); per-trajectory parameters need one row each (`need`: the error's words).
+        `par`: the buffer that goes in the parameters' place (a table model's device_params, which has made these checks)."""
         import torch
         from .engine import kernels
-        par = self._params
-        if par.ndim == 2 and par.shape[0] != rows:
-            raise ValueError(f"per-trajectory params [{par.shape[0]}, P] need " + need.format(par.shape[0], rows))
-        tab = self._table
-        if tab is not None and tab.ndim == 3 and tab.shape[0] != rows:
-            raise ValueError(f"a per-trajectory table [{tab.shape[0]}, N, W] needs " + need.format(tab.shape[0], rows))
+        if par is None:
+            par, tab = self._params, self._table
+            if par.ndim == 2 and par.shape[0] != rows:
+                raise ValueError(f"per-trajectory params [{par.shape[0]}, P] need " + need.format(par.shape[0], rows))
+            if tab is not None and tab.ndim == 3 and tab.shape[0] != rows:
+                raise ValueError(f"a per-trajectory table [{tab.shape[0]}, N, W] needs " + need.format(tab.shape[0], rows))
         dev = torch.device("cuda", torch.cuda.current_device())
         self._load(np.float64)
         return torch, kernels(), dev, [torch.as_tensor(np.array(a, dtype=np.float64, order="C"), device=dev) for a in (par,) + arrays]
@@ -248,26 +270,6 @@ class Custom(UserSource, Model):
             raise ValueError(f"per-trajectory params [{par.shape[0]}, P] and a per-trajectory table [{tab.shape[0]}, N, W]: "
                              "one row and one table per trajectory")
         self.model_id = self._register("model", capi.user_model_create, x_dim, u_dim, params, source, table=table)
-
-    @property
-    def table(self):
-        """The host copy of the per-step table ([N, W] or [B, N, W]; None: a model without one)."""
-        return self._table
-
-    def set_table(self, table):
-        """New values for the table, of the shape it has: the next call of a solver on any iSLS holding this model uses them --
-        no compile, and the engine copies them into the device buffer it already has."""
-        if self._table is None:
-            raise ValueError("set_table: this model was built without a table")
-        table = np.array(table, dtype=np.float64, order="C")
-        if table.shape != self._table.shape:
-            raise ValueError(f"set_table: the table is {self._table.shape}, got {table.shape} (a new shape is a new Custom)")
-        self._table, self._table_version = table, self._table_version + 1
-
-    @property
-    def n_tab(self):
-        """Words per step of the table (0: none)."""
-        return 0 if self._table is None else int(self._table.shape[-1])
 
     def device_params(self, batch=None, N=None, table=None):
         """The buffer a launch names as the model's parameters: params() for a model without a table, else [P + N W] (shared
@@ -311,17 +313,10 @@ class Custom(UserSource, Model):
             if tix.size and (tix.min() < 0 or tix.max() >= N):
                 raise ValueError(f"t: steps in [0, {N}), got [{tix.min()}, {tix.max()}]")
             run, groups = 1, R
-        if not per:
-            groups = None
-        import torch
-        from .engine import kernels
-        dev = torch.device("cuda", torch.cuda.current_device())
-        self._load(np.float64)
-        dt = lambda a: torch.as_tensor(np.array(a, dtype=np.float64, order="C"), device=dev)   # noqa: E731
+        torch, kern, dev, (par, xs, us) = self._on_device(R, None, xs, us, par=self.device_params(groups if per else None, N))
         xn = torch.empty(R, n, dtype=torch.float64, device=dev)
-        kernels().user_model_step_tab(self.model_id, dt(self.device_params(groups, N)), dt(xs), dt(us), xn, run, N,
-                                      t=None if tix is None else torch.as_tensor(tix, device=dev),
-                                      stream=torch.cuda.current_stream().cuda_stream)
+        kern.user_model_step_tab(self.model_id, par, xs, us, xn, run, N, t=None if tix is None else torch.as_tensor(tix, device=dev),
+                                 stream=torch.cuda.current_stream().cuda_stream)
         return xn.cpu().numpy().reshape(lead + (n,))
 
     def __call__(self, x, u, t=None):
@@ -379,13 +374,9 @@ class Custom(UserSource, Model):
             xb, ub = (x[None], u[None]) if single else (x, u)
             par = self.device_params(xb.shape[0] if (self._params.ndim == 2 or tab.ndim == 3) else None, N)
             out = lambda a: a[0] if single else a                 # noqa: E731
-        import torch
-        from .engine import kernels
-        dev = torch.device("cuda", torch.cuda.current_device())
-        self._load(np.float64)
-        dt = lambda a: torch.as_tensor(np.array(a, dtype=np.float64, order="C"), device=dev)   # noqa: E731
         Bt, Nt = xb.shape[:2]
+        torch, kern, dev, (par, xs, us) = self._on_device(Bt, None, xb, ub, par=par)
         A = torch.zeros(Bt, Nt, n, n, dtype=torch.float64, device=dev)
         Bm = torch.zeros(Bt, Nt, n, m, dtype=torch.float64, device=dev)
-        kernels().linearize(self.model_id, dt(par), dt(xb), dt(ub), A, Bm, stream=torch.cuda.current_stream().cuda_stream)
+        kern.linearize(self.model_id, par, xs, us, A, Bm, stream=torch.cuda.current_stream().cuda_stream)
         return out(A.cpu().numpy()), out(Bm.cpu().numpy())

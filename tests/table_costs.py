@@ -54,6 +54,29 @@ __device__ S stage(const S *x, const S *u, const P *par, int t, int N) {{
 '''
 
 
+def generic_source(n, m, W, table):
+    """A cost at any (n, m) whose W constants c_k come from `row` (table=True) or from `par`, every one of them used: the same
+    arithmetic either way, so a table whose every row repeats the constants must give the bits of the `par` form."""
+    c = "row" if table else "par"
+    sig = "const P *par, const P *row, int t, int N" if table else "const P *par, int t, int N"
+    return f'''
+template <typename S, typename P>
+__device__ S stage(const S *x, const S *u, {sig}) {{
+    S c = S(0);
+    for (int k = 0; k < {W}; ++k) {{
+        const S d = x[k % {n}] - {c}[k];
+        c += d * ({c}[(k + 1) % {W}] * d);
+    }}
+    for (int r = 0; r < {m}; ++r) c += u[r] * ({c}[{W} - 1] * u[r]);
+    return c;
+}}
+'''
+
+
+def generic_consts(W):
+    return 0.3 + 0.1 * np.arange(W)
+
+
 def make_table(rng, N, n, B=None, terminal=20.0, shared_weights=False):
     """[N, W] (B None) or [B, N, W]: every row of every trajectory distinct, the last row's weights `terminal` times heavier;
     shared_weights: the trajectories differ in z_t only (iSLS.set_cost_variables takes per-trajectory via points with one Q table)"""

@@ -3,7 +3,8 @@
 The exact comparator everywhere is the built-in via-point cost with one via point per step (n_via = N, seq = arange(N)), which
 tests/table_costs.py restates as a table cost: value and expansion against it and against numpy, the line search against
 ISLS_COST_VIA in every loop form of the search (tail only, first steady-state trip, longer), with a shared and a per-trajectory
-table, with the fused ADMM update and with a mispredicted winner; then the class surface (solve, ilqr_admm), set_table against a
+table, with the fused ADMM update and with a mispredicted winner, and bit for bit against the same constants read from `params`
+at the row widths that take one and two loads per lane; then the class surface (solve, ilqr_admm), set_table against a
 fresh object, and __call__ / get_Cs against numpy.  Every row of every table is distinct and the last row is the heavy one, so a
 step off by one, a wrong clamp at N - 1 or a wrong batch stride shows."""
 import numpy as np
@@ -193,6 +194,48 @@ def test_line_search_with_a_mispredicted_winner():
     missed = same & (ec.best != L - 1) & ((ec.status & capi.ST_LS_REJECT) == 0)
     assert int(missed.sum()) >= 1
     assert not torch.equal(ec.xx[missed], ec.xhat[missed])     # the winner, not the nominal handed back
+
+
+@pytest.mark.parametrize("n, m, W, MW", [(4, 2, 1, 0), (4, 2, 9, 0), (4, 2, 16, 0), (9, 3, 1, 0), (9, 3, 9, 0), (9, 3, 16, 0), (4, 2, 9, 16)])
+def test_line_search_bitwise_against_the_params_form(n, m, W, MW):
+    """A cost whose W constants come from a table that repeats them in every row against the same cost reading them from `params`:
+    the same arithmetic, so the line search gives the same bits, fp64 -- the same words reach `stage`, nothing more: every row
+    is the same, so which step or trajectory a row belongs to is what the comparisons above see, not this one.  W = 9 and 16 take
+    two loads per lane in an 8-lane slot (L = 1), W = 9 leaves the second one partly past the row's end; N = 2: the tail loop
+    alone, N = 5: the first steady-state trip; B = 5: a partial last wavefront at L = 20.  MW = 16: a table model of that width
+    under the table cost, against both in `params` -- side records of unequal widths holding different constants.  A case's time
+    is its two run-time compiles (one program per form; about 15 s at (9, 3))."""
+    import table_models as tm
+    from isls import costs, models
+    from isls.engine import Engine
+    B, c, mc = 5, tc.generic_consts(W), tm.generic_consts(MW)
+    for N in (2, 5):
+        sides = []
+        for table in (False, True):
+            rows = (lambda v: np.tile(v, (N, 1))) if table else (lambda v: None)
+            cst = costs.Custom(n, m, [0.0] if table else c, tc.generic_source(n, m, W, table), table=rows(c))
+            if MW:
+                mdl = models.Custom(n, m, [0.0] if table else mc, tm.generic_source(n, m, MW, table), table=rows(mc))
+                sides.append((mdl.model_id, mdl.device_params(B, N), cst))
+            else:
+                mdl = models.CarSimple(0.1) if n == 4 else models.Planar3R(0.05)
+                sides.append((mdl.model_id, mdl.params(), cst))
+        for L in (1, 20):
+            out = []
+            for model_id, par, cst in sides:
+                rng = np.random.default_rng(7)
+                e = Engine(B, N, n, m)
+                e.set_model(model_id, par)
+                e.set_cost_model(cst.cost_model, cst.params(), table=cst.table)
+                e.K.copy_(e._t(0.05 * rng.standard_normal((B, N, m, n))))
+                e.k.copy_(e._t(0.1 * rng.standard_normal((B, N, m))))
+                e.set_nominal(0.3 * rng.standard_normal((B, N, n)), 0.1 * rng.standard_normal((B, N, m)))
+                ca = torch.zeros(B, L, dtype=e.dtype, device=e.device)
+                e.rollout(L, cost_all=ca)
+                out.append([t.cpu().numpy().copy() for t in (e.xx, e.xu, e.cost_new, e.best, ca)])
+            assert np.isfinite(out[0][4]).all() and (out[0][4] > 0).all()
+            for name, p, q in zip(("xx", "xu", "cost_new", "best", "cost_all"), *out):
+                assert np.array_equal(p, q), (N, L, name)
 
 
 # ---- class surface -------------------------------------------------------------------------------------------------------------
