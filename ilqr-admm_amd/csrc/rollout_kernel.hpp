@@ -1298,6 +1298,20 @@ struct UserExpP {
     int64_t tab_sb;
 };
 
+// arguments of user_constraint_update_kernel (user_cost.hpp): the arrays of isls_constraint_update_args
+template <typename T>
+struct UserConP {
+    int B, N, update;              // update: 0 evaluates only (viol, viol_prev, g_out), the table is not written
+    const T *par;
+    int64_t par_sb;
+    T *tab;                        // [B, N, W + K + 1]: step t of trajectory b at tab + b * tab_sb + t * NTAB
+    int64_t tab_sb;
+    const T *xhat, *uhat;
+    T *viol, *viol_prev, *g_out;   // [B], [B], [B, N, K] (nullable)
+    T eta, phi, mu_max;
+    const int32_t *active;
+};
+
 #ifndef __HIPCC_RTC__
 // the line search with a user model, a user cost or both (user_rtc.hip): the same plan, launched from the run-time compiled
 // module of the (model, cost) pair

@@ -1,6 +1,7 @@
-// user_cost.hip -- user-written cost functions: the launches of a cost's own kernels -- expansion and value (the device side is
-// user_cost.hpp) -- and the isls_user_cost_* entry points.  Registry, run-time compilation, module loading and the line search
-// are user_rtc.hip's: the programs of a cost are the keys (model or none, cost) there, and every one of them holds these two kernels.
+// user_cost.hip -- user-written cost functions: the launches of a cost's own kernels -- expansion, value and, for a cost with
+// constraints, the multiplier update (the device side is user_cost.hpp) -- and the isls_user_cost_* entry points.  Registry,
+// run-time compilation, module loading and the line search are user_rtc.hip's: the programs of a cost are the keys (model or
+// none, cost) there, and every one of them holds these kernels.
 #include "user_rtc.hpp"
 
 namespace isls {
@@ -64,6 +65,36 @@ int launch_expand_user_cost(const isls_expand_args &a, void *Cux, hipStream_t s)
 template int launch_expand_user_cost<double>(const isls_expand_args &, void *, hipStream_t);
 template int launch_expand_user_cost<float>(const isls_expand_args &, void *, hipStream_t);
 
+
+// ---- the multiplier and penalty update of a cost with constraints (user_constraint_update_kernel, user_cost.hpp) ----------------
+template <typename T>
+static int launch_constraint_update(const isls_constraint_update_args &a, hipStream_t s)
+{
+    if (a.B < 0 || a.N < 1 || !a.cost_par || a.cost_par_sb < 0 || !a.tab || !a.xhat || !a.uhat || !a.viol || !a.viol_prev)
+        return ISLS_ERR_ARG;
+    int n, m;
+    int rc = urtc::dims(urtc::KIND_COST, a.cost_model, &n, &m);
+    if (rc != ISLS_OK || n != a.n || m != a.m || urtc::n_con(a.cost_model) <= 0) return ISLS_ERR_ARG;
+    // the multipliers are state of a trajectory: one table each
+    if (a.tab_sb != (int64_t)a.N * urtc::n_tab(a.cost_model) && a.B > 1) return ISLS_ERR_ARG;
+    if (a.update && !(a.phi >= 1.0 && a.mu_max >= 0.0 && a.eta >= 0.0)) return ISLS_ERR_ARG;
+    if (a.B == 0) return ISLS_OK;
+    const std::vector<hipFunction_t> *fns;
+    const urtc::Program *pg;
+    if ((rc = urtc::prepare(urtc::kNone, a.cost_model, urtc::dtype_of<T>(), n, m, s, &fns, &pg)) != ISLS_OK) return rc;
+    if (pg->con < 0) return ISLS_ERR_ARG;
+    UserConP<T> p;
+    p.B = a.B; p.N = a.N; p.update = a.update ? 1 : 0;
+    p.par = (const T *)a.cost_par; p.par_sb = a.cost_par_sb;
+    p.tab = (T *)a.tab; p.tab_sb = a.tab_sb;
+    p.xhat = (const T *)a.xhat; p.uhat = (const T *)a.uhat;
+    p.viol = (T *)a.viol; p.viol_prev = (T *)a.viol_prev; p.g_out = (T *)a.g_out;
+    p.eta = (T)a.eta; p.phi = (T)a.phi; p.mu_max = (T)a.mu_max;
+    p.active = a.active;
+    void *args[] = {&p};
+    return urtc::launch((*fns)[pg->con], a.B, 0, s, args);
+}
+
 }  // namespace isls
 
 using namespace isls;
@@ -80,7 +111,14 @@ ISLS_API int isls_user_cost_create_tab(const char *source, int32_t n, int32_t m,
     return urtc::create(urtc::KIND_COST, source, n, m, n_par, n_tab, id);
 }
 
+ISLS_API int isls_user_cost_create_con(const char *source, int32_t n, int32_t m, int32_t n_par, int32_t n_tab, int32_t n_con, int32_t *id)
+{
+    return urtc::create(urtc::KIND_COST, source, n, m, n_par, n_tab, id, n_con);
+}
+
 ISLS_API int isls_user_cost_n_tab(int32_t id) { return urtc::n_tab(id); }
+
+ISLS_API int isls_user_cost_n_con(int32_t id) { return urtc::n_con(id); }
 
 ISLS_API int64_t isls_user_cost_log(int32_t id, char *buf, int64_t len) { return urtc::copy_log(urtc::KIND_COST, id, buf, len); }
 
@@ -123,4 +161,13 @@ ISLS_API int isls_user_cost_expand_f64(const isls_expand_args *a, void *Cux, voi
 ISLS_API int isls_user_cost_expand_f32(const isls_expand_args *a, void *Cux, void *stream)
 {
     return a && is_user_cost(a->cost_model) ? launch_expand_user_cost<float>(*a, Cux, (hipStream_t)stream) : ISLS_ERR_ARG;
+}
+
+ISLS_API int isls_user_constraint_update_f64(const isls_constraint_update_args *a, void *stream)
+{
+    return a && is_user_cost(a->cost_model) ? launch_constraint_update<double>(*a, (hipStream_t)stream) : ISLS_ERR_ARG;
+}
+ISLS_API int isls_user_constraint_update_f32(const isls_constraint_update_args *a, void *stream)
+{
+    return a && is_user_cost(a->cost_model) ? launch_constraint_update<float>(*a, (hipStream_t)stream) : ISLS_ERR_ARG;
 }

@@ -11,6 +11,11 @@
 // its stage cost --, user_expand_kernel and user_cost_value_kernel.
 // With ISLS_USER_COST_NTAB the user's stage takes the W words of step t as `const P *row` behind `par` (plain P: nothing is
 // differentiated with respect to them); a source of the other form than its registration says does not compile.
+// With ISLS_USER_COST_NCON = K > 0 the source also defines
+//     template <typename S, typename P> __device__ void constraint(const S *x, const S *u, const P *par, [const P *row,] int t, int N, S *g);
+// K path constraints g_i(x, u) <= 0.  ISLS_USER_COST_NTAB is then the width of the library's row, [user row (W) | lambda_0 ..
+// lambda_{K-1} | mu] = W + K + 1 words (the user's functions take `row` only where W > 0), user_stage is the augmented Lagrangian
+// of the stage (PHR form, below) and the program holds user_constraint_update_kernel, the multiplier and penalty update.
 #pragma once
 
 #ifndef ISLS_USER_COST_NPAR
@@ -19,6 +24,17 @@
 
 #ifndef ISLS_USER_COST_NTAB
 #define ISLS_USER_COST_NTAB 0
+#endif
+
+#ifndef ISLS_USER_COST_NCON
+#define ISLS_USER_COST_NCON 0
+#endif
+
+// words of the row that are the user's own (what `stage` and `constraint` see behind `row`)
+#if ISLS_USER_COST_NCON > 0
+#define ISLS_USER_COST_NROW (ISLS_USER_COST_NTAB - ISLS_USER_COST_NCON - 1)
+#else
+#define ISLS_USER_COST_NROW ISLS_USER_COST_NTAB
 #endif
 
 #ifdef ISLS_USER_NPAR
@@ -42,12 +58,51 @@ __device__ __forceinline__ void user_cost_par(const T *p, T (&par)[kUserCostParW
 
 // the user's stage in the form its registration names: with the row of step t, or without
 template <typename S, typename T>
-__device__ __forceinline__ S user_stage(const S *x, const S *u, const T *par, const T *row, int t, int N)
+__device__ __forceinline__ S user_plain_stage(const S *x, const S *u, const T *par, const T *row, int t, int N)
 {
-#if ISLS_USER_COST_NTAB > 0
+#if ISLS_USER_COST_NROW > 0
     return ::isls_user_cost::stage<S, T>(x, u, par, row, t, N);
 #else
     return ::isls_user_cost::stage<S, T>(x, u, par, t, N);
+#endif
+}
+
+#if ISLS_USER_COST_NCON > 0
+// ... and the user's constraint, likewise
+template <typename S, typename T>
+__device__ __forceinline__ void user_constraint(const S *x, const S *u, const T *par, const T *row, int t, int N, S *g)
+{
+#if ISLS_USER_COST_NROW > 0
+    ::isls_user_cost::constraint<S, T>(x, u, par, row, t, N, g);
+#else
+    ::isls_user_cost::constraint<S, T>(x, u, par, t, N, g);
+#endif
+}
+#endif
+
+// What every kernel of the program costs a step with.  With constraints: the augmented Lagrangian of the stage in the
+// Powell-Hestenes-Rockafellar form, lambda_i = row[W + i], mu = row[W + K]:
+//     h_i = lambda_i + mu g_i > 0 :  c += lambda_i g_i + mu / 2 g_i^2 ;   else :  c -= lambda_i^2 / (2 mu)   (0 where mu = 0)
+// continuous with a continuous gradient, and exactly `stage` at lambda = 0, mu = 0.  The branch is taken on the value part of h
+// (the AD contract's comparisons); only g carries derivatives, the row is plain T.
+template <typename S, typename T>
+__device__ __forceinline__ S user_stage(const S *x, const S *u, const T *par, const T *row, int t, int N)
+{
+#if ISLS_USER_COST_NCON > 0
+    S c = user_plain_stage<S, T>(x, u, par, row, t, N);
+    S g[ISLS_USER_COST_NCON];
+    user_constraint<S, T>(x, u, par, row, t, N, g);
+    const T mu = row[ISLS_USER_COST_NROW + ISLS_USER_COST_NCON];
+#pragma unroll
+    for (int i = 0; i < ISLS_USER_COST_NCON; ++i) {
+        const T lam = row[ISLS_USER_COST_NROW + i];
+        const S h = lam + mu * g[i];
+        if (h > T(0)) c += lam * g[i] + (T(0.5) * mu) * (g[i] * g[i]);
+        else c -= S(mu > T(0) ? lam * lam / (T(2) * mu) : T(0));
+    }
+    return c;
+#else
+    return user_plain_stage<S, T>(x, u, par, row, t, N);
 #endif
 }
 
@@ -160,5 +215,61 @@ __global__ __launch_bounds__(64) void user_cost_value_kernel(int R, int N, const
     }
     cost[r] = sum;
 }
+
+#if ISLS_USER_COST_NCON > 0
+// The multiplier and penalty update of the augmented Lagrangian (isls_user_constraint_update_*; arguments: UserConP,
+// rollout_kernel.hpp).  One wavefront per trajectory, lanes stride over the steps.  Per step, in plain T: g = constraint(xhat_t,
+// uhat_t), v_t = max_i max(0, g_i) (a NaN in g: +inf, and its lambda_i stays), g_out[b, t, :] = g where given, and with `update`
+// lambda_i <- max(0, lambda_i + mu g_i) with the mu the trajectory came with.  Then viol[b] = max_t v_t by a wave reduction; with
+// `update` and viol[b] > eta viol_prev[b] the lanes write mu <- min(phi mu, mu_max) into the last word of all N rows; viol_prev[b]
+// <- viol[b].  No LDS, no atomics; a trajectory with active[b] == 0 is left untouched, viol and viol_prev included.
+template <typename T, int NX, int NU>
+__global__ __launch_bounds__(64) void user_constraint_update_kernel(UserConP<T> p)
+{
+    constexpr int K = ISLS_USER_COST_NCON, W = ISLS_USER_COST_NTAB, W0 = ISLS_USER_COST_NROW;
+    const int b = blockIdx.x, N = p.N;
+    if (b >= p.B || (p.active && p.active[b] == 0)) return;    // uniform
+    T par[kUserCostParWords];
+    user_cost_par(p.par + (int64_t)b * p.par_sb, par);
+    T *const tab = p.tab + (int64_t)b * p.tab_sb;
+    const int64_t bN = (int64_t)b * N;
+    const T mu = tab[W0 + K];                                  // row 0's: every row of a trajectory holds the same mu
+    T v = T(0);
+#pragma unroll 1
+    for (int t = threadIdx.x; t < N; t += kWave) {
+        T x[NX], u[NU], g[K];
+#pragma unroll
+        for (int e = 0; e < NX; ++e) x[e] = p.xhat[(bN + t) * NX + e];
+#pragma unroll
+        for (int e = 0; e < NU; ++e) u[e] = p.uhat[(bN + t) * NU + e];
+        T *const row = tab + (int64_t)t * W;
+        user_constraint<T, T>(x, u, par, row, t, N, g);
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            const T gi = g[i];
+            if (gi != gi) {
+                v = (T)__builtin_huge_val();
+            } else {
+                v = gi > v ? gi : v;
+                if (p.update) {
+                    const T nl = row[W0 + i] + mu * gi;
+                    row[W0 + i] = nl > T(0) ? nl : T(0);
+                }
+            }
+            if (p.g_out) p.g_out[(bN + t) * K + i] = gi;
+        }
+    }
+    v = wave_max(v);
+    if (p.update && v > p.eta * p.viol_prev[b]) {
+        const T phimu = p.phi * mu, nm = phimu < p.mu_max ? phimu : p.mu_max;
+#pragma unroll 1
+        for (int t = threadIdx.x; t < N; t += kWave) tab[(int64_t)t * W + W0 + K] = nm;
+    }
+    if (threadIdx.x == 0) {
+        p.viol[b] = v;
+        p.viol_prev[b] = v;
+    }
+}
+#endif
 
 }  // namespace isls

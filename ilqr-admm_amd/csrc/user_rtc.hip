@@ -208,6 +208,7 @@ int load_program(Program &pg, const std::vector<hipFunction_t> **out, hipStream_
 struct Source {
     std::string source;
     int n, m, npar, ntab;                                    // ntab: words per step of the source's table (0: none)
+    int ncon = 0;                                            // path constraints of a cost (ntab then counts their multipliers and mu)
     std::string log;
 };
 
@@ -297,11 +298,18 @@ int program(int model, int cost, int dtype, Program **out)
         pg.stab = (int)pg.names.size();
         pg.names.push_back("isls::user_step_tab_kernel<" + T + ", " + dims + ">");
     }
+    // a cost with constraints: its multiplier update, behind every other name
+    pg.con = -1;
+    if (uc && uc->ncon > 0) {
+        pg.con = (int)pg.names.size();
+        pg.names.push_back("isls::user_constraint_update_kernel<" + T + ", " + dims + ">");
+    }
     std::string src = uc ? "#include \"user_cost_ad.hpp\"\n" : "#include \"user_model_ad.hpp\"\n";
     if (um) src += wrap_source("isls_user", "user_model", um->source) + "#define ISLS_USER_NPAR " + std::to_string(um->npar) + "\n";
     if (um && um->ntab > 0) src += "#define ISLS_USER_MODEL_NTAB " + std::to_string(um->ntab) + "\n";
     if (uc) src += wrap_source("isls_user_cost", "user_cost", uc->source) + "#define ISLS_USER_COST_NPAR " + std::to_string(uc->npar) + "\n";
     if (uc && uc->ntab > 0) src += "#define ISLS_USER_COST_NTAB " + std::to_string(uc->ntab) + "\n";
+    if (uc && uc->ncon > 0) src += "#define ISLS_USER_COST_NCON " + std::to_string(uc->ncon) + "\n";
     src += uc ? "#include \"user_cost.hpp\"\n" : "#include \"user_model.hpp\"\n";
     return compile_program(src, uc ? "user_cost.hip" : "user_model.hip", pg, (uc ? uc : um)->log);
 }
@@ -311,13 +319,15 @@ bool dtype_ok(int dtype) { return dtype == ISLS_DTYPE_F64 || dtype == ISLS_DTYPE
 }  // namespace
 
 // ---- what user_model.hip and user_cost.hip build their entry points and launches from ------------------------------------------
-int create(Kind kind, const char *source, int n, int m, int n_par, int n_tab, int32_t *id)
+int create(Kind kind, const char *source, int n, int m, int n_par, int n_tab, int32_t *id, int n_con)
 {
     if (!source || !id) return ISLS_ERR_ARG;
     if (!dims_supported(n, m) || n_par < 0 || n_par > ISLS_USER_MAX_PAR) return ISLS_ERR_UNSUPPORTED;
     if (n_tab < 0 || n_tab > ISLS_USER_MAX_TAB) return ISLS_ERR_UNSUPPORTED;
+    // constraints: a cost's, and the row then holds a multiplier each and mu behind the user's words
+    if (n_con < 0 || (n_con > 0 && (kind != KIND_COST || n_tab < n_con + 1))) return ISLS_ERR_UNSUPPORTED;
     auto src = std::make_unique<Source>();
-    src->source = source; src->n = n; src->m = m; src->npar = n_par; src->ntab = n_tab;
+    src->source = source; src->n = n; src->m = m; src->npar = n_par; src->ntab = n_tab; src->ncon = n_con;
     if (refused_source(src->source)) return ISLS_ERR_ARG;     // plain arithmetic: no hand-written ISA through this door
     std::lock_guard<std::mutex> lk(g_mu);
     *id = (kind == KIND_MODEL ? ISLS_MODEL_USER_BASE : ISLS_COST_USER_BASE) + (int32_t)g_src[kind].size();
@@ -378,6 +388,13 @@ int n_tab(int cost)
     std::lock_guard<std::mutex> lk(g_mu);
     const Source *src = find(KIND_COST, cost);
     return src ? src->ntab : ISLS_ERR_ARG;
+}
+
+int n_con(int cost)
+{
+    std::lock_guard<std::mutex> lk(g_mu);
+    const Source *src = find(KIND_COST, cost);
+    return src ? src->ncon : ISLS_ERR_ARG;
 }
 
 int model_n_tab(int model)

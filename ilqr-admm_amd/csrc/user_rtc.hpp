@@ -26,14 +26,16 @@ struct Program {                                             // one key: a model
     int ntab = 0;                                            // words per step of the cost's table (its side records enter the plan too)
     int mtab = 0;                                            // ... and of the user model's table (likewise)
     int stab = -1;                                           // index of user_step_tab_kernel (a table model's own program)
+    int con = -1;                                            // index of user_constraint_update_kernel (a cost with constraints)
     int smp0 = -1;                                           // index of sample_cost_kernel; sample_update_kernel and the two *_fb_kernel behind it (a key with a model)
     std::vector<std::pair<int, int>> ro;                     // (JM, OCC) of the rollout variants: names[ro0 + i]
     std::map<int, std::pair<hipModule_t, std::vector<hipFunction_t>>> dev;   // device -> module, functions
 };
 
 // isls_user_{model,cost}_create: register `source` (an id is assigned even when the compile fails) and compile its own program
-// (the model's, or the cost's expansion and value) for fp64; n_tab: words per step of the source's table (0: none)
-int create(Kind kind, const char *source, int n, int m, int n_par, int n_tab, int32_t *id);
+// (the model's, or the cost's expansion and value) for fp64; n_tab: words per step of the source's table (0: none); n_con: path
+// constraints of a cost, whose n_tab counts n_con multipliers and mu behind the user's words (ISLS_ERR_UNSUPPORTED: n_tab < n_con + 1)
+int create(Kind kind, const char *source, int n, int m, int n_par, int n_tab, int32_t *id, int n_con = 0);
 // isls_user_*_log / _code / _load: the compiler's messages for a source so far; the code object of a key, compiled on first use;
 // the same loaded onto the current device
 int64_t copy_log(Kind kind, int id, char *buf, int64_t len);
@@ -41,6 +43,7 @@ int copy_code(int model, int cost, int dtype, void *buf, int64_t *len);
 int load(int model, int cost, int dtype);
 int dims(Kind kind, int id, int *n, int *m);                 // ISLS_ERR_ARG: no such id
 int n_tab(int cost);                                         // words per step of the cost's table (0: none); ISLS_ERR_ARG: no such id
+int n_con(int cost);                                         // constraints of the cost (0: none); ISLS_ERR_ARG: no such id
 int model_n_tab(int model);                                  // the same of a user model's table; 0 for every built-in model
 // A launch's model parameters against a table model's registration, before anything is compiled, loaded or launched (no GPU
 // needed): a model with P parameters and a table of W words per step takes [par (P) | row 0 | ... | row N-1] -- par != NULL and

@@ -261,6 +261,14 @@ class ColumnsIterationArgs(C.Structure):
                 ("any_active", C.c_void_p)]
 
 
+class ConstraintUpdateArgs(C.Structure):
+    """isls_constraint_update_args (include/isls_hip.h)"""
+    _fields_ = [("B", C.c_int32), ("N", C.c_int32), ("n", C.c_int32), ("m", C.c_int32), ("cost_model", C.c_int32), ("update", C.c_int32),
+                ("cost_par", C.c_void_p), ("cost_par_sb", C.c_int64), ("tab", C.c_void_p), ("tab_sb", C.c_int64),
+                ("xhat", C.c_void_p), ("uhat", C.c_void_p), ("viol", C.c_void_p), ("viol_prev", C.c_void_p), ("g_out", C.c_void_p),
+                ("eta", C.c_double), ("phi", C.c_double), ("mu_max", C.c_double), ("active", C.c_void_p)]
+
+
 class AdvanceArgs(C.Structure):
     _fields_ = [("accept", AcceptArgs), ("lin", LinearizeArgs), ("exp", ExpandArgs),
                 ("admm_active", C.c_void_p), ("iters", C.c_void_p), ("lx", C.c_void_p), ("lu", C.c_void_p), ("res_prev", C.c_void_p)]
@@ -270,13 +278,15 @@ class AdvanceArgs(C.Structure):
 EXPORTED = [f"isls_{k}_{s}" for s in ("f64", "f32") for k in
             ("riccati_gain", "riccati_ff", "riccati_gain_ff", "riccati_ff_prepare", "rollout_ls", "admm_update", "project_rows", "sls_admm", "sls_closed_loop", "columns_rollout", "columns_admm", "dense_closed_loop", "mc_closed_loop", "mpc_step", "sample_nominal", "sample_nominal_fb", "cov_closed_loop", "sls_controller", "expand_quadratic", "linearize",
              "accept_step", "reduce_convergence", "reduce_convergence_table", "ilqr_admm_outer", "outer_advance", "columns_iteration",
-             "user_model_step", "user_model_step_tab", "user_cost_value", "user_cost_value_tab", "user_cost_expand", "riccati_gain_reg", "reg_update")] + \
+             "user_model_step", "user_model_step_tab", "user_cost_value", "user_cost_value_tab", "user_cost_expand", "riccati_gain_reg", "reg_update",
+             "user_constraint_update")] + \
            ["isls_ff_segments", "isls_ff_record_elems", "isls_sls_controller_work_elems", "isls_mc_work_elems", "isls_version", "isls_dims_supported", "isls_dims_generic", "isls_error_string", "isls_timing_create",
             "isls_timing_destroy", "isls_timing_reset", "isls_timing_pause", "isls_timing_read_ms",
             "isls_gain_memo_stats", "isls_gain_memo_clear",
             "isls_user_model_create", "isls_user_model_log", "isls_user_model_code", "isls_user_model_load",
             "isls_user_cost_create", "isls_user_cost_log", "isls_user_cost_code", "isls_user_cost_load",
-            "isls_user_cost_create_tab", "isls_user_cost_n_tab", "isls_user_model_create_tab", "isls_user_model_n_tab"]
+            "isls_user_cost_create_tab", "isls_user_cost_n_tab", "isls_user_model_create_tab", "isls_user_model_n_tab",
+            "isls_user_cost_create_con", "isls_user_cost_n_con"]
 
 
 SET_BOX, SET_SOC_UNIT, SET_SQUARE, SET_LINEAR, SET_QUADRATIC, SET_SHELL, SET_MULTILINEAR = 1, 2, 3, 4, 5, 6, 7
@@ -326,6 +336,8 @@ def load_hip_library(path=None):
                                ("load", ids + [i32])):
             getattr(lib, f"isls_user_{noun}_{what}").argtypes = argtypes
         getattr(lib, f"isls_user_{noun}_log").restype = C.c_int64
+    lib.isls_user_cost_create_con.argtypes = src + [i32, i32, C.POINTER(i32)]   # (.., n_tab, n_con, &id)
+    lib.isls_user_cost_n_con.argtypes = [i32]
     return lib
 
 
@@ -399,13 +411,14 @@ class _UserKind:
         self._fn("log")(C.c_int32(uid), buf, len(buf))
         return buf.value.decode(errors="replace")
 
-    def create(self, source, n, m, n_par, n_tab=0):
-        """n_tab > 0: a source with a per-step table of that many words; the key of one without is what it was"""
-        key = (str(source), int(n), int(m), int(n_par)) + ((int(n_tab),) if n_tab else ())
+    def create(self, source, n, m, n_par, n_tab=0, n_con=0):
+        """n_tab > 0: a source with a per-step table of that many words; the key of one without is what it was.  n_con > 0: a cost
+        with that many constraints, whose n_tab counts their multipliers and mu: part of the key as well"""
+        key = (str(source), int(n), int(m), int(n_par)) + ((int(n_tab),) if n_tab else ()) + ((int(n_con),) if n_con else ())
         if key in self.ids:
             return self.ids[key]
         uid = C.c_int32(-1)
-        rc = self._fn("create_tab" if n_tab else "create")(key[0].encode(), *key[1:], C.byref(uid))
+        rc = self._fn("create_con" if n_con else "create_tab" if n_tab else "create")(key[0].encode(), *key[1:], C.byref(uid))
         if rc == ERR_COMPILE:
             raise IslsError(f"user {self.noun}: compile failed\n{self.log(uid.value) if uid.value >= self.base else ''}")
         if rc != OK:
@@ -463,11 +476,13 @@ def user_model_load(model_id, dtype=np.float64):
     _USER_MODEL.load(model_id, dtype=dtype)
 
 
-def user_cost_create(source, n, m, n_par, n_tab=0):
+def user_cost_create(source, n, m, n_par, n_tab=0, n_con=0):
     """Register a user cost and compile its expansion and value for gfx950 (fp64; the line-search kernels are compiled per model
-    it is used with); the same (source, n, m, n_par, n_tab) is registered once per process.  n_tab > 0: the cost reads a table
-    of that many words per step (isls_user_cost_create_tab; the six-argument `stage`).  IslsError carries the compile log."""
-    return _USER_COST.create(source, n, m, n_par, n_tab)
+    it is used with); the same (source, n, m, n_par, n_tab, n_con) is registered once per process.  n_tab > 0: the cost reads a
+    table of that many words per step (isls_user_cost_create_tab; the six-argument `stage`).  n_con > 0: `source` also defines
+    `constraint` (isls_user_cost_create_con) and n_tab = W + n_con + 1: the user's W words, the multipliers and mu.  IslsError
+    carries the compile log."""
+    return _USER_COST.create(source, n, m, n_par, n_tab, n_con)
 
 
 def user_cost_code(cost_id, model=-1, dtype=np.float64):
@@ -531,6 +546,10 @@ def _sfx(x):
     if dt in (np.float32,) or (torch is not None and dt == torch.float32):
         return "f32"
     raise TypeError(f"unsupported dtype {dt}")
+
+
+def _sfx_int(x):
+    return "i32" if x.dtype in (np.int32,) or (torch is not None and x.dtype == torch.int32) else str(x.dtype)
 
 
 def _contiguous(x):
@@ -1327,6 +1346,31 @@ class Kernels:
                                 C.c_void_p(_ptr(cost)), stream=stream)
         return self._invoke("user_cost_value", _sfx(cost), C.c_int32(cost_id), C.c_int32(R), C.c_int32(N), C.c_void_p(ptr), C.c_int64(sb),
                             C.c_void_p(_ptr(x)), C.c_void_p(_ptr(u)), C.c_void_p(_ptr(cost)), stream=stream)
+
+    def user_constraint_update(self, cost_id, par, tab, xhat, uhat, viol, viol_prev, update=True, eta=0.25, phi=10.0, mu_max=1e8,
+                               g_out=None, active=None, stream=None):
+        """isls_user_constraint_update: the multiplier and penalty update of a cost with K constraints along xhat [B,N,n], uhat
+        [B,N,m], INTO tab [B,N,W+K+1]; viol, viol_prev [B]; g_out [B,N,K] or None; update=False evaluates only."""
+        B, N, n = xhat.shape
+        m = int(uhat.shape[2])
+        _dense(xhat, (B, N, n), "xhat"), _dense(uhat, (B, N, m), "uhat"), _dense(tab, (B, N, int(tab.shape[-1])), "tab")
+        _dense(viol, (B,), "viol"), _dense(viol_prev, (B,), "viol_prev")
+        for name, v in (("par", par), ("xhat", xhat), ("uhat", uhat), ("viol", viol), ("viol_prev", viol_prev), ("g_out", g_out)):
+            if v is not None and v.dtype != tab.dtype:
+                raise ValueError(f"{name}: dtype {v.dtype}, the table is {tab.dtype}")
+        if active is not None and _sfx_int(active) != "i32":
+            raise ValueError(f"active: int32, got {active.dtype}")
+        a = ConstraintUpdateArgs()
+        a.B, a.N, a.n, a.m, a.cost_model, a.update = B, N, n, m, int(cost_id), int(bool(update))
+        a.cost_par, a.cost_par_sb = _par(par, B, "par")
+        a.tab, a.tab_sb = _ptr(tab), N * int(tab.shape[-1])
+        a.xhat, a.uhat, a.viol, a.viol_prev = _ptr(xhat), _ptr(uhat), _ptr(viol), _ptr(viol_prev)
+        if g_out is not None:
+            a.g_out = _ptr(_dense(g_out, (B, N, int(g_out.shape[-1])), "g_out"))
+        a.eta, a.phi, a.mu_max = float(eta), float(phi), float(mu_max)
+        if active is not None:
+            a.active = _ptr(_dense(active, (B,), "active"))
+        return self._call("user_constraint_update", _sfx(tab), a, stream)
 
     def user_cost_expand(self, exp, Cux, sfx, stream=None):
         """isls_user_cost_expand: `exp` an expand_args block whose cost_model is the cost's id; Cux [B,N,m,n] or None."""

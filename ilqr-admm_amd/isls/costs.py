@@ -77,10 +77,85 @@ class Custom(UserSource):
 
     `row` the W words of step t: plain P, never differentiated.  `set_table` replaces the values (same shape) between two calls
     of a solver -- a receding-horizon window: no compile, and the engines holding the cost copy the new values into the device
-    table they already have."""
+    table they already have.
 
-    def __init__(self, x_dim, u_dim, params, source, table=None):
-        self.cost_model = self._register("cost", capi.user_cost_create, x_dim, u_dim, params, source, table=table)
+    Nonlinear path constraints g(x, u) <= 0 (a keep-out region of any shape, a friction cone, a limit on a nonlinear function of
+    the state, an inequality that couples x and u): `constraints=K` (K >= 1), and `source` also defines
+
+        template <typename S, typename P>
+        __device__ void constraint(const S *x, const S *u, const P *par, int t, int N, S *g);
+
+    (with a table both functions take `const P *row` behind `par`); feasible is g[i] <= 0.  The solver treats them by augmented
+    Lagrangian: what it costs a step with is stage + sum_i PHR(lambda_i, mu, g_i) (csrc/user_cost.hpp), the multipliers lambda
+    [B, N, K] and the penalty mu [B] ride on the device in the cost's per-step table, [user row (W) | lambda | mu], W + K + 1 <= 16,
+    one table per trajectory from the moment the cost is assigned to an iSLS (a shared table is replicated then).  `iSLS.solve_al`
+    runs the outer loop; every other solver runs on the multipliers that stand.  `multipliers`, `penalty`: the host copies;
+    `reset_multipliers(mu)`: lambda = 0, mu = mu; `constraint(x, u)`: g on the device; __call__ and get_Cs evaluate the augmented
+    cost with the current multipliers (exactly `stage` while lambda = 0 and mu = 0, which is how the object starts).  Such a cost
+    belongs to one iSLS at a time (a second assignment is an IslsError until the first iSLS takes another cost); assigned to an
+    iSLS of another batch or horizon afterwards, its multipliers start again at lambda = 0, mu = the last reset's."""
+
+    def __init__(self, x_dim, u_dim, params, source, table=None, constraints=0):
+        self._lam = self._mu = None                           # host copies of the multipliers [B, N, K] and penalties [B]
+        self._mu_init, self._mult_version = 0.0, 0
+        self._owner = None                                    # weakref to the iSLS whose device table holds the multipliers
+        self.cost_model = self._register("cost", capi.user_cost_create, x_dim, u_dim, params, source, table=table,
+                                         constraints=constraints)
+
+    # ---- constraints: the multipliers and the library's table ----------------------------------------------------------------
+    @property
+    def multipliers(self):
+        """lambda [B, N, K] (None until the cost has met a batch: assigned to an iSLS)"""
+        return self._lam
+
+    @property
+    def penalty(self):
+        """mu [B] (None until the cost has met a batch)"""
+        return self._mu
+
+    def reset_multipliers(self, mu=1.0):
+        """lambda = 0 and mu = mu for every trajectory; the iSLS holding the cost copy them into their device table at their next call"""
+        if not self.n_con:
+            raise ValueError("reset_multipliers: this cost was built without constraints")
+        self._mu_init = float(mu)
+        if self._lam is not None:
+            self._lam, self._mu = np.zeros_like(self._lam), np.full_like(self._mu, float(mu))
+        self._mult_version += 1
+
+    def _al_table(self, B, N, bind=True):
+        """The library's table [B, N, W + K + 1] = [user row | lambda | mu] for B trajectories of N steps, from the host copies.
+        bind: multipliers of another shape (or none yet) start again at lambda = 0, mu = the last reset's; else they must fit."""
+        W, K = self.n_tab, self.n_con
+        if self._table is not None and (self._table.shape[-2] != N or (self._table.ndim == 3 and self._table.shape[0] != B)):
+            raise ValueError(f"the cost's table is {self._table.shape}, needed [{N}, {W}] or [{B}, {N}, {W}]")
+        lam, mu = self._lam, self._mu
+        if lam is None or lam.shape != (B, N, K):
+            if lam is not None and not bind:
+                raise ValueError(f"the cost's multipliers are {lam.shape}: x, u of [{lam.shape[0]}, {lam.shape[1]}, .]")
+            lam, mu = np.zeros((B, N, K)), np.full(B, self._mu_init)
+            if bind:
+                self._lam, self._mu = lam, mu
+        tab = np.empty((B, N, W + K + 1))
+        if W:
+            tab[..., :W] = self._table
+        tab[..., W:W + K], tab[..., W + K] = lam, mu[:, None]
+        return tab
+
+    def _pull(self, tab):
+        """The multipliers and penalties out of a library table [B, N, W + K + 1] (numpy) into the host copies"""
+        W, K = self.n_tab, self.n_con
+        self._lam, self._mu = np.array(tab[..., W:W + K], dtype=np.float64), np.array(tab[:, 0, W + K], dtype=np.float64)
+
+    def constraint(self, x, u):
+        """x [..., N, n], u [..., N, m] -> g [..., N, K] (numpy, fp64), evaluated on the device by the kernel that updates the multipliers."""
+        if not self.n_con:
+            raise ValueError("constraint: this cost was built without constraints")
+        torch, kern, lead, R, N, xs, us, par, dev = self._batch(x, u, multipliers=False)
+        g = torch.empty(R, N, self.n_con, dtype=torch.float64, device=dev)
+        viol = torch.zeros(2, R, dtype=torch.float64, device=dev)
+        kern.user_constraint_update(self.cost_model, par, self._tab_dev, xs, us, viol[0], viol[1], update=False, g_out=g,
+                                    stream=torch.cuda.current_stream().cuda_stream)
+        return g.cpu().numpy().reshape(lead + (N, self.n_con))
 
     def code(self, model=None, dtype=np.float64):
         """The gfx950 code object of the cost for dtype: with `model` (an isls.models object or a model id) every kernel of the
@@ -91,7 +166,7 @@ class Custom(UserSource):
     def _load(self, dtype):
         capi.user_cost_load(self.cost_model, -1, dtype)
 
-    def _batch(self, x, u):
+    def _batch(self, x, u, multipliers=True):
         x, u = np.asarray(x, dtype=np.float64), np.asarray(u, dtype=np.float64)
         lead = np.broadcast_shapes(x.shape[:-2], u.shape[:-2])
         N = x.shape[-2]
@@ -101,7 +176,16 @@ class Custom(UserSource):
         torch, kern, dev, (par, xs, us) = self._on_device(R, "{0} trajectories x, u, got {1}",
                                                            np.broadcast_to(x, lead + (N, self.x_dim)).reshape(R, N, self.x_dim),
                                                            np.broadcast_to(u, lead + (N, self.u_dim)).reshape(R, N, self.u_dim))
-        self._tab_dev = None if self._table is None else torch.as_tensor(self._table, device=dev)
+        if self.n_con:                                        # the library's table, one per trajectory (multipliers=False: zeros)
+            keep = self._lam, self._mu
+            if not multipliers:
+                self._lam = None
+            try:
+                self._tab_dev = torch.as_tensor(self._al_table(R, N, bind=False), device=dev)
+            finally:
+                self._lam, self._mu = keep
+        else:
+            self._tab_dev = None if self._table is None else torch.as_tensor(self._table, device=dev)
         return torch, kern, lead, R, N, xs, us, par, dev
 
     def __call__(self, x, u):

@@ -16,6 +16,8 @@ solve instead of the dense batch-form least squares (identical iterates except t
 SURVEY 8a quirk i); forward models and costs are the built-in device implementations (`isls.models`, via-point
 quadratic cost); status is per trajectory; nothing falls back to the CPU.
 """
+import weakref
+
 import numpy as np
 import torch
 
@@ -35,6 +37,15 @@ class MpcResult:
 
     def __init__(self, x, u, cost, status, admm_iters):
         self.x, self.u, self.cost, self.status, self.admm_iters = x, u, cost, status, admm_iters
+
+
+class AlResult:
+    """What iSLS.solve_al returns (numpy): viol [B, rounds] the violation max_t max_i max(0, g_i) of every trajectory after each
+    round's solve (a trajectory that was already within tol_con keeps its last value), mu [B] the final penalties, rounds [B] the
+    rounds each trajectory took part in, converged [B] (its last violation <= tol_con), cost [B] the final (augmented) cost."""
+
+    def __init__(self, viol, mu, rounds, converged, cost):
+        self.viol, self.mu, self.rounds, self.converged, self.cost = viol, mu, rounds, converged, cost
 
 
 class iSLS(Base):
@@ -89,15 +100,34 @@ class iSLS(Base):
         """None -> the via-point quadratic cost of set_cost_variables; an `isls.costs` object (PseudoHuber, or a Custom cost of
         the user's own) -> that cost on the device, for the line search and for the expansion (the reference's cost_function / get_Cs pair)."""
         if function is None:
+            self._release_constraint_cost()
             self._cost_function, self._host_cost = None, False
             return
         if hasattr(function, "cost_model") and hasattr(function, "x_dim") and (function.x_dim, function.u_dim) != (self.x_dim, self.u_dim):
             raise ValueError("cost dimensions do not match x_dim/u_dim")
+        if getattr(function, "n_con", 0):
+            # the multipliers are state of ONE device table: a second iSLS would see neither what solve_al leaves on the first
+            # nor keep the object's host copies in step with its own
+            owner = function._owner() if function._owner is not None else None
+            if owner is not None and owner is not self:
+                raise capi.IslsError("a cost with constraints (costs.Custom(constraints=)) belongs to one iSLS at a time: its "
+                                     "multipliers live in that object's device table; build a second costs.Custom for a second iSLS, "
+                                     "or assign the first one another cost_function first")
+        self._release_constraint_cost()
         self._cost_function = function
         if hasattr(function, "cost_model"):
             self._host_cost = False
             table = getattr(function, "table", None)           # costs.Custom(table=): per-step data of the user's stage
-            if table is None:
+            if getattr(function, "n_con", 0):
+                # costs.Custom(constraints=): the library's table [B, N, W + K + 1] = [user row | multipliers | penalty], one per
+                # trajectory -- a shared table and shared parameters are replicated now that the batch is known
+                par = function.params()
+                if par.ndim == 1 and par.shape[0] > 0:
+                    par = np.broadcast_to(par, (self.batch, par.shape[0]))
+                self.engine.set_cost_model(function.cost_model, par, table=function._al_table(self.batch, self.N))
+                function._owner = weakref.ref(self)
+                self._cost_table_version, self._cost_mult_version = function._table_version, function._mult_version
+            elif table is None:
                 self.engine.set_cost_model(function.cost_model, function.params())
             else:
                 self.engine.set_cost_model(function.cost_model, function.params(), table=table)
@@ -109,14 +139,45 @@ class iSLS(Base):
         else:
             raise TypeError("cost_function must be None, an isls.costs object or a callable cost(x, u)")
 
+    def _release_constraint_cost(self):
+        """The cost with constraints this object holds, if any, is free for another iSLS"""
+        f = self._cost_function
+        if getattr(f, "n_con", 0) and f._owner is not None and f._owner() is self:
+            f._owner = None
+
     def _sync_tables(self):
         """set_table on the model or on the cost since this object last looked: the new values go INTO the buffer the engine holds
         (one copy_, no compile, no allocation; cached argument blocks stay valid).  The model's rows first (update_model_table
         marks the linearisation stale), so that the cost of the nominal is then evaluated again with both in place."""
         if not self._host_model:
             self._sync_table(self._forward_model, "_model_table_version", self.engine.update_model_table)
-        if not self._host_cost and self._sync_table(self._cost_function, "_cost_table_version", self.engine.update_cost_table):
+        if not self._host_cost and getattr(self._cost_function, "n_con", 0):
+            if self._sync_al_table():
+                self.engine.evaluate_cost()
+        elif not self._host_cost and self._sync_table(self._cost_function, "_cost_table_version", self.engine.update_cost_table):
             self.engine.evaluate_cost()
+
+    def _sync_al_table(self):
+        """The same for a cost with constraints, whose device table is [user row (W) | multipliers (K) | penalty]: set_table
+        writes the user's columns only, reset_multipliers the others -- strided copy_ INTO the table the engine holds."""
+        f, tab = self._cost_function, self.engine.cost_tab
+        W, K, changed = f.n_tab, f.n_con, False
+        if W and f._table_version != self._cost_table_version:
+            tab[..., :W].copy_(self.engine._t(f.table))
+            self._cost_table_version, changed = f._table_version, True
+        if f._mult_version != self._cost_mult_version:
+            if f._lam is None or f._lam.shape != (self.batch, self.N, K):
+                f._al_table(self.batch, self.N)
+            tab[..., W:W + K].copy_(self.engine._t(f._lam))
+            tab[..., W + K].copy_(self.engine._t(f._mu)[:, None])
+            self._cost_mult_version, changed = f._mult_version, True
+        return changed
+
+    def _refuse_constraints(self, what):
+        """The entry points a costs.Custom(constraints=) is not served by"""
+        if not self._host_cost and getattr(self._cost_function, "n_con", 0):
+            raise capi.IslsError(f"{what} does not serve a cost with constraints (costs.Custom(constraints=)): its augmented Lagrangian "
+                                 "runs in the device routes of solve / solve_al, ilqr_admm, mpc, sample_nominal and covariance")
 
     def _sync_table(self, obj, seen, update):
         """update(obj.table) if obj has a table whose version is not the one this object last saw (the attribute `seen`)"""
@@ -183,6 +244,7 @@ class iSLS(Base):
     def _line_search(self, L, flags=0, active=None):
         """Line search over alphas[:L]: the rollout kernel, or the host route when the model / cost is a Python callable."""
         if self._host_ls:
+            self._refuse_constraints("the host route (a forward model given as a Python callable)")
             hostpath.line_search(self, L, flags, active)
         else:
             self.engine.rollout(L, flags=flags, active=active)
@@ -446,6 +508,57 @@ class iSLS(Base):
         return self.solve(get_AB, method='dp' if dp else 'batch', max_iter=max_ilqr_iter, max_line_search_iter=max_line_search_iter,
                           verbose=verbose, **kw)
 
+    # ---- nonlinear path constraints by augmented Lagrangian ---------------------------------------------------
+    def solve_al(self, max_outer=10, max_iter=20, tol_con=1e-4, mu0=1.0, phi=10.0, mu_max=1e8, eta=0.25, regularization=None,
+                 **solve_keywords):
+        """iLQR under the constraints g(x, u) <= 0 of a costs.Custom(constraints=) cost, by augmented Lagrangian.  mu0: lambda = 0
+        and mu = mu0 to start with (None: go on from the multipliers that stand).  Per round: solve(max_iter=, regularization=,
+        **solve_keywords) on the augmented cost; then one launch (isls_user_constraint_update_*) on the new nominal, for the
+        trajectories whose last violation was above tol_con: viol = max_t max_i max(0, g_i), lambda <- max(0, lambda + mu g), and
+        mu <- min(phi mu, mu_max) where viol > eta * (the violation one round before; +inf at the first); then one read of viol.
+        Stops when every trajectory is within tol_con, or after max_outer rounds.  A trajectory within tol_con keeps its
+        multipliers but is still re-solved with the batch.  At the end one evaluate-only launch on the returned nominal gives
+        `converged` (so it is true of that nominal, whatever the later solves did to a trajectory that had been within tol_con;
+        `viol` is the log of the rounds).  Afterwards the cost object's multipliers / penalty are the device's.  Returns an AlResult."""
+        f, e = self._cost_function, self.engine
+        if self._host_cost or f is None or not getattr(f, "n_con", 0):
+            raise capi.IslsError("solve_al needs a costs.Custom(constraints=K) cost_function" +
+                                 (": a cost given as a Python callable has no constraint the device could evaluate" if self._host_cost else ""))
+        if self._host_model or e.model is None:
+            raise capi.IslsError("solve_al runs on the device: set forward_model to an isls.models descriptor (models.Custom for a "
+                                 "model of your own), not a Python callable")
+        if solve_keywords.get("method", "dp") != "dp":
+            self._refuse_constraints("the batch form (iterate_once_batch, solve(method='batch'))")
+        if mu0 is not None:
+            f.reset_multipliers(mu0)
+        self._sync_tables()
+        B = self.batch
+        viol = torch.zeros(B, dtype=e.dtype, device=e.device)
+        prev = torch.full((B,), float("inf"), dtype=e.dtype, device=e.device)
+        act = torch.ones(B, dtype=torch.int32, device=e.device)
+        log, rounds, on = np.zeros((B, 0)), np.zeros(B, dtype=np.int64), np.ones(B, dtype=bool)
+        stream = torch.cuda.current_stream().cuda_stream
+        for r in range(int(max_outer)):
+            self.solve(max_iter=max_iter, regularization=regularization, **solve_keywords)
+            e.kern.user_constraint_update(e.cost_model, e.cost_par, e.cost_tab, e.xhat, e.uhat, viol, prev, update=True, eta=eta,
+                                          phi=phi, mu_max=mu_max, active=act, stream=stream)
+            last = viol.cpu().numpy().astype(np.float64)        # the round's read (a trajectory left out keeps its last value)
+            rounds += on
+            log = np.concatenate([log, last[:, None]], axis=1)
+            e.nominal_rewritten()                               # the nominal's cost under the new multipliers, as after the nominal_values setter
+            if (last <= tol_con).all():
+                break
+            act.mul_((viol > tol_con).to(torch.int32))          # on the device: nothing is sent up
+            on = on & (last > tol_con)
+        # a trajectory that was within tol_con is still re-solved with the batch, and a solve that had stopped at max_iter can move
+        # it afterwards: `converged` speaks of the nominal that is returned -- one evaluate-only launch (update = 0) on it
+        final = torch.zeros(B, dtype=e.dtype, device=e.device)
+        e.kern.user_constraint_update(e.cost_model, e.cost_par, e.cost_tab, e.xhat, e.uhat, final, prev.clone(), update=False,
+                                      stream=stream)
+        f._pull(e.cost_tab.cpu().numpy().astype(np.float64))
+        return AlResult(log, f.penalty.copy(), rounds, final.cpu().numpy().astype(np.float64) <= tol_con,
+                        np.atleast_1d(np.array(self.cost, dtype=np.float64)).copy())
+
     # ---- iLQR-ADMM (DP form) --------------------------------------------------------------------------------
     def ilqr_admm(self, get_AB=None, get_Cs=None, project_x=False, project_u=False, max_iter=20,
                   max_line_search_iter=20, max_admm_iter=20, rho_x=None, rho_u=None, alpha=1, tol=1e-3,
@@ -462,6 +575,8 @@ class iSLS(Base):
         tol = threshold if threshold is not None else tol
         e = self.engine
         px, pu, host_proj = self._setup_admm(project_x, project_u, rho_x, rho_u, alpha)
+        if host_proj:
+            self._refuse_constraints("ilqr_admm through the host (a projection or a model given as a Python callable)")
         if regularization is not None and host_proj:
             raise capi.IslsError("ilqr_admm through the host (a projection or a model / cost given as a Python callable) does not serve "
                                  "a regularisation; use Box / ConvexSets projections and device models")
@@ -588,8 +703,17 @@ class iSLS(Base):
             if tuple(w.shape) != (B, T_, n):
                 raise ValueError(f"w: [{B}, {T_}, {n}], got {tuple(w.shape)}")
             w = w.permute(1, 0, 2).contiguous()
+        n_con = 0 if self._host_cost else getattr(self._cost_function, "n_con", 0)
+        if n_con and table_future is not None and self._cost_function.n_tab == 0:
+            raise capi.IslsError("table_future supplies the user's columns of the cost's table: this cost has none (its table "
+                                 "holds the multipliers only, which move up with the window)")
         if table_future is not None:
-            W, per_traj = int(e.cost_tab.shape[-1]), e.cost_tab.ndim == 3
+            # (a cost with constraints: the user's columns only -- the multipliers and mu of the held last row ride behind them)
+            W, per_traj = int(e.cost_tab.shape[-1]) - (n_con + 1 if n_con else 0), e.cost_tab.ndim == 3
+            if n_con and np.ndim(table_future) == 3 and self._cost_function.table.ndim == 2:
+                # (the device table of such a cost is per trajectory for its multipliers' sake, but the object's table is one for
+                # the batch: per-trajectory futures would leave windows that the object cannot hold afterwards)
+                raise ValueError(f"table_future: [{T_}, {W}] (the cost's table is shared by the batch)")
             tf = e._t(table_future)
             if tuple(tf.shape) not in ((T_, W), (B, T_, W)) or (tf.ndim == 3 and not per_traj):
                 raise ValueError(f"table_future: [{T_}, {W}]" + (f" or [{B}, {T_}, {W}]" if per_traj else " (the table is shared)") +
@@ -658,7 +782,9 @@ class iSLS(Base):
             if world is not None:                              # the window moves up: one device-to-device copy INTO model_par
                 mtab.copy_(world[..., s + 1:s + 1 + N, :])
             e.mpc_step(plant_par=plant if plants is None else plants[s], u_lo=u_lo, u_hi=u_hi, w=None if w is None else w[s], noise_std=noise_std, seed=seed, step=s,
-                       feedback=feedback, shift_z=warm_start_z, tab_next=None if table_future is None else table_future[s],
+                       feedback=feedback, shift_z=warm_start_z,
+                       tab_next=None if table_future is None else table_future[s] if not n_con else
+                       torch.cat([table_future[s], e.cost_tab[:, -1, -(n_con + 1):]], dim=-1),
                        x_meas_out=x_log[:, s], u_out=u_log[:, s], x_next_out=x_log[:, s + 1])
             if any(moving.values()):
                 e.advance_sets(1, x=moving.get("x", False), u=moving.get("u", False))
@@ -667,7 +793,12 @@ class iSLS(Base):
                     if zz is not None:
                         zz.zero_()
         f = self._cost_function
-        if getattr(f, "table", None) is not None:               # the cost object follows the window the engine holds now
+        if n_con:                                               # the cost object follows the window the engine holds now
+            full = e.cost_tab.cpu().numpy().astype(np.float64)
+            f._pull(full)
+            if f.n_tab:
+                f._table = np.ascontiguousarray(full[..., :f.n_tab] if f._table.ndim == 3 else full[0, :, :f.n_tab])
+        elif getattr(f, "table", None) is not None:
             f._table = e.cost_tab.cpu().numpy().astype(np.float64)
         if mtab is not None:                                    # ... and so does the model object
             mdl = self._forward_model
@@ -770,7 +901,11 @@ class iSLS(Base):
             e.zu.copy_(e._t(z_u.reshape(B, N, m))), e.lu.copy_(e._t(l_u.reshape(B, N, m)))
         return res
 
-    isls_admm = _isls_admm                                      # isls/isls.py:503-712, DP form (robust.py)
+    def isls_admm(self, *args, **kwargs):                       # isls/isls.py:503-712, DP form (robust.py)
+        self._refuse_constraints("isls_admm")
+        return _isls_admm(self, *args, **kwargs)
+
+    isls_admm.__doc__ = _isls_admm.__doc__
 
     def controller(self, PHI_U, du):
         """K = Phi_u Phi_x^-1, k = (I - K Su) du with the dynamics of the last linearisation, engine.A / engine.Bm (notebook-era
@@ -992,6 +1127,7 @@ class iSLS(Base):
         (isls/isls.py:191-225).  Returns fp_success (bool, or a bool array when batched)."""
         e = self.engine
         self._refuse_table_model("the batch form (iterate_once_batch, solve(method='batch'))")
+        self._refuse_constraints("the batch form (iterate_once_batch, solve(method='batch'))")
         self.backward_pass_batch(**kwargs)
         zero_K = torch.zeros(self.batch, self.N, self.u_dim, self.x_dim, dtype=e.dtype, device=e.device)
         e.status.zero_()

@@ -172,9 +172,21 @@ class UserSource:
     cost), its per-step table and the way their host-side evaluations put numpy arrays on the device."""
 
     _table = None                                            # the per-step table (Custom(table=)): [N, W] or [B, N, W]
+    _table_version = 0
 
-    def _register(self, noun, create, x_dim, u_dim, params, source, table=None):
+    n_con = 0                                                # path constraints of a cost (costs.Custom(constraints=)), 0: none
+
+    def _register(self, noun, create, x_dim, u_dim, params, source, table=None, constraints=0):
         self._noun, self.x_dim, self.u_dim = noun, int(x_dim), int(u_dim)
+        K = int(constraints)
+        if K < 0:
+            raise ValueError("constraints: K >= 0")
+        if K:                                                # the library's row: [user row (W) | K multipliers | mu], checked ahead of any compile
+            W = 0 if table is None else int(np.shape(table)[-1])
+            if W + K + 1 > capi.USER_MAX_TAB:
+                raise ValueError(f"a table of W = {W} words and K = {K} constraints make a row of W + K + 1 = {W + K + 1} words "
+                                 f"(user row, multipliers, penalty): at most {capi.USER_MAX_TAB}")
+        self.n_con = K
         if table is not None:
             table = np.array(table, dtype=np.float64, order="C")
             if table.ndim not in (2, 3) or table.shape[-1] < 1:
@@ -194,6 +206,8 @@ class UserSource:
         if re.search(r"\b(asm|__asm|__asm__)\b", source) or "__builtin_amdgcn" in source:
             raise capi.IslsError(f"a user {noun} is plain arithmetic: `asm` and `__builtin_amdgcn_*` are not accepted")
         self.source = source
+        if K:
+            return create(source, self.x_dim, self.u_dim, P, self.n_tab + K + 1, K)
         if table is not None:
             return create(source, self.x_dim, self.u_dim, P, table.shape[-1])
         return create(source, self.x_dim, self.u_dim, P)

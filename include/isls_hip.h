@@ -884,6 +884,44 @@ int isls_user_cost_create(const char *source, int32_t n, int32_t m, int32_t n_pa
 int isls_user_cost_create_tab(const char *source, int32_t n, int32_t m, int32_t n_par, int32_t n_tab, int32_t *id);
 /* Words per step of the cost's table (0: a cost without one), or ISLS_ERR_ARG for an id nobody registered. */
 int isls_user_cost_n_tab(int32_t id);
+/* Nonlinear path constraints g(x, u) <= 0 by augmented Lagrangian.  A cost registered with n_con = K >= 1 constraints defines,
+ * next to `stage`,
+ *   template <typename S, typename P> __device__ void constraint(const S *x, const S *u, const P *par, int t, int N, S *g);
+ * (K values; feasible is g_i <= 0), and its table is the library's: n_tab = W + K + 1 words per step,
+ *   [ the user's row (W >= 0 words) | lambda_0 .. lambda_{K-1} | mu ],
+ * n_tab <= ISLS_USER_MAX_TAB.  Where W > 0 both functions take `const P *row` (the W words) behind `par`, as a table cost's stage
+ * does.  Every entry point that serves the cost (line search, expansion, value, sampling, isls_mpc_step_*) takes that table in
+ * ztab / ztab_sb / nvia = n_tab as it takes any table, and costs a step with the augmented Lagrangian in the PHR form:
+ *   c = stage ;  per i, h = lambda_i + mu g_i :  h > 0: c += lambda_i g_i + mu / 2 g_i^2 ;  else: c -= lambda_i^2 / (2 mu) (0 at mu = 0)
+ * -- exactly `stage` at lambda = 0, mu = 0.  ISLS_ERR_UNSUPPORTED: n_con < 0, or n_con > 0 with n_tab < n_con + 1. */
+int isls_user_cost_create_con(const char *source, int32_t n, int32_t m, int32_t n_par, int32_t n_tab, int32_t n_con, int32_t *id);
+/* Constraints of the cost (0: a cost without), or ISLS_ERR_ARG for an id nobody registered. */
+int isls_user_cost_n_con(int32_t id);
+/* The multiplier and penalty update of such a cost along a trajectory, one launch for the batch (one wavefront per trajectory).
+ * Per trajectory b with active[b] != 0 (NULL: all), with g = constraint(xhat_t, uhat_t) and the mu the table came with:
+ *   g_out[b, t, i] = g_i (g_out nullable) ;  v_t = max_i max(0, g_i), +inf where a g_i is NaN ;  viol[b] = max_t v_t ;
+ *   update != 0:  lambda_i <- max(0, lambda_i + mu g_i) (a NaN g_i leaves its lambda_i), and then, where
+ *                 viol[b] > eta * viol_prev[b]:  mu <- min(phi mu, mu_max) in every row ;
+ *   viol_prev[b] <- viol[b].
+ * update == 0 leaves the table as it is.  tab is [B, N, n_tab] with tab_sb = N * n_tab (the multipliers belong to a trajectory);
+ * cost_par [n_par] (cost_par_sb = 0) or [B, n_par].  ISLS_ERR_ARG: a cost without constraints, NULL arrays, another tab_sb,
+ * update with phi < 1, mu_max < 0 or eta < 0. */
+typedef struct isls_constraint_update_args {
+    int32_t B, N, n, m;
+    int32_t cost_model;      /* the cost's id */
+    int32_t update;
+    const void *cost_par;
+    int64_t cost_par_sb;
+    void *tab;
+    int64_t tab_sb;
+    const void *xhat, *uhat; /* [B,N,n], [B,N,m] */
+    void *viol, *viol_prev;  /* [B] */
+    void *g_out;             /* [B,N,n_con], nullable */
+    double eta, phi, mu_max;
+    const int32_t *active;   /* [B], nullable */
+} isls_constraint_update_args;
+int isls_user_constraint_update_f64(const isls_constraint_update_args *a, void *stream);
+int isls_user_constraint_update_f32(const isls_constraint_update_args *a, void *stream);
 /* The compile log of the cost's programs (as isls_user_model_log). */
 int64_t isls_user_cost_log(int32_t id, char *buf, int64_t len);
 /* The gfx950 code object of the cost with `model` (a built-in model of the cost's (n, m), a user model of them, or -1: the

@@ -2,7 +2,7 @@
 """Built-in PseudoHuber against the same cost written as an isls.costs.Custom source, on the Tassa parking problem (N = 100,
 L = 20, J = 5, control box) at B = 4096.
 
-    python tools/user_cost_bench.py [--batch 4096] [--reps 20] [--rounds 5] [--legs phuber,arm,table,host]
+    python tools/user_cost_bench.py [--batch 4096] [--reps 20] [--rounds 5] [--legs phuber,arm,table,host,al]
 
 Two engines on the same problem, the forms alternating over the rounds (medians; spread = max - min over the rounds):
 * one rollout launch (the line search of the ADMM iteration, same gains and ADMM targets on both sides);
@@ -16,6 +16,9 @@ Two engines on the same problem, the forms alternating over the rounds (medians;
   a constant reference folded into `params` (what a cost without a table can hold), the same reference as a shared [N, W]
   table, and as a [B, N, W] table -- what the row's way through the line search (fetched two steps ahead, staged in LDS) and
   the expansion's global reads of it cost;
+* a cost with K = 3 path constraints (tests/al_reference.py, costs.Custom(constraints=3)) against the same stage without them on
+  the Tassa shapes, non-zero multipliers: one rollout launch and one expansion launch each -- what the augmented-Lagrangian terms
+  cost --, and one multiplier update launch (isls_user_constraint_update_*);
 * the run-time compile of the Custom source (fresh source: registration with the expansion, then the program with the Tassa
   rollout kernels) and one `solve` iteration of the host slow path (the cost as numpy callables + get_Cs) at a small batch.
 Prints the numbers and one JSON line."""
@@ -33,6 +36,7 @@ for p in (os.path.join(ROOT, "ilqr-admm_amd"), ROOT, os.path.join(ROOT, "tests")
     if p not in sys.path:
         sys.path.insert(0, p)
 
+import al_reference as al  # noqa: E402
 import table_costs as tc  # noqa: E402
 import user_costs as uc  # noqa: E402
 
@@ -127,6 +131,45 @@ def table_section(a, out, g, mdl, x, u):
             print(f"tracking {what:8s} {k:13s} median {np.median(r):9.1f} us  spread {max(r) - min(r):7.1f}")
 
 
+def al_section(a, out, g, mdl, x, u):
+    from isls import costs
+    K, B = 3, a.batch
+    forms = {"plain": costs.Custom(4, 2, al.PAR, al.full_source(4, 2, 0, K, constraints=False)),
+             "constraints": costs.Custom(4, 2, al.PAR, al.full_source(4, 2, 0, K), constraints=K)}
+    engines = {}
+    for k, c in forms.items():
+        s = make(g, mdl, c, x, u, False)
+        e = s.engine
+        if k == "constraints":                                 # multipliers that stand: both branches of the PHR form are taken
+            e.cost_tab[..., :K] = 0.1
+            e.cost_tab[..., K] = 1.0
+            e.evaluate_cost()
+        e.gain(active=e.admm_active); e.feedforward(active=e.admm_active)
+        engines[k] = e
+    for what, fn in (("rollout", lambda e: e.rollout(20, active=e.admm_active)), ("expand", lambda e: e.expand())):
+        runs = {k: [] for k in engines}
+        for e in engines.values():
+            timed(lambda: fn(e), 3)
+        for _ in range(a.rounds):
+            for k, e in engines.items():
+                runs[k].append(timed(lambda: fn(e), a.reps))
+        for k, r in runs.items():
+            out[f"al_{what}_{k}_us"] = [float(np.median(r)), float(max(r) - min(r))]
+            print(f"al {what:8s} {k:13s} median {np.median(r):9.1f} us  spread {max(r) - min(r):7.1f}")
+    e = engines["constraints"]
+    viol, prev = torch.zeros(B, dtype=e.dtype, device=e.device), torch.full((B,), float("inf"), dtype=e.dtype, device=e.device)
+    keep = e.cost_tab.clone()
+
+    def update():
+        e.kern.user_constraint_update(e.cost_model, e.cost_par, e.cost_tab, e.xhat, e.uhat, viol, prev, update=True, eta=0.25, phi=1.0,
+                                      mu_max=1e8, stream=torch.cuda.current_stream().cuda_stream)
+    timed(update, 3)
+    r = [timed(update, a.reps) for _ in range(a.rounds)]
+    e.cost_tab.copy_(keep)
+    out["al_update_launch_us"] = [float(np.median(r)), float(max(r) - min(r))]
+    print(f"al update   one launch    median {np.median(r):9.1f} us  spread {max(r) - min(r):7.1f}")
+
+
 def timed(fn, reps):
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record()
@@ -142,7 +185,7 @@ def main():
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--legs", default="phuber,arm,table,host", help="comma-separated: phuber, arm, table, host")
+    ap.add_argument("--legs", default="phuber,arm,table,host", help="comma-separated: phuber, arm, table, host, al")
     a = ap.parse_args()
     legs = set(a.legs.split(","))
     from isls import costs
@@ -150,6 +193,8 @@ def main():
     out = {"batch": a.batch}
     if "table" in legs:
         table_section(a, out, g, mdl, x, u)
+    if "al" in legs:
+        al_section(a, out, g, mdl, x, u)
     if "arm" in legs:
         arm_section(a, out)
     if "phuber" in legs:
