@@ -316,6 +316,40 @@ int program(int model, int cost, int dtype, Program **out)
 
 bool dtype_ok(int dtype) { return dtype == ISLS_DTYPE_F64 || dtype == ISLS_DTYPE_F32; }
 
+// The gradient program of a source (user_grad.hpp): the text of its own program with user_grad.hpp as the device side and one
+// name expression, compiled on first request and kept apart from g_prog -- no key there, no code object there changes.  The
+// compiler's messages go to the source's log; a failure adds the sentence that names the contract.
+std::map<std::tuple<int, int, int>, Program> g_grad;         // (kind, id, dtype) -> program
+
+int grad_program(Kind kind, int id, int dtype, Program **out)
+{
+    Source *src = find(kind, id);
+    if (!src) return ISLS_ERR_ARG;
+    Program &pg = g_grad[std::make_tuple((int)kind, id, dtype)];
+    *out = &pg;
+    if (pg.tried) return pg.ok ? ISLS_OK : ISLS_ERR_COMPILE;
+    const std::string T = dtype == ISLS_DTYPE_F64 ? "double" : "float", dims = std::to_string(src->n) + ", " + std::to_string(src->m);
+    const bool cost = kind == KIND_COST;
+    pg.names = {std::string(cost ? "isls::user_cost_grad_kernel<" : "isls::user_model_grad_kernel<") + T + ", " + dims + ">"};
+    std::string text = cost ? "#include \"user_cost_ad.hpp\"\n" : "#include \"user_model_ad.hpp\"\n";
+    if (cost) {
+        text += wrap_source("isls_user_cost", "user_cost", src->source) + "#define ISLS_USER_COST_NPAR " + std::to_string(src->npar) + "\n";
+        if (src->ntab > 0) text += "#define ISLS_USER_COST_NTAB " + std::to_string(src->ntab) + "\n";
+        if (src->ncon > 0) text += "#define ISLS_USER_COST_NCON " + std::to_string(src->ncon) + "\n";
+    } else {
+        text += wrap_source("isls_user", "user_model", src->source) + "#define ISLS_USER_NPAR " + std::to_string(src->npar) + "\n";
+        if (src->ntab > 0) text += "#define ISLS_USER_MODEL_NTAB " + std::to_string(src->ntab) + "\n";
+    }
+    text += "#include \"user_grad.hpp\"\n";
+    const int rc = compile_program(text, cost ? "user_cost_grad.hip" : "user_model_grad.hip", pg, src->log);
+    if (rc != ISLS_OK)
+        src->log += std::string("the gradient program instantiates the source with P = S = a dual number: what it does with `par` and "
+                                "`row` must keep to the S contract of user_model_ad.hpp (arithmetic, comparisons and the listed "
+                                "functions; no integer cast, no plain-number copy of them).  The ") +
+                    (cost ? "cost" : "model") + "'s other programs are not affected.\n";
+    return rc;
+}
+
 }  // namespace
 
 // ---- what user_model.hip and user_cost.hip build their entry points and launches from ------------------------------------------
@@ -449,6 +483,31 @@ int prepare(int model, int cost, int dtype, int n, int m, hipStream_t s, const s
     if (rc != ISLS_OK) return rc;
     if (out) *out = pg;
     return load_program(*pg, fns, s);
+}
+
+int grad_build(Kind kind, int id, int dtype)
+{
+    if (!dtype_ok(dtype)) return ISLS_ERR_ARG;
+    std::lock_guard<std::mutex> lk(g_mu);
+    Program *pg;
+    return grad_program(kind, id, dtype, &pg);
+}
+
+int grad_prepare(Kind kind, int id, int dtype, int n, int m, hipStream_t s, hipFunction_t *fn, int *n_par, int *n_row, int *n_tab)
+{
+    std::lock_guard<std::mutex> lk(g_mu);
+    const Source *src = find(kind, id);
+    if (!src || src->n != n || src->m != m) return ISLS_ERR_ARG;
+    *n_par = src->npar; *n_tab = src->ntab;
+    *n_row = src->ncon > 0 ? src->ntab - src->ncon - 1 : src->ntab;
+    if (!fn) return ISLS_OK;
+    Program *pg;
+    int rc = grad_program(kind, id, dtype, &pg);
+    if (rc != ISLS_OK) return rc;
+    const std::vector<hipFunction_t> *fns;
+    if ((rc = load_program(*pg, &fns, s)) != ISLS_OK) return rc;
+    *fn = (*fns)[0];
+    return ISLS_OK;
 }
 
 int launch(hipFunction_t f, int grid, size_t smem, hipStream_t s, void **args)

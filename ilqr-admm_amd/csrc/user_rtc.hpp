@@ -60,6 +60,12 @@ int check_table(int cost, int N, const void *tab, int64_t tab_sb, int nvia);
 int prepare(int model, int cost, int dtype, int n, int m, hipStream_t s, const std::vector<hipFunction_t> **fns,
             const Program **pg = nullptr);
 int launch(hipFunction_t f, int grid, size_t smem, hipStream_t s, void **args);
+// The gradient program of a model or a cost (user_grad.hpp; one per source and dtype, apart from every key above): grad_build
+// compiles it on first request (no GPU needed; ISLS_ERR_COMPILE with the log and the sentence on the contract in the source's
+// log).  grad_prepare: the registration's n_par, the user's words per row n_row and the table's words per row n_tab (a cost with
+// constraints: n_row + n_con + 1) and, fn != NULL, the kernel on the current device, compiled and loaded on first use.
+int grad_build(Kind kind, int id, int dtype);
+int grad_prepare(Kind kind, int id, int dtype, int n, int m, hipStream_t s, hipFunction_t *fn, int *n_par, int *n_row, int *n_tab);
 
 template <typename T>
 constexpr int dtype_of() { return sizeof(T) == 8 ? ISLS_DTYPE_F64 : ISLS_DTYPE_F32; }

@@ -269,6 +269,21 @@ class ConstraintUpdateArgs(C.Structure):
                 ("eta", C.c_double), ("phi", C.c_double), ("mu_max", C.c_double), ("active", C.c_void_p)]
 
 
+class AdjointArgs(C.Structure):
+    """isls_adjoint_args (include/isls_hip.h)"""
+    _fields_ = [("B", C.c_int32), ("N", C.c_int32), ("n", C.c_int32), ("m", C.c_int32), ("A", View), ("Bm", View),
+                ("c0x", C.c_void_p), ("c0u", C.c_void_p), ("lam", C.c_void_p), ("gu", C.c_void_p), ("gx0", C.c_void_p),
+                ("active", C.c_void_p)]
+
+
+class UserGradArgs(C.Structure):
+    """isls_user_grad_args (include/isls_hip.h)"""
+    _fields_ = [("B", C.c_int32), ("N", C.c_int32), ("n", C.c_int32), ("m", C.c_int32), ("id", C.c_int32), ("_pad", C.c_int32),
+                ("par", C.c_void_p), ("par_sb", C.c_int64), ("tab", C.c_void_p), ("tab_sb", C.c_int64),
+                ("xhat", C.c_void_p), ("uhat", C.c_void_p), ("lam", C.c_void_p), ("g_par", C.c_void_p), ("g_tab", C.c_void_p),
+                ("active", C.c_void_p)]
+
+
 class AdvanceArgs(C.Structure):
     _fields_ = [("accept", AcceptArgs), ("lin", LinearizeArgs), ("exp", ExpandArgs),
                 ("admm_active", C.c_void_p), ("iters", C.c_void_p), ("lx", C.c_void_p), ("lu", C.c_void_p), ("res_prev", C.c_void_p)]
@@ -279,14 +294,14 @@ EXPORTED = [f"isls_{k}_{s}" for s in ("f64", "f32") for k in
             ("riccati_gain", "riccati_ff", "riccati_gain_ff", "riccati_ff_prepare", "rollout_ls", "admm_update", "project_rows", "sls_admm", "sls_closed_loop", "columns_rollout", "columns_admm", "dense_closed_loop", "mc_closed_loop", "mpc_step", "sample_nominal", "sample_nominal_fb", "cov_closed_loop", "sls_controller", "expand_quadratic", "linearize",
              "accept_step", "reduce_convergence", "reduce_convergence_table", "ilqr_admm_outer", "outer_advance", "columns_iteration",
              "user_model_step", "user_model_step_tab", "user_cost_value", "user_cost_value_tab", "user_cost_expand", "riccati_gain_reg", "reg_update",
-             "user_constraint_update")] + \
+             "user_constraint_update", "adjoint_sweep", "user_model_grad", "user_cost_grad")] + \
            ["isls_ff_segments", "isls_ff_record_elems", "isls_sls_controller_work_elems", "isls_mc_work_elems", "isls_version", "isls_dims_supported", "isls_dims_generic", "isls_error_string", "isls_timing_create",
             "isls_timing_destroy", "isls_timing_reset", "isls_timing_pause", "isls_timing_read_ms",
             "isls_gain_memo_stats", "isls_gain_memo_clear",
             "isls_user_model_create", "isls_user_model_log", "isls_user_model_code", "isls_user_model_load",
             "isls_user_cost_create", "isls_user_cost_log", "isls_user_cost_code", "isls_user_cost_load",
             "isls_user_cost_create_tab", "isls_user_cost_n_tab", "isls_user_model_create_tab", "isls_user_model_n_tab",
-            "isls_user_cost_create_con", "isls_user_cost_n_con"]
+            "isls_user_cost_create_con", "isls_user_cost_n_con", "isls_user_model_grad_build", "isls_user_cost_grad_build"]
 
 
 SET_BOX, SET_SOC_UNIT, SET_SQUARE, SET_LINEAR, SET_QUADRATIC, SET_SHELL, SET_MULTILINEAR = 1, 2, 3, 4, 5, 6, 7
@@ -338,6 +353,7 @@ def load_hip_library(path=None):
         getattr(lib, f"isls_user_{noun}_log").restype = C.c_int64
     lib.isls_user_cost_create_con.argtypes = src + [i32, i32, C.POINTER(i32)]   # (.., n_tab, n_con, &id)
     lib.isls_user_cost_n_con.argtypes = [i32]
+    lib.isls_user_model_grad_build.argtypes = lib.isls_user_cost_grad_build.argtypes = [i32, i32]
     return lib
 
 
@@ -449,6 +465,13 @@ class _UserKind:
             raise self._fail("load", rc, uid)
 
 
+    def grad_build(self, uid, dtype):
+        """The source's gradient program (isls_user_*_grad_build), compiled on first request; IslsError carries the log."""
+        rc = self._fn("grad_build")(C.c_int32(uid), _dtype_code(dtype))
+        if rc != OK:
+            raise self._fail("grad_build", rc, uid)
+
+
 _USER_MODEL, _USER_COST = _UserKind("model", MODEL_USER_BASE), _UserKind("cost", COST_USER_BASE)
 user_model_log, user_cost_log = _USER_MODEL.log, _USER_COST.log
 user_cost_n_tab = _USER_COST.n_tab
@@ -474,6 +497,16 @@ def user_model_code(model_id, dtype=np.float64):
 def user_model_load(model_id, dtype=np.float64):
     """Load the model's module onto the current device (outside any stream capture)."""
     _USER_MODEL.load(model_id, dtype=dtype)
+
+
+def user_model_grad_build(model_id, dtype=np.float64):
+    """Compile the model's gradient program (the parameter and table directions of iSLS.gradient) for dtype; needs no GPU."""
+    _USER_MODEL.grad_build(model_id, dtype)
+
+
+def user_cost_grad_build(cost_id, dtype=np.float64):
+    """The same for a cost."""
+    _USER_COST.grad_build(cost_id, dtype)
 
 
 def user_cost_create(source, n, m, n_par, n_tab=0, n_con=0):
@@ -1371,6 +1404,41 @@ class Kernels:
         if active is not None:
             a.active = _ptr(_dense(active, (B,), "active"))
         return self._call("user_constraint_update", _sfx(tab), a, stream)
+
+    def adjoint_sweep(self, A, Bm, c0x, c0u, lam, gu, gx0=None, active=None, stream=None):
+        """isls_adjoint_sweep: costate lam [B,N,n], gu [B,N,m], gx0 [B,n] from A [B|1,N,n,n] / [N,n,n] / [n,n], Bm likewise,
+        c0x [B,N,n], c0u [B,N,m]."""
+        B, N, n = c0x.shape
+        m = int(c0u.shape[2])
+        a = AdjointArgs(B=B, N=N, n=n, m=m)
+        a.A, a.Bm = make_view(A, B, N, (n, n), "A"), make_view(Bm, B, N, (n, m), "B")
+        a.c0x, a.c0u = _ptr(_dense(c0x, (B, N, n), "c0x")), _ptr(_dense(c0u, (B, N, m), "c0u"))
+        a.lam, a.gu = _ptr(_dense(lam, (B, N, n), "lam")), _ptr(_dense(gu, (B, N, m), "gu"))
+        a.gx0 = _ptr(_dense(gx0, (B, n), "gx0")) if gx0 is not None else None
+        for name, v in (("A", A), ("B", Bm), ("c0u", c0u), ("lam", lam), ("gu", gu), ("gx0", gx0)):
+            if v is not None and v.dtype != c0x.dtype:
+                raise ValueError(f"{name}: dtype {v.dtype}, c0x is {c0x.dtype}")
+        a.active = _ptr(active)
+        return self._call("adjoint_sweep", _sfx(c0x), a, stream)
+
+    def user_grad(self, noun, uid, par, xhat, uhat, lam=None, tab=None, g_par=None, g_tab=None, active=None, stream=None):
+        """isls_user_{model,cost}_grad (noun: "model" | "cost"): g_par [B,P], g_tab [B,N,W] (None: not computed) along xhat, uhat;
+        par: the model's block [par | rows] or the cost's parameters, [.] or [B,.]; tab: the cost's table [N,.] or [B,N,.]."""
+        B, N, n = xhat.shape
+        m = int(uhat.shape[2])
+        a = UserGradArgs(B=B, N=N, n=n, m=m, id=int(uid))
+        a.par, a.par_sb = _par(par, B, "par")
+        if tab is not None:
+            a.tab, a.tab_sb = _tab(tab, B, (N, int(tab.shape[-1])), "tab")
+        a.xhat, a.uhat = _ptr(_dense(xhat, (B, N, n), "xhat")), _ptr(_dense(uhat, (B, N, m), "uhat"))
+        a.lam = _ptr(_dense(lam, (B, N, n), "lam")) if lam is not None else None
+        a.g_par = _ptr(_dense(g_par, (B, int(g_par.shape[-1])), "g_par")) if g_par is not None else None
+        a.g_tab = _ptr(_dense(g_tab, (B, N, int(g_tab.shape[-1])), "g_tab")) if g_tab is not None else None
+        for name, v in (("par", par), ("tab", tab), ("uhat", uhat), ("lam", lam), ("g_par", g_par), ("g_tab", g_tab)):
+            if v is not None and v.dtype != xhat.dtype:
+                raise ValueError(f"{name}: dtype {v.dtype}, xhat is {xhat.dtype}")
+        a.active = _ptr(active)
+        return self._call(f"user_{noun}_grad", _sfx(xhat), a, stream)
 
     def user_cost_expand(self, exp, Cux, sfx, stream=None):
         """isls_user_cost_expand: `exp` an expand_args block whose cost_model is the cost's id; Cux [B,N,m,n] or None."""

@@ -559,6 +559,30 @@ class iSLS(Base):
         return AlResult(log, f.penalty.copy(), rounds, final.cpu().numpy().astype(np.float64) <= tol_con,
                         np.atleast_1d(np.array(self.cost, dtype=np.float64)).copy())
 
+    # ---- gradients of the nominal's cost ------------------------------------------------------------------------
+    def gradient(self, wrt=("u", "x0"), as_tensors=False):
+        """Gradients of J = `cost` of the current nominal by an adjoint sweep on the device (isls/gradient.py).  J is the sum of
+        the stage costs along the nominal with x_0 given and x_{t+1} = f(x_t, u_t): for a costs.Custom(constraints=) it includes
+        the augmented-Lagrangian terms at the multipliers that stand; ADMM's proximal terms are not part of it.
+        wrt: any of "u", "x0", "cost_params", "model_params", "cost_table", "model_table".  Returns a Gradient with cost [B],
+        costate [B, N, n] (lambda_t = dJ/dx_t along the dynamics) and, where asked for (else None), u [B, N, m], x0 [B, n] (=
+        costate[:, 0]), cost_params [B, Pc], model_params [B, Pm], cost_table [B, N, Wc], model_table [B, N, Wm] (row N-1: 0, the
+        last control steps nothing) -- numpy arrays, or torch tensors on the device with as_tensors=True.  Shared params [P] /
+        tables [N, W] still give one gradient per trajectory: sum over the batch for the shared quantity's.
+        What it is: the TOTAL derivative of J at FIXED controls, at whatever nominal stands.  At a converged unconstrained
+        `solve` the envelope theorem makes it the derivative of the optimal cost as well; after `solve_al` it is the derivative
+        of the Lagrangian at the multipliers that stand; under an active projection of `ilqr_admm` it is only the fixed-controls
+        derivative.  Nothing more is promised: no derivative of the optimal trajectory, none with respect to the multipliers.
+        "u", "x0" and the costate serve every device model and cost (built-in, Custom, the generic (x_dim, u_dim) pairs, a
+        caller's A, B from the AB setter); the parameter / table entries need the models.Custom / costs.Custom they belong to, whose
+        source must keep to the S contract of csrc/user_model_ad.hpp in what it does with `par` and `row` too (the gradient program
+        is compiled on the first request; IslsError with the compile log otherwise).  IslsError for an unknown entry, a missing
+        Custom object or table, or a model / cost given as a Python callable -- before anything is launched.
+        The call linearises and expands about the nominal (A, B, c0x, c0u are rewritten, as every solver rewrites them first) and
+        touches nothing else: gains, records, regularisation state, multipliers and the nominal stay as they are."""
+        from .gradient import gradient
+        return gradient(self, wrt, as_tensors)
+
     # ---- iLQR-ADMM (DP form) --------------------------------------------------------------------------------
     def ilqr_admm(self, get_AB=None, get_Cs=None, project_x=False, project_u=False, max_iter=20,
                   max_line_search_iter=20, max_admm_iter=20, rho_x=None, rho_u=None, alpha=1, tol=1e-3,

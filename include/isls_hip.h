@@ -948,6 +948,62 @@ int isls_user_cost_expand_f64(const isls_expand_args *a, void *Cux, void *stream
 int isls_user_cost_expand_f32(const isls_expand_args *a, void *Cux, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Gradients of the nominal's cost by an adjoint sweep.  J = sum_{t=0}^{N-1} c_t(x_t, u_t) with x_0 given and x_{t+1} =
+ * f(x_t, u_t, row_t) for t <= N-2 (u_{N-1} is costed and steps nothing, as in the line search).  With A_t, B_t of isls_linearize_*
+ * and c0x, c0u of an expansion about the same nominal (no ADMM weights: Qr, Rr are not part of J), the TOTAL derivative of J at
+ * fixed controls is
+ *   lam_{N-1} = c0x_{N-1} ;   lam_t = c0x_t + A_t' lam_{t+1}   (t = N-2 .. 0)
+ *   gu_t = c0u_t + B_t' lam_{t+1}   (t <= N-2) ;   gu_{N-1} = c0u_{N-1} ;   gx0 = lam_0
+ * (each product summed from zero in index order, then added to the cost term).  A, Bm: views with any batch and time stride (a
+ * batch stride of 0: one pair for the batch); c0x [B,N,n], c0u [B,N,m] dense; lam [B,N,n], gu [B,N,m], gx0 [B,n] (nullable).  A
+ * trajectory with active[b] == 0 is left untouched in all three.  Served for every fast pair and for the generic pairs (n <= 16,
+ * m <= 8); ISLS_ERR_UNSUPPORTED beyond, ISLS_ERR_ARG for a NULL array or a negative stride.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct isls_adjoint_args {
+    int32_t B, N, n, m;
+    isls_view A, Bm;
+    const void *c0x, *c0u;
+    void *lam, *gu;
+    void *gx0;                      /* nullable */
+    const int32_t *active;          /* [B], nullable */
+} isls_adjoint_args;
+int isls_adjoint_sweep_f64(const isls_adjoint_args *a, void *stream);
+int isls_adjoint_sweep_f32(const isls_adjoint_args *a, void *stream);
+
+/* The directions of J that the sweep does not reach: the parameters and the per-step tables of a user model and a user cost.
+ * They come from a program of their own per source and dtype, built on first request (isls_user_*_grad_build; needs no GPU): it
+ * instantiates the source with S = P = a forward-mode dual number -- x, u constants, one word of [par | row] seeded -- so a source
+ * must keep to the S contract of csrc/user_model_ad.hpp in what it does with `par` and `row` as well (no cast of them to an
+ * integer, no plain-number temporaries of them).  A source that does not keeps working everywhere else: only this build fails,
+ * ISLS_ERR_COMPILE, with the compiler's messages and that sentence in the source's log.  No other program of the source changes.
+ *   model:  g_par[b,p] = sum_{t <= N-2} lam_{t+1}' df/dpar_p (x_t, u_t, row_t) ;  g_tab[b,t,w] = lam_{t+1}' df/drow_w  (row N-1: 0)
+ *   cost:   g_par[b,p] = sum_t dc_t/dpar_p ;                                      g_tab[b,t,w] = dc_t/drow_w
+ * One wavefront per (trajectory, direction); its lanes stride over the steps and the sum over t is a wave reduction in a fixed
+ * order (no atomics: two launches give the same bits).  par / par_sb: the model's block [par | rows] as in isls_linearize_args
+ * (its table is read from there), or the cost's parameters; tab / tab_sb: the cost's table as in isls_expand_args.ztab (unused
+ * for a model).  A cost with constraints is differentiated in its PHR-augmented form at the multipliers in the table; only the
+ * user's W words of a row are directions (g_tab [B,N,W]), the multipliers and mu are constants.  g_par [B,n_par], g_tab
+ * [B,N,W]: either may be NULL (not computed).  Per-trajectory outputs also where par / tab are shared: the caller sums.
+ * lam: the costate [B,N,n] of isls_adjoint_sweep_* (model only).  active as above. */
+typedef struct isls_user_grad_args {
+    int32_t B, N, n, m;
+    int32_t id;                     /* the model's or the cost's id */
+    int32_t _pad;
+    const void *par; int64_t par_sb;
+    const void *tab; int64_t tab_sb;
+    const void *xhat, *uhat;        /* [B,N,n], [B,N,m] */
+    const void *lam;
+    void *g_par, *g_tab;
+    const int32_t *active;
+} isls_user_grad_args;
+int isls_user_model_grad_build(int32_t id, int32_t dtype);
+int isls_user_cost_grad_build(int32_t id, int32_t dtype);
+int isls_user_model_grad_f64(const isls_user_grad_args *a, void *stream);
+int isls_user_model_grad_f32(const isls_user_grad_args *a, void *stream);
+int isls_user_cost_grad_f64(const isls_user_grad_args *a, void *stream);
+int isls_user_cost_grad_f32(const isls_user_grad_args *a, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Monte-Carlo validation of a batch of controllers: M closed loops of each of P problems through its forward model and its own
  * controller, from random (or given) initial states and under random (or given) process noise, in one launch
  * (get_trajectory_sls, isls/isls_base.py:28-42 and isls/sls_base.py:91-105; get_trajectory_dp / _batch, isls/sls_base.py:61-89):
