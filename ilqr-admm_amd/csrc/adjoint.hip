@@ -11,6 +11,7 @@
 //   * every lane keeps a ring of D steps of its column and its gradient entry in flight in registers; the loads are
 //     unconditional (steps past the start are clamped, idle lanes shadow the block's first trajectory);
 //   * the one hand-off of a step is lam_{t+1}: the x-lanes publish it in the slot's n words of LDS (slot_sync, no s_barrier).
+#include "entry.hpp"
 #include "isls_common.hpp"
 
 namespace isls {
@@ -161,13 +162,4 @@ int launch_adjoint(const isls_adjoint_args &a, hipStream_t s)
 
 using namespace isls;
 
-#define ISLS_API extern "C" __attribute__((visibility("default")))
-
-ISLS_API int isls_adjoint_sweep_f64(const isls_adjoint_args *a, void *stream)
-{
-    return a ? launch_adjoint<double>(*a, (hipStream_t)stream) : ISLS_ERR_ARG;
-}
-ISLS_API int isls_adjoint_sweep_f32(const isls_adjoint_args *a, void *stream)
-{
-    return a ? launch_adjoint<float>(*a, (hipStream_t)stream) : ISLS_ERR_ARG;
-}
+ISLS_ENTRY(adjoint_sweep, isls_adjoint_args, launch_adjoint, false)

@@ -1,6 +1,6 @@
 // sampling.hip -- isls_sample_nominal_*: argument checks and dispatch of one sampling round about the nominal (kernel templates:
 // sampling.hpp).  The (n, m, model) families of families.def run the library's instantiations; a user model and / or a user
-// cost runs the two kernels of its run-time compiled (model, cost) program (user_rtc.hip).  isls_sample_nominal_fb_* is the same
+// cost runs the sampling kernels of its run-time compiled (model, cost) program (user_rtc.hip).  isls_sample_nominal_fb_* is the same
 // round in closed loop about the caller's gains: the same checks and dispatch, the *_fb_kernel pair and its argument block.
 #include "sampling.hpp"
 #include "user_rtc.hpp"
@@ -13,18 +13,15 @@ template <typename T>
 int launch_sample_user(const SampleP<T> &p0, int model, int cost, int n, int m, size_t smem_cost, size_t smem_update, int phase, hipStream_t s,
                        const T *K, int64_t K_sb)
 {
-    const urtc::Program *pg;
-    const std::vector<hipFunction_t> *fns;
-    const int rc = urtc::prepare(model, cost, urtc::dtype_of<T>(), n, m, s, &fns, &pg);
+    urtc::Kernels k;
+    const int rc = urtc::prepare(model, cost, urtc::dtype_of<T>(), n, m, s, &k);
     if (rc != ISLS_OK) return rc;
-    if (pg->smp0 < 0) return ISLS_ERR_UNSUPPORTED;
     SampleP<T> p = p0;
     SampleFbP<T> q = {p0, K, K_sb};
     void *args[] = {K ? (void *)&q : (void *)&p};
-    const int k0 = pg->smp0 + (K ? 2 : 0);                    // the closed-loop pair lies behind the open-loop one
     const int64_t grid = (int64_t)p.B * p.chunks;
-    const int rc1 = phase == 2 ? ISLS_OK : urtc::launch((*fns)[k0], (int)grid, smem_cost, s, args);
-    return rc1 != ISLS_OK || phase == 1 ? rc1 : urtc::launch((*fns)[k0 + 1], p.B, smem_update, s, args);
+    const int rc1 = phase == 2 ? ISLS_OK : urtc::launch(k.of(K ? urtc::ROLE_SMP_COST_FB : urtc::ROLE_SMP_COST), (int)grid, smem_cost, s, args);
+    return rc1 != ISLS_OK || phase == 1 ? rc1 : urtc::launch(k.of(K ? urtc::ROLE_SMP_UPDATE_FB : urtc::ROLE_SMP_UPDATE), p.B, smem_update, s, args);
 }
 template int launch_sample_user<double>(const SampleP<double> &, int, int, int, int, size_t, size_t, int, hipStream_t, const double *, int64_t);
 template int launch_sample_user<float>(const SampleP<float> &, int, int, int, int, size_t, size_t, int, hipStream_t, const float *, int64_t);
@@ -78,15 +75,8 @@ static int launch_sample_round(const isls_sample_args &a, bool fb, const T *K, i
     const SampleFbP<T> q = {p, K, K_sb};
     if (umodel || ucost) {
         // a user model keeps its parameters in registers; a built-in model under a user cost brings its LDS words
-        int mdlw = 0;
-        if (!umodel) {
-            bool found = false;
-#define ISLS_SMP_FAMILY_(NX_, NU_, MODEL_) \
-    if (a.n == NX_ && a.m == NU_ && a.model == MODEL_) { mdlw = Model<T, NX_, NU_, MODEL_>::LDS_WORDS; found = true; }
-            ISLS_FOR_EACH_FAMILY(ISLS_SMP_FAMILY_)
-#undef ISLS_SMP_FAMILY_
-            if (!found) return ISLS_ERR_UNSUPPORTED;
-        }
+        const int mdlw = umodel ? 0 : family_lds_words(a.n, a.m, a.model);
+        if (mdlw < 0) return ISLS_ERR_UNSUPPORTED;
         const size_t smem2 = smp_mdl_words(mdlw) * sizeof(T) + ubytes;
         if (smem2 > kSmpMaxLds) return ISLS_ERR_UNSUPPORTED;
         return launch_sample_user<T>(p, a.model, ucost ? a.cost_model : urtc::kNone, a.n, a.m, mdlw * sizeof(T), smem2, a.phase, s,

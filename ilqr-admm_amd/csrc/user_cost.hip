@@ -2,22 +2,17 @@
 // constraints, the multiplier update (the device side is user_cost.hpp) -- and the isls_user_cost_* entry points.  Registry,
 // run-time compilation, module loading and the line search are user_rtc.hip's: the programs of a cost are the keys (model or
 // none, cost) there, and every one of them holds these kernels.
+#include "entry.hpp"
 #include "user_rtc.hpp"
 
 namespace isls {
 
-namespace {
-
-enum Fn { FN_EXP = 0, FN_VAL };                              // the order of the key's name expressions (user_rtc.hip)
-
-// the expansion and the value of cost `id` for a launch of dims (n, m): whichever of its programs is on the device
+// the kernels of cost `id` for a launch of dims (n, m): whichever of its programs is on the device
 template <typename T>
-int prepare(int id, int n, int m, hipStream_t s, const std::vector<hipFunction_t> **fns)
+static int prepare(int id, int n, int m, hipStream_t s, urtc::Kernels *k)
 {
-    return urtc::prepare(urtc::kNone, id, urtc::dtype_of<T>(), n, m, s, fns);
+    return urtc::prepare(urtc::kNone, id, urtc::dtype_of<T>(), n, m, s, k);
 }
-
-}  // namespace
 
 template <typename T>
 static int user_cost_value(int32_t id, int32_t R, int32_t N, const void *par, int64_t par_sb, const void *tab, int64_t tab_sb,
@@ -28,13 +23,13 @@ static int user_cost_value(int32_t id, int32_t R, int32_t N, const void *par, in
     int rc = urtc::dims(urtc::KIND_COST, id, &n, &m);
     if (rc == ISLS_OK) rc = urtc::check_table(id, N, tab, tab_sb, -1);   // (a cost with a table through the entry without one: NULL)
     if (rc != ISLS_OK || R == 0) return rc;
-    const std::vector<hipFunction_t> *fns;
-    if ((rc = prepare<T>(id, n, m, s, &fns)) != ISLS_OK) return rc;
+    urtc::Kernels k;
+    if ((rc = prepare<T>(id, n, m, s, &k)) != ISLS_OK) return rc;
     int R_ = R, N_ = N;
     const T *par_ = (const T *)par, *x_ = (const T *)x, *u_ = (const T *)u, *tab_ = (const T *)tab;
     T *cost_ = (T *)cost;
     void *args[] = {&R_, &N_, &par_, &par_sb, &x_, &u_, &cost_, &active, &tab_, &tab_sb};
-    return urtc::launch((*fns)[FN_VAL], (R + 63) / 64, 0, s, args);
+    return urtc::launch(k.of(urtc::ROLE_VAL), (R + 63) / 64, 0, s, args);
 }
 
 // ---- launches (dispatched from misc.hip on a.cost_model >= ISLS_COST_USER_BASE) ----------------------------------------------
@@ -45,8 +40,8 @@ int launch_expand_user_cost(const isls_expand_args &a, void *Cux, hipStream_t s)
     if (a.B == 0) return ISLS_OK;
     int rc = urtc::check_table(a.cost_model, a.N, a.ztab, a.ztab_sb, a.nvia);   // the table: ztab, ztab_sb, nvia (isls_hip.h)
     if (rc != ISLS_OK) return rc;
-    const std::vector<hipFunction_t> *fns;
-    if ((rc = prepare<T>(a.cost_model, a.n, a.m, s, &fns)) != ISLS_OK) return rc;
+    urtc::Kernels k;
+    if ((rc = prepare<T>(a.cost_model, a.n, a.m, s, &k)) != ISLS_OK) return rc;
     const int K = a.n + a.m, NP = K * (K + 1) / 2, steps = NP <= kWave ? kWave / NP : 4;   // user_expand_kernel's S
     UserExpP<T> p;
     p.B = a.B; p.N = a.N; p.nbt = (a.N + steps - 1) / steps;
@@ -59,7 +54,7 @@ int launch_expand_user_cost(const isls_expand_args &a, void *Cux, hipStream_t s)
     const int64_t grid = (int64_t)a.B * p.nbt;
     if (grid > 0x7fffffff) return ISLS_ERR_UNSUPPORTED;
     void *args[] = {&p};
-    if ((rc = urtc::launch((*fns)[FN_EXP], (int)grid, 0, s, args)) != ISLS_OK || !a.cost) return rc;
+    if ((rc = urtc::launch(k.of(urtc::ROLE_EXP), (int)grid, 0, s, args)) != ISLS_OK || !a.cost) return rc;
     return user_cost_value<T>(a.cost_model, a.B, a.N, a.cost_par, a.cost_par_sb, a.ztab, a.ztab_sb, a.xhat, a.uhat, a.cost, a.active, s);
 }
 template int launch_expand_user_cost<double>(const isls_expand_args &, void *, hipStream_t);
@@ -79,10 +74,8 @@ static int launch_constraint_update(const isls_constraint_update_args &a, hipStr
     if (a.tab_sb != (int64_t)a.N * urtc::n_tab(a.cost_model) && a.B > 1) return ISLS_ERR_ARG;
     if (a.update && !(a.phi >= 1.0 && a.mu_max >= 0.0 && a.eta >= 0.0)) return ISLS_ERR_ARG;
     if (a.B == 0) return ISLS_OK;
-    const std::vector<hipFunction_t> *fns;
-    const urtc::Program *pg;
-    if ((rc = urtc::prepare(urtc::kNone, a.cost_model, urtc::dtype_of<T>(), n, m, s, &fns, &pg)) != ISLS_OK) return rc;
-    if (pg->con < 0) return ISLS_ERR_ARG;
+    urtc::Kernels k;
+    if ((rc = prepare<T>(a.cost_model, n, m, s, &k)) != ISLS_OK) return rc;
     UserConP<T> p;
     p.B = a.B; p.N = a.N; p.update = a.update ? 1 : 0;
     p.par = (const T *)a.cost_par; p.par_sb = a.cost_par_sb;
@@ -92,14 +85,12 @@ static int launch_constraint_update(const isls_constraint_update_args &a, hipStr
     p.eta = (T)a.eta; p.phi = (T)a.phi; p.mu_max = (T)a.mu_max;
     p.active = a.active;
     void *args[] = {&p};
-    return urtc::launch((*fns)[pg->con], a.B, 0, s, args);
+    return urtc::launch(k.of(urtc::ROLE_CON_UPDATE), a.B, 0, s, args);
 }
 
 }  // namespace isls
 
 using namespace isls;
-
-#define ISLS_API extern "C" __attribute__((visibility("default")))
 
 ISLS_API int isls_user_cost_create(const char *source, int32_t n, int32_t m, int32_t n_par, int32_t *id)
 {
@@ -133,41 +124,13 @@ ISLS_API int isls_user_cost_load(int32_t id, int32_t model, int32_t dtype)
     return is_user_cost(id) ? urtc::load(model < 0 ? urtc::kNone : model, id, dtype) : ISLS_ERR_ARG;
 }
 
-ISLS_API int isls_user_cost_value_f64(int32_t id, int32_t R, int32_t N, const void *par, int64_t par_sb, const void *x, const void *u,
-                                      void *cost, void *stream)
-{
-    return user_cost_value<double>(id, R, N, par, par_sb, nullptr, 0, x, u, cost, nullptr, (hipStream_t)stream);
-}
-ISLS_API int isls_user_cost_value_f32(int32_t id, int32_t R, int32_t N, const void *par, int64_t par_sb, const void *x, const void *u,
-                                      void *cost, void *stream)
-{
-    return user_cost_value<float>(id, R, N, par, par_sb, nullptr, 0, x, u, cost, nullptr, (hipStream_t)stream);
-}
-ISLS_API int isls_user_cost_value_tab_f64(int32_t id, int32_t R, int32_t N, const void *par, int64_t par_sb, const void *tab, int64_t tab_sb,
-                                          const void *x, const void *u, void *cost, void *stream)
-{
-    return user_cost_value<double>(id, R, N, par, par_sb, tab, tab_sb, x, u, cost, nullptr, (hipStream_t)stream);
-}
-ISLS_API int isls_user_cost_value_tab_f32(int32_t id, int32_t R, int32_t N, const void *par, int64_t par_sb, const void *tab, int64_t tab_sb,
-                                          const void *x, const void *u, void *cost, void *stream)
-{
-    return user_cost_value<float>(id, R, N, par, par_sb, tab, tab_sb, x, u, cost, nullptr, (hipStream_t)stream);
-}
-
-ISLS_API int isls_user_cost_expand_f64(const isls_expand_args *a, void *Cux, void *stream)
-{
-    return a && is_user_cost(a->cost_model) ? launch_expand_user_cost<double>(*a, Cux, (hipStream_t)stream) : ISLS_ERR_ARG;
-}
-ISLS_API int isls_user_cost_expand_f32(const isls_expand_args *a, void *Cux, void *stream)
-{
-    return a && is_user_cost(a->cost_model) ? launch_expand_user_cost<float>(*a, Cux, (hipStream_t)stream) : ISLS_ERR_ARG;
-}
-
-ISLS_API int isls_user_constraint_update_f64(const isls_constraint_update_args *a, void *stream)
-{
-    return a && is_user_cost(a->cost_model) ? launch_constraint_update<double>(*a, (hipStream_t)stream) : ISLS_ERR_ARG;
-}
-ISLS_API int isls_user_constraint_update_f32(const isls_constraint_update_args *a, void *stream)
-{
-    return a && is_user_cost(a->cost_model) ? launch_constraint_update<float>(*a, (hipStream_t)stream) : ISLS_ERR_ARG;
-}
+ISLS_TYPED_PAIR(user_cost_value, (int32_t id, int32_t R, int32_t N, const void *par, int64_t par_sb, const void *x, const void *u, void *cost,
+                                  void *stream),
+                return user_cost_value<T>(id, R, N, par, par_sb, nullptr, 0, x, u, cost, nullptr, (hipStream_t)stream);)
+ISLS_TYPED_PAIR(user_cost_value_tab, (int32_t id, int32_t R, int32_t N, const void *par, int64_t par_sb, const void *tab, int64_t tab_sb,
+                                      const void *x, const void *u, void *cost, void *stream),
+                return user_cost_value<T>(id, R, N, par, par_sb, tab, tab_sb, x, u, cost, nullptr, (hipStream_t)stream);)
+ISLS_TYPED_PAIR(user_cost_expand, (const isls_expand_args *a, void *Cux, void *stream),
+                return a && is_user_cost(a->cost_model) ? launch_expand_user_cost<T>(*a, Cux, (hipStream_t)stream) : ISLS_ERR_ARG;)
+ISLS_TYPED_PAIR(user_constraint_update, (const isls_constraint_update_args *a, void *stream),
+                return a && is_user_cost(a->cost_model) ? launch_constraint_update<T>(*a, (hipStream_t)stream) : ISLS_ERR_ARG;)

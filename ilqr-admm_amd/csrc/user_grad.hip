@@ -1,6 +1,7 @@
 // user_grad.hip -- the parameter and table directions of the nominal's cost for user-written models and costs: the launches of
 // user_model_grad_kernel / user_cost_grad_kernel (the device side is user_grad.hpp) and the isls_user_*_grad_* entry points.  The
 // program of a source's gradient is built and kept by user_rtc.hip, apart from the source's other programs.
+#include "entry.hpp"
 #include "user_grad.hpp"
 #include "user_rtc.hpp"
 
@@ -40,8 +41,6 @@ static int launch_user_grad(urtc::Kind kind, const isls_user_grad_args &a, hipSt
 
 using namespace isls;
 
-#define ISLS_API extern "C" __attribute__((visibility("default")))
-
 ISLS_API int isls_user_model_grad_build(int32_t id, int32_t dtype)
 {
     return is_user_model(id) ? urtc::grad_build(urtc::KIND_MODEL, id, dtype) : ISLS_ERR_ARG;
@@ -50,19 +49,7 @@ ISLS_API int isls_user_cost_grad_build(int32_t id, int32_t dtype)
 {
     return is_user_cost(id) ? urtc::grad_build(urtc::KIND_COST, id, dtype) : ISLS_ERR_ARG;
 }
-ISLS_API int isls_user_model_grad_f64(const isls_user_grad_args *a, void *stream)
-{
-    return a ? launch_user_grad<double>(urtc::KIND_MODEL, *a, (hipStream_t)stream) : ISLS_ERR_ARG;
-}
-ISLS_API int isls_user_model_grad_f32(const isls_user_grad_args *a, void *stream)
-{
-    return a ? launch_user_grad<float>(urtc::KIND_MODEL, *a, (hipStream_t)stream) : ISLS_ERR_ARG;
-}
-ISLS_API int isls_user_cost_grad_f64(const isls_user_grad_args *a, void *stream)
-{
-    return a ? launch_user_grad<double>(urtc::KIND_COST, *a, (hipStream_t)stream) : ISLS_ERR_ARG;
-}
-ISLS_API int isls_user_cost_grad_f32(const isls_user_grad_args *a, void *stream)
-{
-    return a ? launch_user_grad<float>(urtc::KIND_COST, *a, (hipStream_t)stream) : ISLS_ERR_ARG;
-}
+ISLS_TYPED_PAIR(user_model_grad, (const isls_user_grad_args *a, void *stream),
+                return a ? launch_user_grad<T>(urtc::KIND_MODEL, *a, (hipStream_t)stream) : ISLS_ERR_ARG;)
+ISLS_TYPED_PAIR(user_cost_grad, (const isls_user_grad_args *a, void *stream),
+                return a ? launch_user_grad<T>(urtc::KIND_COST, *a, (hipStream_t)stream) : ISLS_ERR_ARG;)

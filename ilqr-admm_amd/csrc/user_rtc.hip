@@ -2,12 +2,13 @@
 // sources, the cache of compiled programs, module loading and the line-search launch (user_rtc.hpp; the device side is
 // user_model.hpp / user_cost.hpp, the launches of a model's and a cost's own kernels are user_model.hip / user_cost.hip).
 //
-// One hiprtc program per (model, cost, dtype).  (user model, none) holds the model's linearisation, dense closed loop and row-wise
-// step, (none, cost) the cost's expansion and value, (model, cost) -- the model a built-in id or a user model, whose source goes
-// into the same program -- the cost's two kernels again; and every key with a model holds each rollout_kernel variant the launch
-// plan can pick for its (n, m).  The rollout launch takes its plan from plan_rollout -- the very function the built-in families
-// launch with -- and differs only in how it starts the kernel (hipModuleLaunchKernel of the matching instantiation in the key's
-// module instead of hipLaunchKernelGGL).
+// One hiprtc program per (model, cost, dtype).  (user model, none) holds the model's own kernels, (none, cost) the cost's,
+// (model, cost) -- the model a built-in id or a user model, whose source goes into the same program -- the cost's again; and
+// every key with a model holds each rollout_kernel variant the launch plan can pick for its (n, m) and the sampling round.
+// program() registers every kernel under its Role (user_rtc.hpp) or its (JM, OCC), and a launch asks for it by that: where a
+// name expression lies is written down nowhere else.  The rollout launch takes its plan from plan_rollout -- the very function
+// the built-in families launch with -- and differs only in how it starts the kernel (hipModuleLaunchKernel of the matching
+// instantiation in the key's module instead of hipLaunchKernelGGL).
 #ifndef _GNU_SOURCE
 #define _GNU_SOURCE                                          // dlmopen
 #endif
@@ -177,7 +178,7 @@ int compile_program(const std::string &src, const char *file, Program &pg, std::
     return ok ? ISLS_OK : ISLS_ERR_COMPILE;
 }
 
-// the program's functions (index: pg.names) on the current device, loaded on first use -- never inside a stream capture
+// the program's functions (in the order of pg.names) on the current device, loaded on first use -- never inside a stream capture
 // (capture_check: the stream to test, or nullptr)
 int load_program(Program &pg, const std::vector<hipFunction_t> **out, hipStream_t capture_check)
 {
@@ -235,83 +236,80 @@ void ro_variants(std::vector<std::pair<int, int>> &v)
         }
 }
 
-// the built-in family (n, m, model) and its LDS words
-bool builtin_family(int n, int m, int model, int *mdlw)
+// The text of a program: the dual-number header (the cost's where there is a cost), the user model and the user cost (either may
+// be absent), each in its namespace with the defines of its registration behind it, and the device side `device_hpp` last.
+std::string program_text(const Source *um, const Source *uc, const char *device_hpp)
 {
-#define ISLS_URTC_FAMILY_(NX_, NU_, MODEL_) \
-    if (n == NX_ && m == NU_ && model == MODEL_) { *mdlw = Model<double, NX_, NU_, MODEL_>::LDS_WORDS; return true; }
-    ISLS_FOR_EACH_FAMILY(ISLS_URTC_FAMILY_)
-#undef ISLS_URTC_FAMILY_
-    return false;
-}
-
-// The program of (model, cost, dtype), compiled on first use: its text, its file name and its name expressions in order --
-// lin, loop, step, Monte-Carlo loop, control step, rollouts for a model alone; exp, val, rollouts (none without a model) for a cost;
-// behind them the four kernels of the sampling round (the open-loop pair, then the closed-loop pair) where the key has a model.  The
-// compiler's messages go to the cost's log, to the model's when there is no cost.  ISLS_ERR_ARG: no such source, or a model and
-// a cost of different dimensions; ISLS_ERR_UNSUPPORTED: a built-in model with no family for the cost's dimensions.
-int program(int model, int cost, int dtype, Program **out)
-{
-    Source *um = is_user_model(model) ? find(KIND_MODEL, model) : nullptr, *uc = cost != kNone ? find(KIND_COST, cost) : nullptr;
-    if ((is_user_model(model) && !um) || (cost != kNone && !uc) || (!um && !uc)) return ISLS_ERR_ARG;
-    if (um && uc && (um->n != uc->n || um->m != uc->m)) return ISLS_ERR_ARG;
-    const int n = uc ? uc->n : um->n, m = uc ? uc->m : um->m;
-    int mdlw = 0;
-    if (!um && model != kNone && !builtin_family(n, m, model, &mdlw)) return ISLS_ERR_UNSUPPORTED;
-    Program &pg = g_prog[std::make_tuple(cost, dtype, model)];
-    *out = &pg;
-    if (pg.tried) return pg.ok ? ISLS_OK : ISLS_ERR_COMPILE;
-    const std::string T = dtype == ISLS_DTYPE_F64 ? "double" : "float", dims = std::to_string(n) + ", " + std::to_string(m);
-    const std::string tmodel = std::to_string(um ? ISLS_MODEL_USER : model);   // the MODEL template argument
-    if (uc)
-        pg.names = {"isls::user_expand_kernel<" + T + ", " + dims + ">", "isls::user_cost_value_kernel<" + T + ", " + dims + ">"};
-    else
-        pg.names = {"isls::user_linearize_kernel<" + T + ", " + dims + ">",
-                    "isls::dense_closed_loop_kernel<" + T + ", " + dims + ", " + tmodel + ">",
-                    "isls::user_step_kernel<" + T + ", " + dims + ">",
-                    "isls::mc_closed_loop_kernel<" + T + ", " + dims + ", " + tmodel + ">",
-                    "isls::mpc_step_kernel<" + T + ", " + dims + ", " + tmodel + ">"};
-    pg.ro0 = (int)pg.names.size();
-    pg.mdlw = mdlw;
-    pg.ntab = uc ? uc->ntab : 0;
-    pg.mtab = um ? um->ntab : 0;
-    pg.ro.clear();
-    if (model != kNone) {
-#define ISLS_URTC_VARIANTS_(NX_, NU_) if (n == NX_ && m == NU_) ro_variants<NX_, NU_>(pg.ro);
-        ISLS_FOR_EACH_DIMS(ISLS_URTC_VARIANTS_)
-#undef ISLS_URTC_VARIANTS_
-    }
-    for (const auto &jo : pg.ro)
-        pg.names.push_back("isls::rollout_kernel<" + T + ", " + dims + ", " + tmodel + ", " + std::to_string(jo.first) + ", " +
-                           std::to_string(jo.second) + ">");
-    // the sampling round's two kernels (sampling.hpp) of a key with a model, behind every other name: no earlier index moves
-    pg.smp0 = -1;
-    if (model != kNone) {
-        pg.smp0 = (int)pg.names.size();
-        // (the closed-loop pair of isls_sample_nominal_fb_* behind the open-loop one: smp0 + 2, smp0 + 3)
-        for (const char *k : {"isls::sample_cost_kernel<", "isls::sample_update_kernel<", "isls::sample_cost_fb_kernel<", "isls::sample_update_fb_kernel<"})
-            pg.names.push_back(k + T + ", " + dims + ", " + tmodel + ">");
-    }
-    // a table model's own program: its row-wise step with a row per state row, behind every other name
-    pg.stab = -1;
-    if (um && !uc && um->ntab > 0) {
-        pg.stab = (int)pg.names.size();
-        pg.names.push_back("isls::user_step_tab_kernel<" + T + ", " + dims + ">");
-    }
-    // a cost with constraints: its multiplier update, behind every other name
-    pg.con = -1;
-    if (uc && uc->ncon > 0) {
-        pg.con = (int)pg.names.size();
-        pg.names.push_back("isls::user_constraint_update_kernel<" + T + ", " + dims + ">");
-    }
     std::string src = uc ? "#include \"user_cost_ad.hpp\"\n" : "#include \"user_model_ad.hpp\"\n";
     if (um) src += wrap_source("isls_user", "user_model", um->source) + "#define ISLS_USER_NPAR " + std::to_string(um->npar) + "\n";
     if (um && um->ntab > 0) src += "#define ISLS_USER_MODEL_NTAB " + std::to_string(um->ntab) + "\n";
     if (uc) src += wrap_source("isls_user_cost", "user_cost", uc->source) + "#define ISLS_USER_COST_NPAR " + std::to_string(uc->npar) + "\n";
     if (uc && uc->ntab > 0) src += "#define ISLS_USER_COST_NTAB " + std::to_string(uc->ntab) + "\n";
     if (uc && uc->ncon > 0) src += "#define ISLS_USER_COST_NCON " + std::to_string(uc->ncon) + "\n";
-    src += uc ? "#include \"user_cost.hpp\"\n" : "#include \"user_model.hpp\"\n";
-    return compile_program(src, uc ? "user_cost.hip" : "user_model.hip", pg, (uc ? uc : um)->log);
+    return src + "#include \"" + device_hpp + "\"\n";
+}
+
+// The name expressions of a program as it is put together: kernel `k` of dims (n, m) in T, its further template arguments in
+// `more`, goes behind the names so far and its slot to the role or to the rollout variant.  Nobody else knows a position.
+struct Names {
+    Program &pg;
+    std::string head;                                        // "<T, n, m"
+    Names(Program &pg_, int dtype, int n, int m)
+        : pg(pg_), head(std::string(dtype == ISLS_DTYPE_F64 ? "<double, " : "<float, ") + std::to_string(n) + ", " + std::to_string(m)) {}
+    int add(const char *k, const std::string &more = std::string())
+    {
+        pg.names.push_back(std::string("isls::") + k + head + more + ">");
+        return (int)pg.names.size() - 1;
+    }
+    void role(Role r, const char *k, const std::string &more = std::string()) { pg.slot[r] = add(k, more); }
+};
+
+// The program of (model, cost, dtype), compiled on first use: a user model alone holds its own kernels, every key with a cost the
+// cost's, every key with a model the rollout variants of its dimensions and the sampling round.  The compiler's messages go to
+// the cost's log, to the model's when there is no cost.  ISLS_ERR_ARG: no such source, or a model and a cost of different
+// dimensions; ISLS_ERR_UNSUPPORTED: a built-in model with no family for the cost's dimensions.
+int program(int model, int cost, int dtype, Program **out)
+{
+    Source *um = is_user_model(model) ? find(KIND_MODEL, model) : nullptr, *uc = cost != kNone ? find(KIND_COST, cost) : nullptr;
+    if ((is_user_model(model) && !um) || (cost != kNone && !uc) || (!um && !uc)) return ISLS_ERR_ARG;
+    if (um && uc && (um->n != uc->n || um->m != uc->m)) return ISLS_ERR_ARG;
+    const int n = uc ? uc->n : um->n, m = uc ? uc->m : um->m;
+    const int mdlw = !um && model != kNone ? family_lds_words(n, m, model) : 0;
+    if (mdlw < 0) return ISLS_ERR_UNSUPPORTED;
+    Program &pg = g_prog[std::make_tuple(cost, dtype, model)];
+    *out = &pg;
+    if (pg.tried) return pg.ok ? ISLS_OK : ISLS_ERR_COMPILE;
+    pg.mdlw = mdlw;
+    pg.ntab = uc ? uc->ntab : 0;
+    pg.mtab = um ? um->ntab : 0;
+    Names nm(pg, dtype, n, m);
+    const std::string tmodel = ", " + std::to_string(um ? ISLS_MODEL_USER : model);   // the MODEL template argument
+    if (uc) {
+        nm.role(ROLE_EXP, "user_expand_kernel");
+        nm.role(ROLE_VAL, "user_cost_value_kernel");
+    } else {
+        nm.role(ROLE_LIN, "user_linearize_kernel");
+        nm.role(ROLE_LOOP, "dense_closed_loop_kernel", tmodel);
+        nm.role(ROLE_STEP, "user_step_kernel");
+        nm.role(ROLE_MC, "mc_closed_loop_kernel", tmodel);
+        nm.role(ROLE_MPC, "mpc_step_kernel", tmodel);
+    }
+    if (model != kNone) {
+        std::vector<std::pair<int, int>> ro;
+#define ISLS_URTC_VARIANTS_(NX_, NU_) if (n == NX_ && m == NU_) ro_variants<NX_, NU_>(ro);
+        ISLS_FOR_EACH_DIMS(ISLS_URTC_VARIANTS_)
+#undef ISLS_URTC_VARIANTS_
+        for (const auto &jo : ro)
+            pg.ro.push_back({jo.first, jo.second, nm.add("rollout_kernel", tmodel + ", " + std::to_string(jo.first) + ", " + std::to_string(jo.second))});
+        nm.role(ROLE_SMP_COST, "sample_cost_kernel", tmodel);
+        nm.role(ROLE_SMP_UPDATE, "sample_update_kernel", tmodel);
+        nm.role(ROLE_SMP_COST_FB, "sample_cost_fb_kernel", tmodel);
+        nm.role(ROLE_SMP_UPDATE_FB, "sample_update_fb_kernel", tmodel);
+    }
+    if (um && !uc && um->ntab > 0) nm.role(ROLE_STEP_TAB, "user_step_tab_kernel");           // a row of the table per state row
+    if (uc && uc->ncon > 0) nm.role(ROLE_CON_UPDATE, "user_constraint_update_kernel");
+    return compile_program(program_text(um, uc, uc ? "user_cost.hpp" : "user_model.hpp"), uc ? "user_cost.hip" : "user_model.hip", pg,
+                           (uc ? uc : um)->log);
 }
 
 bool dtype_ok(int dtype) { return dtype == ISLS_DTYPE_F64 || dtype == ISLS_DTYPE_F32; }
@@ -328,19 +326,10 @@ int grad_program(Kind kind, int id, int dtype, Program **out)
     Program &pg = g_grad[std::make_tuple((int)kind, id, dtype)];
     *out = &pg;
     if (pg.tried) return pg.ok ? ISLS_OK : ISLS_ERR_COMPILE;
-    const std::string T = dtype == ISLS_DTYPE_F64 ? "double" : "float", dims = std::to_string(src->n) + ", " + std::to_string(src->m);
     const bool cost = kind == KIND_COST;
-    pg.names = {std::string(cost ? "isls::user_cost_grad_kernel<" : "isls::user_model_grad_kernel<") + T + ", " + dims + ">"};
-    std::string text = cost ? "#include \"user_cost_ad.hpp\"\n" : "#include \"user_model_ad.hpp\"\n";
-    if (cost) {
-        text += wrap_source("isls_user_cost", "user_cost", src->source) + "#define ISLS_USER_COST_NPAR " + std::to_string(src->npar) + "\n";
-        if (src->ntab > 0) text += "#define ISLS_USER_COST_NTAB " + std::to_string(src->ntab) + "\n";
-        if (src->ncon > 0) text += "#define ISLS_USER_COST_NCON " + std::to_string(src->ncon) + "\n";
-    } else {
-        text += wrap_source("isls_user", "user_model", src->source) + "#define ISLS_USER_NPAR " + std::to_string(src->npar) + "\n";
-        if (src->ntab > 0) text += "#define ISLS_USER_MODEL_NTAB " + std::to_string(src->ntab) + "\n";
-    }
-    text += "#include \"user_grad.hpp\"\n";
+    Names nm(pg, dtype, src->n, src->m);
+    nm.role(ROLE_GRAD, cost ? "user_cost_grad_kernel" : "user_model_grad_kernel");
+    const std::string text = program_text(cost ? nullptr : src, cost ? src : nullptr, "user_grad.hpp");
     const int rc = compile_program(text, cost ? "user_cost_grad.hip" : "user_model_grad.hip", pg, src->log);
     if (rc != ISLS_OK)
         src->log += std::string("the gradient program instantiates the source with P = S = a dual number: what it does with `par` and "
@@ -463,13 +452,13 @@ int check_table(int cost, int N, const void *tab, int64_t tab_sb, int nvia)
     return ok ? ISLS_OK : ISLS_ERR_ARG;
 }
 
-int prepare(int model, int cost, int dtype, int n, int m, hipStream_t s, const std::vector<hipFunction_t> **fns, const Program **out)
+int prepare(int model, int cost, int dtype, int n, int m, hipStream_t s, Kernels *k)
 {
     std::lock_guard<std::mutex> lk(g_mu);
     const Source *src = cost != kNone ? find(KIND_COST, cost) : find(KIND_MODEL, model);
     if (!src || src->n != n || src->m != m) return ISLS_ERR_ARG;
     if (model == kNone) {
-        // expansion / value: every program of the cost holds them.  One that is on this device already serves (the pair the
+        // the cost's own kernels: every program of the cost holds them.  One that is on this device already serves (the pair the
         // engine loaded); the cost's own program is compiled only when there is no such pair
         int dev = 0;
         if (hipGetDevice(&dev) != hipSuccess) return ISLS_ERR_LAUNCH;
@@ -481,8 +470,8 @@ int prepare(int model, int cost, int dtype, int n, int m, hipStream_t s, const s
     Program *pg;
     const int rc = program(model, cost, dtype, &pg);
     if (rc != ISLS_OK) return rc;
-    if (out) *out = pg;
-    return load_program(*pg, fns, s);
+    k->pg = pg;
+    return load_program(*pg, &k->fns, s);
 }
 
 int grad_build(Kind kind, int id, int dtype)
@@ -504,16 +493,17 @@ int grad_prepare(Kind kind, int id, int dtype, int n, int m, hipStream_t s, hipF
     Program *pg;
     int rc = grad_program(kind, id, dtype, &pg);
     if (rc != ISLS_OK) return rc;
-    const std::vector<hipFunction_t> *fns;
-    if ((rc = load_program(*pg, &fns, s)) != ISLS_OK) return rc;
-    *fn = (*fns)[0];
+    Kernels k = {pg, nullptr};
+    if ((rc = load_program(*pg, &k.fns, s)) != ISLS_OK) return rc;
+    *fn = k.of(ROLE_GRAD);
     return ISLS_OK;
 }
 
-int launch(hipFunction_t f, int grid, size_t smem, hipStream_t s, void **args)
+int launch(hipFunction_t f, int grid, size_t smem, hipStream_t s, void **args, int lanes)
 {
+    if (!f) return ISLS_ERR_UNSUPPORTED;
     if (grid <= 0) return ISLS_OK;
-    return hipModuleLaunchKernel(f, grid, 1, 1, 64, 1, 1, (unsigned)smem, s, args, nullptr) == hipSuccess ? ISLS_OK : ISLS_ERR_LAUNCH;
+    return hipModuleLaunchKernel(f, grid, 1, 1, lanes, 1, 1, (unsigned)smem, s, args, nullptr) == hipSuccess ? ISLS_OK : ISLS_ERR_LAUNCH;
 }
 
 }  // namespace urtc
@@ -524,13 +514,13 @@ int launch_rollout_user(RoP<T> &p, const isls_rollout_args &a, hipStream_t s, bo
 {
     const bool ucost = is_user_cost(a.cost_model);
     if (ucost && (!a.cost_par || a.cost_par_sb < 0)) return ISLS_ERR_ARG;
-    const urtc::Program *pg;
-    const std::vector<hipFunction_t> *fns;
+    urtc::Kernels k;
     int rc = ucost ? urtc::check_table(a.cost_model, a.N, a.ztab, a.ztab_sb, a.nvia) : ISLS_OK;   // the table: ztab, ztab_sb, nvia
     if (rc != ISLS_OK) return rc;
     if ((rc = urtc::check_model_table(a.model, a.N, a.model_par, a.model_par_sb)) != ISLS_OK) return rc;   // a model's: behind model_par
-    rc = urtc::prepare(a.model, ucost ? a.cost_model : urtc::kNone, urtc::dtype_of<T>(), a.n, a.m, s, &fns, &pg);
+    rc = urtc::prepare(a.model, ucost ? a.cost_model : urtc::kNone, urtc::dtype_of<T>(), a.n, a.m, s, &k);
     if (rc != ISLS_OK) return rc;
+    const urtc::Program *pg = k.pg;
     if (ucost) p.cpar_sb = a.cost_par_sb;
     RoLaunch pl;
     rc = ISLS_ERR_UNSUPPORTED;
@@ -543,12 +533,8 @@ int launch_rollout_user(RoP<T> &p, const isls_rollout_args &a, hipStream_t s, bo
     ISLS_FOR_EACH_DIMS(ISLS_URTC_PLAN_)
 #undef ISLS_URTC_PLAN_
     if (rc != ISLS_OK) return rc;
-    for (size_t i = 0; i < pg->ro.size(); ++i)
-        if (pg->ro[i].first == pl.jm && pg->ro[i].second == pl.occ) {
-            void *args[] = {&p};
-            return urtc::launch((*fns)[pg->ro0 + i], pl.grid, pl.smem, s, args);
-        }
-    return ISLS_ERR_UNSUPPORTED;
+    void *args[] = {&p};
+    return urtc::launch(k.rollout(pl.jm, pl.occ), pl.grid, pl.smem, s, args);
 }
 template int launch_rollout_user<double>(RoP<double> &, const isls_rollout_args &, hipStream_t, bool);
 template int launch_rollout_user<float>(RoP<float> &, const isls_rollout_args &, hipStream_t, bool);

@@ -2,7 +2,8 @@
 // cache of their hiprtc programs and the module launcher.  A program is keyed by (model, cost, dtype): the model slot is a
 // built-in id, a user model or kNone, the cost slot a user cost or kNone.  (user model, kNone) is the model's own program
 // (user_model.hip launches its kernels), (kNone, cost) the cost's expansion and value (user_cost.hip), and a key with both slots
-// filled is the line search of that pair, which launch_rollout_user (rollout_kernel.hpp) serves for every key.
+// filled is the line search of that pair, which launch_rollout_user (rollout_kernel.hpp) serves for every key.  A caller names
+// the kernel it launches by its Role; where a kernel lies in a program only user_rtc.hip's Names knows.
 #pragma once
 
 #include <map>
@@ -13,23 +14,64 @@
 #include "rollout_kernel.hpp"
 
 namespace isls {
+
+// LDS words of the model of the built-in family (n, m, model) of families.def -- a dense LTI model's [A B], none for the others;
+// -1: no such family.  A count of words, the same in both precisions.  (Here and not in isls_common.hpp: every run-time
+// compiled program includes that header, and a code object's symbol order follows its text, skipped lines included.)
+inline int family_lds_words(int n, int m, int model)
+{
+#define ISLS_FAMILY_WORDS_(NX_, NU_, MODEL_)                                                                                         \
+    static_assert(Model<double, NX_, NU_, MODEL_>::LDS_WORDS == Model<float, NX_, NU_, MODEL_>::LDS_WORDS, "LDS words depend on T"); \
+    if (n == NX_ && m == NU_ && model == MODEL_) return Model<double, NX_, NU_, MODEL_>::LDS_WORDS;
+    ISLS_FOR_EACH_FAMILY(ISLS_FAMILY_WORDS_)
+#undef ISLS_FAMILY_WORDS_
+    return -1;
+}
+
 namespace urtc {
 
 enum Kind { KIND_MODEL = 0, KIND_COST = 1 };                 // ids count from ISLS_{MODEL,COST}_USER_BASE per kind: every lookup takes it
 constexpr int kNone = -1;                                    // the empty slot of a key
 
+// What a kernel of a program is for.  A program holds the roles its key calls for and no others.  The rollout variants are no
+// role: a program has one per (JM, OCC) the launch plan can pick (Program::ro).
+enum Role {
+    ROLE_LIN = 0, ROLE_LOOP, ROLE_STEP, ROLE_MC, ROLE_MPC,   // a user model's own program ...
+    ROLE_STEP_TAB,                                           // ... of a table model
+    ROLE_EXP, ROLE_VAL,                                      // every program of a cost ...
+    ROLE_CON_UPDATE,                                         // ... with constraints
+    ROLE_SMP_COST, ROLE_SMP_UPDATE, ROLE_SMP_COST_FB, ROLE_SMP_UPDATE_FB,   // every key with a model: the sampling round, open and closed loop
+    ROLE_GRAD,                                               // a gradient program
+    ROLE_COUNT
+};
+
 struct Program {                                             // one key: a model, a cost, or a (model, cost) pair in one dtype
+    struct Variant { int jm, occ, slot; };
     bool tried = false, ok = false;
     std::vector<char> code;
     std::vector<std::string> names, lowered;                 // name expressions and their mangled names
-    int ro0 = 0, mdlw = 0;                                   // index of the first rollout variant; LDS words of the model (plan_rollout)
+    int slot[ROLE_COUNT];                                    // role -> index in names / functions; -1: the program does not hold it
+    std::vector<Variant> ro;                                 // the rollout variants and theirs
+    int mdlw = 0;                                            // LDS words of the model (plan_rollout)
     int ntab = 0;                                            // words per step of the cost's table (its side records enter the plan too)
     int mtab = 0;                                            // ... and of the user model's table (likewise)
-    int stab = -1;                                           // index of user_step_tab_kernel (a table model's own program)
-    int con = -1;                                            // index of user_constraint_update_kernel (a cost with constraints)
-    int smp0 = -1;                                           // index of sample_cost_kernel; sample_update_kernel and the two *_fb_kernel behind it (a key with a model)
-    std::vector<std::pair<int, int>> ro;                     // (JM, OCC) of the rollout variants: names[ro0 + i]
     std::map<int, std::pair<hipModule_t, std::vector<hipFunction_t>>> dev;   // device -> module, functions
+    Program() { for (int &k : slot) k = -1; }
+};
+
+// A program on the current device (prepare): its kernels by role; NULL for one the program does not hold, which launch answers
+// with ISLS_ERR_UNSUPPORTED.
+struct Kernels {
+    const Program *pg = nullptr;
+    const std::vector<hipFunction_t> *fns = nullptr;
+    hipFunction_t at(int slot) const { return slot < 0 ? nullptr : (*fns)[slot]; }
+    hipFunction_t of(Role role) const { return at(pg->slot[role]); }
+    hipFunction_t rollout(int jm, int occ) const
+    {
+        for (const auto &v : pg->ro)
+            if (v.jm == jm && v.occ == occ) return at(v.slot);
+        return nullptr;
+    }
 };
 
 // isls_user_{model,cost}_create: register `source` (an id is assigned even when the compile fails) and compile its own program
@@ -54,12 +96,12 @@ int check_model_table(int model, int N, const void *par, int64_t par_sb, int row
 // cost with a table of W words needs tab != NULL, tab_sb == 0 or N * W, and nvia == W (nvia < 0: not given); the fields of a cost
 // without a table are ignored.  ISLS_ERR_ARG otherwise, and for an id nobody registered.
 int check_table(int cost, int N, const void *tab, int64_t tab_sb, int nvia);
-// The functions (index: pg.names) of the key's program for a launch of dims (n, m) on the current device: compiled and loaded on
-// first use -- never inside a capture of stream `s`.  (kNone, cost) asks for the expansion and the value, which every program
-// of the cost holds: one that is on this device already serves, the cost's own program is compiled only when there is none.
-int prepare(int model, int cost, int dtype, int n, int m, hipStream_t s, const std::vector<hipFunction_t> **fns,
-            const Program **pg = nullptr);
-int launch(hipFunction_t f, int grid, size_t smem, hipStream_t s, void **args);
+// The program of the key for a launch of dims (n, m) on the current device: compiled and loaded on first use -- never inside a
+// capture of stream `s`.  (kNone, cost) asks for the cost's own kernels, which every program of the cost holds: one that is on
+// this device already serves, the cost's own program is compiled only when there is none.
+int prepare(int model, int cost, int dtype, int n, int m, hipStream_t s, Kernels *k);
+// `grid` workgroups of `lanes` lanes; ISLS_ERR_UNSUPPORTED: no such kernel (f == NULL); grid <= 0: nothing to launch
+int launch(hipFunction_t f, int grid, size_t smem, hipStream_t s, void **args, int lanes = kWave);
 // The gradient program of a model or a cost (user_grad.hpp; one per source and dtype, apart from every key above): grad_build
 // compiles it on first request (no GPU needed; ISLS_ERR_COMPILE with the log and the sentence on the contract in the source's
 // log).  grad_prepare: the registration's n_par, the user's words per row n_row and the table's words per row n_tab (a cost with

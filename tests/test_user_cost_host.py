@@ -13,9 +13,10 @@ import pytest
 from isls import _capi as capi
 from isls import costs, models
 
+import al_reference as al
 import user_costs as uc
 import user_models as um
-from test_user_model_host import kernels_of, rollout_variants
+from test_user_model_host import COST_KERNELS, SAMPLING_KERNELS, assert_kernel_set, kernels_of, rollout_variants
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -32,7 +33,15 @@ def library_table():
 
 
 def pair(which):
-    """(cost, model, n, m, template id of the model in the pair's program, built-in family to compare with)"""
+    """(cost, model or None, n, m, template id of the model in the pair's program, built-in family to compare with)"""
+    alone = {"alone_42": (4, 2), "alone_62": (6, 2), "con_42": (4, 2), "con_63": (6, 3)}
+    if which in alone:
+        n, m = alone[which]
+        if which.startswith("con"):
+            return costs.Custom(n, m, al.PAR, al.full_source(n, m, 0, 3), constraints=3), None, n, m, None, None
+        return costs.Custom(n, m, uc.COUPLED_PAR, uc.coupled_source(n, m)), None, n, m, None, None
+    if which == "coupled_car":
+        return costs.Custom(4, 2, uc.COUPLED_PAR, uc.coupled_source(4, 2)), models.Custom(4, 2, [0.1], um.CAR), 4, 2, 99, capi.MODEL_CAR
     if which == "phuber_tassa":
         c = costs.Custom(4, 2, uc.phuber_params(PH["cu"], PH["cx"], PH["cf"]), uc.phuber_source(4, 2, PH["px"], PH["pf"]))
         return c, models.TassaCar(0.03), 4, 2, capi.MODEL_TASSA, capi.MODEL_TASSA
@@ -42,7 +51,7 @@ def pair(which):
             capi.MODEL_LTI)
 
 
-@pytest.mark.parametrize("which", ["phuber_tassa", "via_arm", "coupled_quad"])
+@pytest.mark.parametrize("which", ["phuber_tassa", "via_arm", "coupled_quad", "coupled_car", "alone_42", "alone_62", "con_42", "con_63"])
 @pytest.mark.parametrize("dtype, T", [(np.float64, "d"), (np.float32, "f")])
 def test_code_object_holds_every_kernel(library_table, which, dtype, T):
     cost, mdl, n, m, tid, builtin = pair(which)
@@ -53,12 +62,16 @@ def test_code_object_holds_every_kernel(library_table, which, dtype, T):
     exp = ks[f"_ZN4isls18user_expand_kernelI{T}Li{n}ELi{m}EEEvNS_8UserExpPIT_EE"]
     assert any(k.startswith(f"_ZN4isls22user_cost_value_kernelI{T}Li{n}ELi{m}E") for k in ks)
     mine = rollout_variants(ks, T, n, m, tid)
-    ref = rollout_variants(library_table, T, n, m, builtin)
-    assert ref and set(mine) == set(ref), (sorted(mine), sorted(ref))
+    ref = rollout_variants(library_table, T, n, m, builtin) if mdl is not None else {}
+    assert (ref or mdl is None) and set(mine) == set(ref), (sorted(mine), sorted(ref))
     for jo, k in mine.items():
         r = library_table[ref[jo]]
         assert ks[k][".private_segment_fixed_size"] <= r["scratch"], (k, ks[k][".private_segment_fixed_size"], r)
     assert exp[".private_segment_fixed_size"] == 0 and exp.get(".vgpr_spill_count", 0) == 0, exp
+    # and nothing else: the cost's kernels, its multiplier update with constraints only, the sampling round and the roll-outs
+    # with a model only, none of a model's own kernels
+    con = {"user_constraint_update_kernel"} if which.startswith("con") else set()
+    assert_kernel_set(ks, T, n, m, COST_KERNELS | con | (SAMPLING_KERNELS if mdl is not None else set()), len(ref))
 
 
 @pytest.mark.parametrize("n, m", [(4, 2), (6, 2), (9, 3)])

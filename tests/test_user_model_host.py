@@ -14,6 +14,7 @@ import pytest
 from isls import _capi as capi
 from isls import models
 
+import table_models as tm
 import user_models as um
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,6 +24,12 @@ import scan_kernels  # noqa: E402
 sys.path.pop(0)
 
 RO = re.compile(r"^_ZN4isls14rollout_kernelI([df])Li(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)EEEvNS_3RoPIT_EE$")
+KERNEL = re.compile(r"^_ZN4isls\d+([a-z_]+_kernel)I([df])Li(\d+)ELi(\d+)E")
+
+# the kernels of a run-time compiled program by the kind of its key, the roll-out variants apart
+MODEL_KERNELS = {"user_linearize_kernel", "dense_closed_loop_kernel", "user_step_kernel", "mc_closed_loop_kernel", "mpc_step_kernel"}
+COST_KERNELS = {"user_expand_kernel", "user_cost_value_kernel"}
+SAMPLING_KERNELS = {"sample_cost_kernel", "sample_update_kernel", "sample_cost_fb_kernel", "sample_update_fb_kernel"}
 
 
 @pytest.fixture(scope="module")
@@ -40,6 +47,16 @@ def quad():
     return models.Custom(6, 2, um.QUAD_PAR, um.QUAD)
 
 
+@pytest.fixture(scope="module")
+def car_tab():
+    return models.Custom(4, 2, [0.0], tm.generic_source(4, 2, 16, True), table=np.tile(tm.generic_consts(16), (5, 1)))
+
+
+@pytest.fixture(scope="module")
+def lti_tab():
+    return models.Custom(6, 3, [0.0], tm.generic_source(6, 3, 16, True), table=np.tile(tm.generic_consts(16), (5, 1)))
+
+
 def kernels_of(code):
     md = scan_kernels._metadata(code)
     return {k[".name"]: k for k in md["amdhsa.kernels"]}
@@ -55,7 +72,17 @@ def rollout_variants(names, prec, n, m, model):
     return out
 
 
-@pytest.mark.parametrize("which, n, m, builtin", [("car", 4, 2, capi.MODEL_CAR), ("quad", 6, 2, capi.MODEL_LTI)])
+def assert_kernel_set(ks, prec, n, m, expected, rollouts):
+    """The code object holds exactly `expected` (one instantiation each) and `rollouts` roll-out variants, all of (prec, n, m)."""
+    found = [KERNEL.match(k) for k in ks]
+    assert all(found), sorted(ks)
+    assert {(g.group(2), int(g.group(3)), int(g.group(4))) for g in found} == {(prec, n, m)}, sorted(ks)
+    base = sorted(g.group(1) for g in found)
+    assert base == sorted(list(expected) + ["rollout_kernel"] * rollouts), (base, sorted(expected), rollouts)
+
+
+@pytest.mark.parametrize("which, n, m, builtin", [("car", 4, 2, capi.MODEL_CAR), ("quad", 6, 2, capi.MODEL_LTI),
+                                                  ("car_tab", 4, 2, capi.MODEL_CAR), ("lti_tab", 6, 3, capi.MODEL_LTI)])
 @pytest.mark.parametrize("dtype, prec", [(np.float64, "d"), (np.float32, "f")])
 def test_code_object_holds_every_kernel(request, library_table, which, n, m, builtin, dtype, prec):
     mdl = request.getfixturevalue(which)
@@ -76,6 +103,9 @@ def test_code_object_holds_every_kernel(request, library_table, which, n, m, bui
         assert ks[k][".private_segment_fixed_size"] <= r["scratch"], (k, ks[k][".private_segment_fixed_size"], r)
     lin = ks[f"_ZN4isls21user_linearize_kernelI{T}Li{n}ELi{m}EEEvNS_8UserLinPIT_EE"]
     assert lin[".private_segment_fixed_size"] == 0 and lin.get(".vgpr_spill_count", 0) == 0
+    # and nothing else: a model's own kernels, the sampling round, the table step of a table model only, nothing of a cost
+    tab = {"user_step_tab_kernel"} if which.endswith("_tab") else set()
+    assert_kernel_set(ks, prec, n, m, MODEL_KERNELS | SAMPLING_KERNELS | tab, len(ref))
 
 
 def test_arm_compiles_within_the_builtin_scratch(library_table):
