@@ -107,6 +107,28 @@ ISLS_API int isls_user_cost_create_con(const char *source, int32_t n, int32_t m,
     return urtc::create(urtc::KIND_COST, source, n, m, n_par, n_tab, id, n_con);
 }
 
+ISLS_API int isls_user_cost_create_field(const char *source, int32_t n, int32_t m, int32_t n_par, int32_t n_tab, int32_t n_con,
+                                         int32_t n_field, int32_t nx, int32_t ny, int32_t *id)
+{
+    if (n_field < 1) return ISLS_ERR_UNSUPPORTED;             // (0 is the other creates')
+    return urtc::create(urtc::KIND_COST, source, n, m, n_par, n_tab, id, n_con, n_field, nx, ny);
+}
+
+ISLS_API int isls_user_cost_set_field(int32_t id, const void *values, int32_t dtype_of_values, const double origin[2],
+                                      const double spacing[2], void *stream)
+{
+    return urtc::set_field(id, values, dtype_of_values, origin, spacing, (hipStream_t)stream);
+}
+
+ISLS_API int isls_user_cost_field_dims(int32_t id, int32_t *n_field, int32_t *nx, int32_t *ny)
+{
+    return urtc::field_dims(id, n_field, nx, ny);
+}
+
+ISLS_API int isls_user_cost_field_ptr(int32_t id, int32_t dtype, void **ptr) { return urtc::field_ptr(id, dtype, ptr); }
+
+ISLS_API int isls_user_cost_release_field(int32_t id) { return urtc::release_field(id); }
+
 ISLS_API int isls_user_cost_n_tab(int32_t id) { return urtc::n_tab(id); }
 
 ISLS_API int isls_user_cost_n_con(int32_t id) { return urtc::n_con(id); }

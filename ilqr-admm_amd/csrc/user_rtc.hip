@@ -22,6 +22,7 @@
 #include <tuple>
 
 #include "user_rtc.hpp"
+#include "user_field.hpp"                                    // FieldDesc: the descriptor a module of a field cost holds
 
 #ifndef ISLS_ROCM_PATH
 #define ISLS_ROCM_PATH "/opt/rocm"                           // the Makefile passes the ROCm of its hipcc
@@ -178,8 +179,10 @@ int compile_program(const std::string &src, const char *file, Program &pg, std::
     return ok ? ISLS_OK : ISLS_ERR_COMPILE;
 }
 
+int write_field(const Program &pg, int dev, hipModule_t mod);   // (below, with the registry)
+
 // the program's functions (in the order of pg.names) on the current device, loaded on first use -- never inside a stream capture
-// (capture_check: the stream to test, or nullptr)
+// (capture_check: the stream to test, or nullptr); a module of a field cost gets the field's descriptor where the field is set
 int load_program(Program &pg, const std::vector<hipFunction_t> **out, hipStream_t capture_check)
 {
     if (!pg.ok) return ISLS_ERR_COMPILE;
@@ -199,6 +202,10 @@ int load_program(Program &pg, const std::vector<hipFunction_t> **out, hipStream_
                 hipModuleUnload(mod);
                 return ISLS_ERR_LAUNCH;
             }
+        if (write_field(pg, dev, mod) != ISLS_OK) {
+            hipModuleUnload(mod);
+            return ISLS_ERR_LAUNCH;
+        }
         it = pg.dev.emplace(dev, std::make_pair(mod, std::move(fns))).first;
     }
     if (out) *out = &it->second.second;
@@ -210,6 +217,15 @@ struct Source {
     std::string source;
     int n, m, npar, ntab;                                    // ntab: words per step of the source's table (0: none)
     int ncon = 0;                                            // path constraints of a cost (ntab then counts their multipliers and mu)
+    // the field of a cost (user_field.hpp): C channels of nx x ny samples; per device the two sample buffers the registration
+    // owns and the origin and 1 / spacing that stand in the descriptors there (set: isls_user_cost_set_field has been there)
+    struct FieldDev {
+        void *v64 = nullptr, *v32 = nullptr;
+        double org[2] = {0, 0}, inv[2] = {0, 0};
+        bool set = false;
+    };
+    int nfield = 0, fnx = 0, fny = 0;
+    std::map<int, FieldDev> fdev;
     std::string log;
 };
 
@@ -221,6 +237,47 @@ Source *find(Kind kind, int id)
 {
     const int k = id - (kind == KIND_MODEL ? ISLS_MODEL_USER_BASE : ISLS_COST_USER_BASE);
     return (k >= 0 && k < (int)g_src[kind].size()) ? g_src[kind][k].get() : nullptr;
+}
+
+// ---- the field of a cost: its descriptor in the modules, its samples in the registration's buffers ----------------------------
+template <typename T>
+int write_field_as(const Source &src, const Source::FieldDev &fd, hipModule_t mod)
+{
+    hipDeviceptr_t sym = nullptr;
+    size_t bytes = 0;
+    const hipError_t e = hipModuleGetGlobal(&sym, &bytes, mod, "isls_user_cost_field");
+    if (e == hipErrorNotFound) return ISLS_OK;               // a source that never reads its field: the compiler kept no descriptor
+    if (e != hipSuccess || bytes != sizeof(FieldDesc<T>)) return ISLS_ERR_LAUNCH;
+    FieldDesc<T> d;
+    d.set((const T *)(sizeof(T) == 8 ? fd.v64 : fd.v32), src.fnx, src.fny, fd.org, fd.inv);
+    return hipMemcpyHtoD(sym, &d, sizeof(d)) == hipSuccess ? ISLS_OK : ISLS_ERR_LAUNCH;
+}
+
+// the descriptor of pg's module `mod` on device `dev`: written where the program is a field cost's and the field is set there
+int write_field(const Program &pg, int dev, hipModule_t mod)
+{
+    const Source *src = pg.field_cost != kNone ? find(KIND_COST, pg.field_cost) : nullptr;
+    if (!src || src->nfield == 0) return ISLS_OK;
+    const auto it = src->fdev.find(dev);
+    if (it == src->fdev.end() || !it->second.set) return ISLS_OK;   // set_field writes it when it comes
+    return pg.dtype == ISLS_DTYPE_F64 ? write_field_as<double>(*src, it->second, mod) : write_field_as<float>(*src, it->second, mod);
+}
+
+// ISLS_ERR_ARG for a launch of a field cost on a device its field was never set on, before anything is compiled, loaded or launched
+int check_field(const Source *uc)
+{
+    if (!uc || uc->nfield == 0) return ISLS_OK;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return ISLS_ERR_LAUNCH;
+    const auto it = uc->fdev.find(dev);
+    return it != uc->fdev.end() && it->second.set ? ISLS_OK : ISLS_ERR_ARG;
+}
+
+template <typename From, typename To>
+__global__ __launch_bounds__(256) void field_convert_kernel(const From *src, To *dst, int n)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) dst[i] = (To)src[i];
 }
 
 // the (JM, OCC) variants the launch plan of these dimensions can pick
@@ -238,9 +295,15 @@ void ro_variants(std::vector<std::pair<int, int>> &v)
 
 // The text of a program: the dual-number header (the cost's where there is a cost), the user model and the user cost (either may
 // be absent), each in its namespace with the defines of its registration behind it, and the device side `device_hpp` last.
-std::string program_text(const Source *um, const Source *uc, const char *device_hpp)
+std::string program_text(const Source *um, const Source *uc, const char *device_hpp, int dtype)
 {
-    std::string src = uc ? "#include \"user_cost_ad.hpp\"\n" : "#include \"user_model_ad.hpp\"\n";
+    std::string src;
+    // a cost with a field: isls::field (user_field.hpp) ahead of the source that calls it; the text of every other program is
+    // what it was, line for line
+    if (uc && uc->nfield > 0)
+        src = "#define ISLS_USER_COST_NFIELD " + std::to_string(uc->nfield) + "\n#define ISLS_USER_COST_FIELD_T " +
+              (dtype == ISLS_DTYPE_F64 ? "double" : "float") + "\n#include \"user_field.hpp\"\n";
+    src += uc ? "#include \"user_cost_ad.hpp\"\n" : "#include \"user_model_ad.hpp\"\n";
     if (um) src += wrap_source("isls_user", "user_model", um->source) + "#define ISLS_USER_NPAR " + std::to_string(um->npar) + "\n";
     if (um && um->ntab > 0) src += "#define ISLS_USER_MODEL_NTAB " + std::to_string(um->ntab) + "\n";
     if (uc) src += wrap_source("isls_user_cost", "user_cost", uc->source) + "#define ISLS_USER_COST_NPAR " + std::to_string(uc->npar) + "\n";
@@ -264,6 +327,14 @@ struct Names {
     void role(Role r, const char *k, const std::string &more = std::string()) { pg.slot[r] = add(k, more); }
 };
 
+// a failed compile of a cost that calls isls::field and was registered without one: the sentence that says so, behind the compiler's
+void no_field_sentence(Source &uc)
+{
+    if (uc.nfield == 0 && uc.source.find("isls::field") != std::string::npos)
+        uc.log += "the source calls isls::field, but the cost was registered without a field: isls::field exists only in the programs "
+                  "of a cost created with one (isls_user_cost_create_field; costs.Custom(field=...)).\n";
+}
+
 // The program of (model, cost, dtype), compiled on first use: a user model alone holds its own kernels, every key with a cost the
 // cost's, every key with a model the rollout variants of its dimensions and the sampling round.  The compiler's messages go to
 // the cost's log, to the model's when there is no cost.  ISLS_ERR_ARG: no such source, or a model and a cost of different
@@ -282,6 +353,8 @@ int program(int model, int cost, int dtype, Program **out)
     pg.mdlw = mdlw;
     pg.ntab = uc ? uc->ntab : 0;
     pg.mtab = um ? um->ntab : 0;
+    pg.field_cost = uc && uc->nfield > 0 ? cost : kNone;
+    pg.dtype = dtype;
     Names nm(pg, dtype, n, m);
     const std::string tmodel = ", " + std::to_string(um ? ISLS_MODEL_USER : model);   // the MODEL template argument
     if (uc) {
@@ -308,8 +381,10 @@ int program(int model, int cost, int dtype, Program **out)
     }
     if (um && !uc && um->ntab > 0) nm.role(ROLE_STEP_TAB, "user_step_tab_kernel");           // a row of the table per state row
     if (uc && uc->ncon > 0) nm.role(ROLE_CON_UPDATE, "user_constraint_update_kernel");
-    return compile_program(program_text(um, uc, uc ? "user_cost.hpp" : "user_model.hpp"), uc ? "user_cost.hip" : "user_model.hip", pg,
-                           (uc ? uc : um)->log);
+    const int rc = compile_program(program_text(um, uc, uc ? "user_cost.hpp" : "user_model.hpp", dtype), uc ? "user_cost.hip" : "user_model.hip",
+                                   pg, (uc ? uc : um)->log);
+    if (rc != ISLS_OK && uc) no_field_sentence(*uc);
+    return rc;
 }
 
 bool dtype_ok(int dtype) { return dtype == ISLS_DTYPE_F64 || dtype == ISLS_DTYPE_F32; }
@@ -329,8 +404,11 @@ int grad_program(Kind kind, int id, int dtype, Program **out)
     const bool cost = kind == KIND_COST;
     Names nm(pg, dtype, src->n, src->m);
     nm.role(ROLE_GRAD, cost ? "user_cost_grad_kernel" : "user_model_grad_kernel");
-    const std::string text = program_text(cost ? nullptr : src, cost ? src : nullptr, "user_grad.hpp");
+    pg.field_cost = cost && src->nfield > 0 ? id : kNone;
+    pg.dtype = dtype;
+    const std::string text = program_text(cost ? nullptr : src, cost ? src : nullptr, "user_grad.hpp", dtype);
     const int rc = compile_program(text, cost ? "user_cost_grad.hip" : "user_model_grad.hip", pg, src->log);
+    if (rc != ISLS_OK && cost) no_field_sentence(*src);
     if (rc != ISLS_OK)
         src->log += std::string("the gradient program instantiates the source with P = S = a dual number: what it does with `par` and "
                                 "`row` must keep to the S contract of user_model_ad.hpp (arithmetic, comparisons and the listed "
@@ -342,14 +420,18 @@ int grad_program(Kind kind, int id, int dtype, Program **out)
 }  // namespace
 
 // ---- what user_model.hip and user_cost.hip build their entry points and launches from ------------------------------------------
-int create(Kind kind, const char *source, int n, int m, int n_par, int n_tab, int32_t *id, int n_con)
+int create(Kind kind, const char *source, int n, int m, int n_par, int n_tab, int32_t *id, int n_con, int n_field, int nx, int ny)
 {
     if (!source || !id) return ISLS_ERR_ARG;
     if (!dims_supported(n, m) || n_par < 0 || n_par > ISLS_USER_MAX_PAR) return ISLS_ERR_UNSUPPORTED;
     if (n_tab < 0 || n_tab > ISLS_USER_MAX_TAB) return ISLS_ERR_UNSUPPORTED;
     // constraints: a cost's, and the row then holds a multiplier each and mu behind the user's words
     if (n_con < 0 || (n_con > 0 && (kind != KIND_COST || n_tab < n_con + 1))) return ISLS_ERR_UNSUPPORTED;
+    if (n_field != 0 && (kind != KIND_COST || n_field < 1 || n_field > ISLS_USER_MAX_FIELD || nx < 4 || ny < 4 ||
+                         (int64_t)n_field * nx * ny > ISLS_USER_MAX_FIELD_WORDS))
+        return ISLS_ERR_UNSUPPORTED;
     auto src = std::make_unique<Source>();
+    src->nfield = n_field; src->fnx = n_field ? nx : 0; src->fny = n_field ? ny : 0;
     src->source = source; src->n = n; src->m = m; src->npar = n_par; src->ntab = n_tab; src->ncon = n_con;
     if (refused_source(src->source)) return ISLS_ERR_ARG;     // plain arithmetic: no hand-written ISA through this door
     std::lock_guard<std::mutex> lk(g_mu);
@@ -457,6 +539,7 @@ int prepare(int model, int cost, int dtype, int n, int m, hipStream_t s, Kernels
     std::lock_guard<std::mutex> lk(g_mu);
     const Source *src = cost != kNone ? find(KIND_COST, cost) : find(KIND_MODEL, model);
     if (!src || src->n != n || src->m != m) return ISLS_ERR_ARG;
+    if (cost != kNone && check_field(src) != ISLS_OK) return ISLS_ERR_ARG;   // a field cost whose field was never set here
     if (model == kNone) {
         // the cost's own kernels: every program of the cost holds them.  One that is on this device already serves (the pair the
         // engine loaded); the cost's own program is compiled only when there is no such pair
@@ -490,6 +573,7 @@ int grad_prepare(Kind kind, int id, int dtype, int n, int m, hipStream_t s, hipF
     *n_par = src->npar; *n_tab = src->ntab;
     *n_row = src->ncon > 0 ? src->ntab - src->ncon - 1 : src->ntab;
     if (!fn) return ISLS_OK;
+    if (kind == KIND_COST && check_field(src) != ISLS_OK) return ISLS_ERR_ARG;
     Program *pg;
     int rc = grad_program(kind, id, dtype, &pg);
     if (rc != ISLS_OK) return rc;
@@ -497,6 +581,106 @@ int grad_prepare(Kind kind, int id, int dtype, int n, int m, hipStream_t s, hipF
     if ((rc = load_program(*pg, &k.fns, s)) != ISLS_OK) return rc;
     *fn = k.of(ROLE_GRAD);
     return ISLS_OK;
+}
+
+int field_dims(int cost, int *C, int *nx, int *ny)
+{
+    std::lock_guard<std::mutex> lk(g_mu);
+    const Source *src = find(KIND_COST, cost);
+    if (!src || !C || !nx || !ny) return ISLS_ERR_ARG;
+    *C = src->nfield; *nx = src->fnx; *ny = src->fny;
+    return ISLS_OK;
+}
+
+int field_ptr(int cost, int dtype, void **ptr)
+{
+    if (!dtype_ok(dtype) || !ptr) return ISLS_ERR_ARG;
+    std::lock_guard<std::mutex> lk(g_mu);
+    const Source *src = find(KIND_COST, cost);
+    if (!src || src->nfield == 0) return ISLS_ERR_ARG;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return ISLS_ERR_LAUNCH;
+    const auto it = src->fdev.find(dev);
+    *ptr = it == src->fdev.end() || !it->second.set ? nullptr : (dtype == ISLS_DTYPE_F64 ? it->second.v64 : it->second.v32);
+    return ISLS_OK;
+}
+
+int set_field(int cost, const void *values, int dtype, const double *origin, const double *spacing, hipStream_t s)
+{
+    if (!dtype_ok(dtype) || !values || !origin || !spacing) return ISLS_ERR_ARG;
+    for (int a = 0; a < 2; ++a)                              // (a NaN fails every comparison)
+        if (!(spacing[a] > 0.0) || !(spacing[a] <= 1.79e308) || !(origin[a] >= -1.79e308 && origin[a] <= 1.79e308)) return ISLS_ERR_ARG;
+    std::lock_guard<std::mutex> lk(g_mu);
+    Source *src = find(KIND_COST, cost);
+    if (!src || src->nfield == 0) return ISLS_ERR_ARG;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return ISLS_ERR_LAUNCH;
+    const int n = src->nfield * src->fnx * src->fny;          // <= 2^24
+    Source::FieldDev &fd = src->fdev[dev];
+    const double inv[2] = {1.0 / spacing[0], 1.0 / spacing[1]};
+    const bool same_grid = fd.set && fd.org[0] == origin[0] && fd.org[1] == origin[1] && fd.inv[0] == inv[0] && fd.inv[1] == inv[1];
+    if (!same_grid) {
+        // the first field on this device, or another grid: buffers are allocated and descriptors written below, neither of which
+        // a stream capture can hold -- refused before anything is enqueued, so samples and descriptors never part ways
+        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(s, &st) != hipSuccess || st != hipStreamCaptureStatusNone) return ISLS_ERR_LAUNCH;
+    }
+    if (!fd.v64) {
+        if (hipMalloc(&fd.v64, (size_t)n * sizeof(double)) != hipSuccess) { fd.v64 = nullptr; return ISLS_ERR_LAUNCH; }
+        if (hipMalloc(&fd.v32, (size_t)n * sizeof(float)) != hipSuccess) {
+            (void)hipFree(fd.v64);
+            fd.v64 = fd.v32 = nullptr;
+            return ISLS_ERR_LAUNCH;
+        }
+    }
+    // the samples: the copy of the caller's precision as it is, the other by the conversion kernel, both in place on `s`
+    const int grid = (n + 255) / 256;
+    if (dtype == ISLS_DTYPE_F64) {
+        if (hipMemcpyAsync(fd.v64, values, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess) return ISLS_ERR_LAUNCH;
+        hipLaunchKernelGGL((field_convert_kernel<double, float>), dim3(grid), dim3(256), 0, s, (const double *)fd.v64, (float *)fd.v32, n);
+    } else {
+        if (hipMemcpyAsync(fd.v32, values, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) return ISLS_ERR_LAUNCH;
+        hipLaunchKernelGGL((field_convert_kernel<float, double>), dim3(grid), dim3(256), 0, s, (const float *)fd.v32, (double *)fd.v64, n);
+    }
+    if (hipGetLastError() != hipSuccess) return ISLS_ERR_LAUNCH;
+    if (same_grid) return ISLS_OK;
+    // the first field on this device, or another grid: into the descriptor of every module of the cost that is here already.  What
+    // is in flight on `s` still reads the old one, so it ends first (not inside a capture of `s`).
+    if (fd.set && hipStreamSynchronize(s) != hipSuccess) return ISLS_ERR_LAUNCH;
+    fd.org[0] = origin[0]; fd.org[1] = origin[1]; fd.inv[0] = inv[0]; fd.inv[1] = inv[1];
+    fd.set = true;
+    auto write = [&](Program &pg) {
+        const auto it = pg.dev.find(dev);
+        return pg.field_cost != cost || it == pg.dev.end() ? (int)ISLS_OK : write_field(pg, dev, it->second.first);
+    };
+    int rc = ISLS_OK;
+    for (auto &kv : g_prog)
+        if (rc == ISLS_OK) rc = write(kv.second);
+    for (auto &kv : g_grad)
+        if (rc == ISLS_OK) rc = write(kv.second);
+    // a descriptor that could not be written leaves the modules on two grids: the field counts as not set here (every launch is
+    // ISLS_ERR_ARG) until a set_field goes through, which writes all of them again
+    if (rc != ISLS_OK) fd.set = false;
+    return rc;
+}
+
+int release_field(int cost)
+{
+    std::lock_guard<std::mutex> lk(g_mu);
+    Source *src = find(KIND_COST, cost);
+    if (!src || src->nfield == 0) return ISLS_ERR_ARG;
+    int cur = 0;
+    if (src->fdev.empty()) return ISLS_OK;
+    if (hipGetDevice(&cur) != hipSuccess) return ISLS_ERR_LAUNCH;
+    int rc = ISLS_OK;
+    for (auto &kv : src->fdev) {                             // hipFree waits for what still reads the buffers
+        if (!kv.second.v64) continue;
+        if (hipSetDevice(kv.first) != hipSuccess || hipFree(kv.second.v64) != hipSuccess || hipFree(kv.second.v32) != hipSuccess)
+            rc = ISLS_ERR_LAUNCH;
+    }
+    (void)hipSetDevice(cur);
+    src->fdev.clear();                                       // not set anywhere: a launch is ISLS_ERR_ARG until the next set_field
+    return rc;
 }
 
 int launch(hipFunction_t f, int grid, size_t smem, hipStream_t s, void **args, int lanes)

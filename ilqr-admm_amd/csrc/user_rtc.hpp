@@ -55,6 +55,7 @@ struct Program {                                             // one key: a model
     int mdlw = 0;                                            // LDS words of the model (plan_rollout)
     int ntab = 0;                                            // words per step of the cost's table (its side records enter the plan too)
     int mtab = 0;                                            // ... and of the user model's table (likewise)
+    int field_cost = kNone, dtype = 0;                       // the cost whose field descriptor the program's module holds (kNone: none), in dtype
     std::map<int, std::pair<hipModule_t, std::vector<hipFunction_t>>> dev;   // device -> module, functions
     Program() { for (int &k : slot) k = -1; }
 };
@@ -77,7 +78,23 @@ struct Kernels {
 // isls_user_{model,cost}_create: register `source` (an id is assigned even when the compile fails) and compile its own program
 // (the model's, or the cost's expansion and value) for fp64; n_tab: words per step of the source's table (0: none); n_con: path
 // constraints of a cost, whose n_tab counts n_con multipliers and mu behind the user's words (ISLS_ERR_UNSUPPORTED: n_tab < n_con + 1)
-int create(Kind kind, const char *source, int n, int m, int n_par, int n_tab, int32_t *id, int n_con = 0);
+// n_field = C > 0: a cost that reads a 2-D field of C channels of nx x ny samples (user_field.hpp); ISLS_ERR_UNSUPPORTED: C outside
+// [1, 4], nx or ny < 4, C nx ny > 2^24, a model
+int create(Kind kind, const char *source, int n, int m, int n_par, int n_tab, int32_t *id, int n_con = 0, int n_field = 0, int nx = 0,
+           int ny = 0);
+// The field of a cost registered with one.  set_field: `values` [C, nx, ny] on the current device, of `dtype`, into the two sample
+// buffers (fp64 and fp32) the registration owns on that device -- allocated at the first call there, overwritten in place on stream
+// `s` by every later one -- and origin, 1 / spacing into the descriptor of every module of the cost on the device (only when they
+// differ from what stands: a same-grid set_field touches no descriptor).  Modules loaded later get the descriptor as they load.
+// ISLS_ERR_ARG: no such cost, a cost without a field, values / origin / spacing NULL, a spacing <= 0 or not finite.
+// field_dims: C, nx, ny (0, 0, 0: a cost without a field).  field_ptr: the sample buffer of `dtype` on the current device (NULL: not set).
+int set_field(int cost, const void *values, int dtype, const double *origin, const double *spacing, hipStream_t s);
+int field_dims(int cost, int *C, int *nx, int *ny);
+int field_ptr(int cost, int dtype, void **ptr);
+// Frees the sample buffers of the cost's field on every device (the registration itself, its programs and modules stay): the
+// field is then set nowhere, and the next set_field allocates again and rewrites the descriptors.  ISLS_ERR_ARG: no such cost, a
+// cost without a field.
+int release_field(int cost);
 // isls_user_*_log / _code / _load: the compiler's messages for a source so far; the code object of a key, compiled on first use;
 // the same loaded onto the current device
 int64_t copy_log(Kind kind, int id, char *buf, int64_t len);

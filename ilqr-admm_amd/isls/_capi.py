@@ -25,6 +25,7 @@ SOLVE_CHOL, SOLVE_INV = 0, 1
 MODEL_LTI, MODEL_ARM3R, MODEL_CAR, MODEL_DI, MODEL_TASSA = 0, 1, 2, 3, 4
 MODEL_USER_BASE, USER_MAX_PAR = 1024, 16      # ids of user models (isls_user_model_create), parameters per model at most
 USER_MAX_TAB = 16                              # words per step of a user cost's / model's table (isls_user_*_create_tab), at most
+USER_MAX_FIELD, USER_MAX_FIELD_WORDS = 4, 1 << 24   # channels and samples of a user cost's 2-D field (isls_user_cost_create_field), at most
 DTYPE_F64, DTYPE_F32 = 0, 1
 COST_VIA, COST_PHUBER = 0, 1
 COST_USER_BASE = 1024                          # ids of user costs (isls_user_cost_create)
@@ -301,7 +302,9 @@ EXPORTED = [f"isls_{k}_{s}" for s in ("f64", "f32") for k in
             "isls_user_model_create", "isls_user_model_log", "isls_user_model_code", "isls_user_model_load",
             "isls_user_cost_create", "isls_user_cost_log", "isls_user_cost_code", "isls_user_cost_load",
             "isls_user_cost_create_tab", "isls_user_cost_n_tab", "isls_user_model_create_tab", "isls_user_model_n_tab",
-            "isls_user_cost_create_con", "isls_user_cost_n_con", "isls_user_model_grad_build", "isls_user_cost_grad_build"]
+            "isls_user_cost_create_con", "isls_user_cost_n_con", "isls_user_model_grad_build", "isls_user_cost_grad_build",
+            "isls_user_cost_create_field", "isls_user_cost_set_field", "isls_user_cost_field_dims", "isls_user_cost_field_ptr",
+            "isls_user_cost_release_field"]
 
 
 SET_BOX, SET_SOC_UNIT, SET_SQUARE, SET_LINEAR, SET_QUADRATIC, SET_SHELL, SET_MULTILINEAR = 1, 2, 3, 4, 5, 6, 7
@@ -353,6 +356,11 @@ def load_hip_library(path=None):
         getattr(lib, f"isls_user_{noun}_log").restype = C.c_int64
     lib.isls_user_cost_create_con.argtypes = src + [i32, i32, C.POINTER(i32)]   # (.., n_tab, n_con, &id)
     lib.isls_user_cost_n_con.argtypes = [i32]
+    lib.isls_user_cost_create_field.argtypes = src + [i32] * 5 + [C.POINTER(i32)]   # (.., n_tab, n_con, n_field, nx, ny, &id)
+    lib.isls_user_cost_set_field.argtypes = [i32, C.c_void_p, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]
+    lib.isls_user_cost_field_dims.argtypes = [i32] + [C.POINTER(i32)] * 3
+    lib.isls_user_cost_field_ptr.argtypes = [i32, i32, C.POINTER(C.c_void_p)]
+    lib.isls_user_cost_release_field.argtypes = [i32]
     lib.isls_user_model_grad_build.argtypes = lib.isls_user_cost_grad_build.argtypes = [i32, i32]
     return lib
 
@@ -427,19 +435,24 @@ class _UserKind:
         self._fn("log")(C.c_int32(uid), buf, len(buf))
         return buf.value.decode(errors="replace")
 
-    def create(self, source, n, m, n_par, n_tab=0, n_con=0):
+    def create(self, source, n, m, n_par, n_tab=0, n_con=0, field=None):
         """n_tab > 0: a source with a per-step table of that many words; the key of one without is what it was.  n_con > 0: a cost
-        with that many constraints, whose n_tab counts their multipliers and mu: part of the key as well"""
+        with that many constraints, whose n_tab counts their multipliers and mu: part of the key as well.  field = (C, nx, ny): a
+        cost with a 2-D field -- a registration of its own every time, since the id owns the field's device buffers"""
         key = (str(source), int(n), int(m), int(n_par)) + ((int(n_tab),) if n_tab else ()) + ((int(n_con),) if n_con else ())
-        if key in self.ids:
+        if field is None and key in self.ids:
             return self.ids[key]
         uid = C.c_int32(-1)
-        rc = self._fn("create_con" if n_con else "create_tab" if n_tab else "create")(key[0].encode(), *key[1:], C.byref(uid))
+        if field is not None:
+            rc = self._fn("create_field")(key[0].encode(), *key[1:4], int(n_tab), int(n_con), *(int(v) for v in field), C.byref(uid))
+        else:
+            rc = self._fn("create_con" if n_con else "create_tab" if n_tab else "create")(key[0].encode(), *key[1:], C.byref(uid))
         if rc == ERR_COMPILE:
             raise IslsError(f"user {self.noun}: compile failed\n{self.log(uid.value) if uid.value >= self.base else ''}")
         if rc != OK:
             raise IslsError(f"isls_user_{self.noun}_create -> {rc}: {library().isls_error_string(rc).decode()}")
-        self.ids[key] = uid.value
+        if field is None:
+            self.ids[key] = uid.value
         return uid.value
 
     def n_tab(self, uid):
@@ -509,13 +522,50 @@ def user_cost_grad_build(cost_id, dtype=np.float64):
     _USER_COST.grad_build(cost_id, dtype)
 
 
-def user_cost_create(source, n, m, n_par, n_tab=0, n_con=0):
+def user_cost_create(source, n, m, n_par, n_tab=0, n_con=0, field=None):
     """Register a user cost and compile its expansion and value for gfx950 (fp64; the line-search kernels are compiled per model
     it is used with); the same (source, n, m, n_par, n_tab, n_con) is registered once per process.  n_tab > 0: the cost reads a
     table of that many words per step (isls_user_cost_create_tab; the six-argument `stage`).  n_con > 0: `source` also defines
-    `constraint` (isls_user_cost_create_con) and n_tab = W + n_con + 1: the user's W words, the multipliers and mu.  IslsError
-    carries the compile log."""
-    return _USER_COST.create(source, n, m, n_par, n_tab, n_con)
+    `constraint` (isls_user_cost_create_con) and n_tab = W + n_con + 1: the user's W words, the multipliers and mu.  field = (C, nx, ny):
+    the source may call isls::field (isls_user_cost_create_field), and every call registers a cost of its own, whose values come
+    with user_cost_set_field.  IslsError carries the compile log."""
+    return _USER_COST.create(source, n, m, n_par, n_tab, n_con, field)
+
+
+def user_cost_set_field(cost_id, values, origin, spacing, stream=None):
+    """isls_user_cost_set_field: `values` a contiguous fp64 or fp32 torch tensor [C, nx, ny] on the current device."""
+    if values.dtype not in (torch.float64, torch.float32) or not values.is_contiguous():
+        raise ValueError("user_cost_set_field: a contiguous fp64 or fp32 device tensor")
+    org, spc = (C.c_double * 2)(*(float(v) for v in origin)), (C.c_double * 2)(*(float(v) for v in spacing))
+    rc = library().isls_user_cost_set_field(C.c_int32(cost_id), C.c_void_p(values.data_ptr()), _dtype_code(values.dtype), org, spc,
+                                            C.c_void_p(stream or 0))
+    if rc != OK:
+        raise IslsError(f"isls_user_cost_set_field -> {rc}: {library().isls_error_string(rc).decode()}")
+
+
+def user_cost_field_dims(cost_id):
+    """(C, nx, ny) of the cost's field, (0, 0, 0) for a cost without one (isls_user_cost_field_dims)."""
+    c, nx, ny = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    rc = library().isls_user_cost_field_dims(C.c_int32(cost_id), C.byref(c), C.byref(nx), C.byref(ny))
+    if rc != OK:
+        raise IslsError(f"isls_user_cost_field_dims -> {rc}: {library().isls_error_string(rc).decode()}")
+    return c.value, nx.value, ny.value
+
+
+def user_cost_release_field(cost_id):
+    """Free the field's sample buffers on every device (isls_user_cost_release_field); the next user_cost_set_field allocates again."""
+    rc = library().isls_user_cost_release_field(C.c_int32(cost_id))
+    if rc != OK:
+        raise IslsError(f"isls_user_cost_release_field -> {rc}: {library().isls_error_string(rc).decode()}")
+
+
+def user_cost_field_ptr(cost_id, dtype=np.float64):
+    """The address of the field's sample buffer of dtype on the current device (None: not set there): it never moves."""
+    ptr = C.c_void_p(0)
+    rc = library().isls_user_cost_field_ptr(C.c_int32(cost_id), _dtype_code(dtype), C.byref(ptr))
+    if rc != OK:
+        raise IslsError(f"isls_user_cost_field_ptr -> {rc}: {library().isls_error_string(rc).decode()}")
+    return ptr.value
 
 
 def user_cost_code(cost_id, model=-1, dtype=np.float64):

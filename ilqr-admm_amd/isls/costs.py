@@ -93,14 +93,109 @@ class Custom(UserSource):
     `reset_multipliers(mu)`: lambda = 0, mu = mu; `constraint(x, u)`: g on the device; __call__ and get_Cs evaluate the augmented
     cost with the current multipliers (exactly `stage` while lambda = 0 and mu = 0, which is how the object starts).  Such a cost
     belongs to one iSLS at a time (a second assignment is an IslsError until the first iSLS takes another cost); assigned to an
-    iSLS of another batch or horizon afterwards, its multipliers start again at lambda = 0, mu = the last reset's."""
+    iSLS of another batch or horizon afterwards, its multipliers start again at lambda = 0, mu = the last reset's.
 
-    def __init__(self, x_dim, u_dim, params, source, table=None, constraints=0):
+    A map (a signed-distance map from an occupancy grid, a terrain height map, a risk map -- 10^4 .. 10^6 words, shared by the
+    batch and indexed by the state): `field` is [nx, ny] or [C, nx, ny] (C <= 4 channels, nx, ny >= 4), sample [c, i, j] at
+    (field_origin[0] + i field_spacing[0], field_origin[1] + j field_spacing[1]), and `stage` and `constraint` read it as
+
+        isls::field(c, px, py)        c: a plain int channel; px, py: each an S or a plain number; the result an S
+
+    with exact first and second derivatives: the tensor-product Catmull-Rom cubic (csrc/user_field.hpp), C1, exact on the samples
+    and on polynomials up to degree 2 per variable; outside the grid the field continues as a constant (zero derivative along a
+    clamped axis).  It composes with `table=` and `constraints=`: `g[0] = par[0] - isls::field(0, x[0], x[1])` keeps a car at a
+    clearance par[0] from a region known only by its distance map.  `field`: the host copy; `set_field(values)` replaces the
+    values (same shape) between two calls of a solver -- no compile, and the copy goes INTO the device buffers the cost owns.
+    Each such object is a registration of its own, and it owns device memory: an fp64 and an fp32 copy of the samples (12 bytes per
+    sample) on every device it has been used on, which garbage collection of the object does NOT free -- they live until
+    `release_field()` or the end of the process.  A program that builds many field costs (one per map) calls `release_field()` on
+    the ones it is done with; one that only changes the map keeps one object and calls `set_field`.  After `release_field()` the
+    object still works: its next use puts the host copy on the device again.  A field per trajectory is not served.  One read per step keeps the
+    fp64 line search free of scratch memory; a stage with several reads per step may spill registers there."""
+
+    def __init__(self, x_dim, u_dim, params, source, table=None, constraints=0, field=None, field_origin=(0.0, 0.0),
+                 field_spacing=(1.0, 1.0)):
         self._lam = self._mu = None                           # host copies of the multipliers [B, N, K] and penalties [B]
         self._mu_init, self._mult_version = 0.0, 0
         self._owner = None                                    # weakref to the iSLS whose device table holds the multipliers
+        shape = None
+        if field is not None:
+            self._field = self._field_values(field, None)
+            self._field_origin, self._field_spacing = (tuple(float(v) for v in np.ravel(a)) for a in (field_origin, field_spacing))
+            if len(self._field_origin) != 2 or len(self._field_spacing) != 2 or not all(np.isfinite(self._field_origin)):
+                raise ValueError("field_origin, field_spacing: (x0, y0), (dx, dy)")
+            if not all(np.isfinite(d) and d > 0 for d in self._field_spacing):
+                raise ValueError(f"field_spacing: dx, dy > 0, got {self._field_spacing}")
+            shape = self._field.shape if self._field.ndim == 3 else (1,) + self._field.shape
+            self._field_on = {}                               # device index -> the version of the values in the device buffers there
         self.cost_model = self._register("cost", capi.user_cost_create, x_dim, u_dim, params, source, table=table,
-                                         constraints=constraints)
+                                         constraints=constraints, field=shape)
+
+    # ---- the field ---------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _field_values(field, like):
+        """`field` as the fp64 host copy, checked against the limits of the registration (like=None) or the shape that stands"""
+        field = np.array(field, dtype=np.float64, order="C")
+        if like is not None:
+            if field.shape != like.shape:
+                raise ValueError(f"set_field: the field is {like.shape}, got {field.shape} (a new shape is a new costs.Custom)")
+            return field
+        if field.ndim == 4:
+            raise ValueError(f"field: [nx, ny] or [C, nx, ny], one field shared by the batch; got {field.shape} -- a field per "
+                             "trajectory is not served (put the maps into the channels, or build one cost per map)")
+        if field.ndim not in (2, 3):
+            raise ValueError(f"field: [nx, ny] or [C, nx, ny], got {field.shape}")
+        C, nx, ny = ((1,) + field.shape)[-3:]
+        if not 1 <= C <= capi.USER_MAX_FIELD:
+            raise ValueError(f"field: 1 <= C <= {capi.USER_MAX_FIELD} channels, got {C}")
+        if nx < 4 or ny < 4:
+            raise ValueError(f"field: nx, ny >= 4 (the interpolant has four taps per axis), got {nx} x {ny}")
+        if C * nx * ny > capi.USER_MAX_FIELD_WORDS:
+            raise ValueError(f"field: at most {capi.USER_MAX_FIELD_WORDS} samples over all channels, got {C * nx * ny}")
+        return field
+
+    @property
+    def field(self):
+        """The host copy of the field ([nx, ny] or [C, nx, ny] as it was given; None: a cost without one)."""
+        return self._field
+
+    @property
+    def field_origin(self):
+        return self._field_origin if self._field is not None else None
+
+    @property
+    def field_spacing(self):
+        return self._field_spacing if self._field is not None else None
+
+    def set_field(self, values):
+        """New values for the field, of the shape it has: the next call of a solver on any iSLS holding this object, and the next
+        evaluation of the object itself, use them -- no compile, one copy into the device buffers the cost owns."""
+        if self._field is None:
+            raise ValueError("set_field: this cost was built without a field")
+        self._field, self._field_version = self._field_values(values, self._field), self._field_version + 1
+
+    def release_field(self):
+        """Free the device copies of the field on every device (the host copy stays; the next use of the cost uploads it again).
+        The cost's registration and its compiled programs are kept."""
+        if self._field is None:
+            raise ValueError("release_field: this cost was built without a field")
+        capi.user_cost_release_field(self.cost_model)
+        self._field_on = {}
+
+    def _push_field(self, device=None):
+        """The values that stand into the cost's buffers on `device` (the current one), unless they are there already"""
+        if self._field is None:
+            return
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        index = torch.cuda.current_device() if dev.index is None else dev.index
+        if self._field_on.get(index) == self._field_version:
+            return
+        with torch.cuda.device(index):
+            values = torch.as_tensor(self._field, device=torch.device("cuda", index)).reshape(capi.user_cost_field_dims(self.cost_model))
+            capi.user_cost_set_field(self.cost_model, values, self._field_origin, self._field_spacing,
+                                     stream=torch.cuda.current_stream().cuda_stream)
+        self._field_on[index] = self._field_version
 
     # ---- constraints: the multipliers and the library's table ----------------------------------------------------------------
     @property
@@ -164,6 +259,7 @@ class Custom(UserSource):
         return capi.user_cost_code(self.cost_model, mid, dtype)
 
     def _load(self, dtype):
+        self._push_field()
         capi.user_cost_load(self.cost_model, -1, dtype)
 
     def _batch(self, x, u, multipliers=True):

@@ -117,6 +117,9 @@ class iSLS(Base):
         self._cost_function = function
         if hasattr(function, "cost_model"):
             self._host_cost = False
+            if getattr(function, "field", None) is not None:   # costs.Custom(field=): its samples onto this device ahead of any launch
+                function._push_field(self.engine.device)
+                self._cost_field_version = function._field_version
             table = getattr(function, "table", None)           # costs.Custom(table=): per-step data of the user's stage
             if getattr(function, "n_con", 0):
                 # costs.Custom(constraints=): the library's table [B, N, W + K + 1] = [user row | multipliers | penalty], one per
@@ -156,6 +159,13 @@ class iSLS(Base):
                 self.engine.evaluate_cost()
         elif not self._host_cost and self._sync_table(self._cost_function, "_cost_table_version", self.engine.update_cost_table):
             self.engine.evaluate_cost()
+        # set_field on the cost: the new samples go INTO the buffers its registration owns on this device (no compile either)
+        if not self._host_cost and getattr(self._cost_function, "field", None) is not None:
+            f = self._cost_function
+            f._push_field(self.engine.device)
+            if f._field_version != self._cost_field_version:
+                self._cost_field_version = f._field_version
+                self.engine.evaluate_cost()
 
     def _sync_al_table(self):
         """The same for a cost with constraints, whose device table is [user row (W) | multipliers (K) | penalty]: set_table

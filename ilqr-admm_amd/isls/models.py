@@ -176,7 +176,10 @@ class UserSource:
 
     n_con = 0                                                # path constraints of a cost (costs.Custom(constraints=)), 0: none
 
-    def _register(self, noun, create, x_dim, u_dim, params, source, table=None, constraints=0):
+    _field = None                                            # the 2-D field of a cost (costs.Custom(field=)): [C, nx, ny]
+    _field_version = 0
+
+    def _register(self, noun, create, x_dim, u_dim, params, source, table=None, constraints=0, field=None):
         self._noun, self.x_dim, self.u_dim = noun, int(x_dim), int(u_dim)
         K = int(constraints)
         if K < 0:
@@ -206,6 +209,8 @@ class UserSource:
         if re.search(r"\b(asm|__asm|__asm__)\b", source) or "__builtin_amdgcn" in source:
             raise capi.IslsError(f"a user {noun} is plain arithmetic: `asm` and `__builtin_amdgcn_*` are not accepted")
         self.source = source
+        if field is not None:                                # (C, nx, ny): a cost of its own registration, which owns the field's buffers
+            return create(source, self.x_dim, self.u_dim, P, self.n_tab + (K + 1 if K else 0), K, field=field)
         if K:
             return create(source, self.x_dim, self.u_dim, P, self.n_tab + K + 1, K)
         if table is not None:
@@ -278,7 +283,9 @@ class Custom(UserSource, Model):
     linearised at every iteration.  Served: solve / iterate_once_dp / solve_ilqr / ilqr_admm, mpc (model_table_future=,
     plant_table=) and sample_nominal; monte_carlo, isls_admm and the dense closed loop refuse it."""
 
-    def __init__(self, x_dim, u_dim, params, source, table=None):
+    def __init__(self, x_dim, u_dim, params, source, table=None, field=None):
+        if field is not None:
+            raise ValueError("field=: a 2-D field belongs to a cost (costs.Custom(field=)); a forward model cannot read one")
         par, tab = np.atleast_1d(np.asarray(params)), None if table is None else np.asarray(table)
         if tab is not None and par.ndim == 2 and tab.ndim == 3 and tab.shape[0] != par.shape[0]:
             raise ValueError(f"per-trajectory params [{par.shape[0]}, P] and a per-trajectory table [{tab.shape[0]}, N, W]: "

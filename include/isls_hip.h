@@ -76,6 +76,8 @@ extern "C" {
 #define ISLS_MODEL_USER_BASE 1024
 #define ISLS_USER_MAX_PAR 16        /* parameters of a user model, at most                                             */
 #define ISLS_USER_MAX_TAB 16        /* words per step of a user cost's or a user model's table, at most (isls_user_*_create_tab) */
+#define ISLS_USER_MAX_FIELD 4       /* channels of a user cost's 2-D field, at most (isls_user_cost_create_field) */
+#define ISLS_USER_MAX_FIELD_WORDS (1 << 24) /* samples of such a field over all its channels, at most */
 #define ISLS_DTYPE_F64 0
 #define ISLS_DTYPE_F32 1
 
@@ -897,6 +899,45 @@ int isls_user_cost_n_tab(int32_t id);
 int isls_user_cost_create_con(const char *source, int32_t n, int32_t m, int32_t n_par, int32_t n_tab, int32_t n_con, int32_t *id);
 /* Constraints of the cost (0: a cost without), or ISLS_ERR_ARG for an id nobody registered. */
 int isls_user_cost_n_con(int32_t id);
+/* A 2-D field with derivatives for `stage` and `constraint`: a signed-distance map, a terrain height map, a risk map -- data of
+ * 10^4 .. 10^6 words, shared by the batch and indexed by the state, which neither the parameters nor a table row can hold.  A
+ * cost registered with n_field = C >= 1 channels of nx x ny samples may call, in both functions,
+ *   isls::field(c, px, py)        c: a plain int channel (clamped to [0, C)); px, py: each an S or a plain number; the result an S
+ * Sample [c, i, j] sits at (origin[0] + i spacing[0], origin[1] + j spacing[1]).  The interpolant is the tensor-product cubic
+ * convolution with Keys' kernel at a = -1/2 (Catmull-Rom; csrc/user_field.hpp has the weights): C1, exact on the samples and on
+ * polynomials up to degree 2 in each variable, first and second derivatives exact for every type of the contract.  Outside the
+ * grid the field continues as a constant: the position is clamped per axis, and where the clamp acts the derivative along that
+ * axis is zero.  The other arguments are those of isls_user_cost_create_con (n_tab = n_con = 0: neither).  A source that calls
+ * isls::field in a cost registered WITHOUT a field does not compile (isls::field exists only in the programs of a field cost),
+ * and the log ends with a sentence that says so.  The samples are never differentiated.
+ * ISLS_ERR_UNSUPPORTED: n_field outside [1, ISLS_USER_MAX_FIELD], nx < 4, ny < 4, n_field * nx * ny > ISLS_USER_MAX_FIELD_WORDS.
+ * Needs no GPU; the field's values come with isls_user_cost_set_field.  Unlike the other creates' ids, the id owns device memory. */
+int isls_user_cost_create_field(const char *source, int32_t n, int32_t m, int32_t n_par, int32_t n_tab, int32_t n_con,
+                                int32_t n_field, int32_t nx, int32_t ny, int32_t *id);
+/* The values of the field: `values` [n_field, nx, ny] of dtype_of_values (ISLS_DTYPE_*) on the current device.  The library keeps
+ * an fp64 and an fp32 copy in two buffers the registration owns on that device (allocated by the first call there; the copy of
+ * the other precision is made by one small conversion kernel), and every later call overwrites them in place on `stream` -- no
+ * compile, and no module's descriptor changes while origin and spacing stay what they were.  The first call on a device, and
+ * one with another origin or spacing, also write the descriptor of every module of the cost loaded there, after what runs on
+ * `stream` has ended (not inside a stream capture); modules loaded later get it as they load.
+ * ISLS_ERR_ARG: an id nobody registered, a cost without a field, values / origin / spacing NULL, a spacing <= 0 or not finite.
+ * ISLS_ERR_LAUNCH, before anything is enqueued: a first call on the device or a new grid while `stream` is capturing.
+ * A NaN position gives NaN (value and derivatives; it reads cell 0, so no index leaves the buffers): under ISLS_RO_NAN_TO_1E5 a
+ * diverged candidate of the line search is costed as one, as with any other stage.
+ * Every launch that costs a step with a field cost (line search, expansion, value, multiplier update, sampling, isls_mpc_step_*,
+ * isls_user_cost_grad_*) returns ISLS_ERR_ARG, before anything is launched, on a device where the field was never set. */
+int isls_user_cost_set_field(int32_t id, const void *values, int32_t dtype_of_values, const double origin[2], const double spacing[2],
+                             void *stream);
+/* C, nx, ny of the cost's field (0, 0, 0: a cost without one); ISLS_ERR_ARG for an id nobody registered. */
+int isls_user_cost_field_dims(int32_t id, int32_t *n_field, int32_t *nx, int32_t *ny);
+/* The sample buffer of `dtype` on the current device (*ptr = NULL: not set there): it never moves once allocated.  ISLS_ERR_ARG:
+ * no such id, a cost without a field. */
+int isls_user_cost_field_ptr(int32_t id, int32_t dtype, void **ptr);
+/* Lifetime: the two sample buffers (12 bytes per sample and device, about 200 MB at the limit) live until this call or the end of
+ * the process -- the registry of user costs has no destroy.  isls_user_cost_release_field frees them on every device (it waits for
+ * what still reads them); the registration, its programs and its loaded modules stay, the field is set nowhere afterwards (a
+ * launch: ISLS_ERR_ARG), and the next isls_user_cost_set_field allocates again.  ISLS_ERR_ARG: no such id, a cost without a field. */
+int isls_user_cost_release_field(int32_t id);
 /* The multiplier and penalty update of such a cost along a trajectory, one launch for the batch (one wavefront per trajectory).
  * Per trajectory b with active[b] != 0 (NULL: all), with g = constraint(xhat_t, uhat_t) and the mu the table came with:
  *   g_out[b, t, i] = g_i (g_out nullable) ;  v_t = max_i max(0, g_i), +inf where a g_i is NaN ;  viol[b] = max_t v_t ;
